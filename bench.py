@@ -1,6 +1,6 @@
 """bench.py -- train samples/sec of the GAN-DANet G+D step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one full G+D update (generator forward/backward with PAM/CAM attention, three discriminator
@@ -8,6 +8,18 @@ passes, TV + perceptual(VGG19 random-init) + MSE + BCE losses, SSIM evaluation, 
 synthetic 8-channel 256x256 tiles -> 1024x1024, batch 32 per GPU (BASELINE.json configs[2]; config 3 of
 SURVEY.md 8d), bf16 MFMA operands / fp32 accumulate and storage.  Weak scaling: per-GPU batch fixed,
 gradients all-reduced with RCCL.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (value = samples/s, ms_per_step = one timed step).
+--full adds the side measurements: the per-kernel HIP-event roofline of the timed steps, the generator's output error on
+the reference fixture (g_out_rel_err) and the CPU-oracle baseline (cpu_baseline; --no-cpu-baseline drops it).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32; an output of more than 2^22
+elements as a fixed, seeded sample of 2^22 of them).
+
+Every step, warm-up and timed, starts from the same seeded state: inputs, weights and buffers are seeded, and the
+parameters, buffers and AdamW moments are restored before each step, outside its timed interval (HIP events bracket each
+step).  A chain of training steps would not be reproducible: the default kernels add split reductions with fp32 atomics,
+and training amplifies that rounding from step to step (two runs' generator outputs measured 18 % apart after 3 steps).
+With the same arguments, every run therefore computes the same step from the same inputs.
 
 --config selects the other measured configurations of SURVEY.md 8d (default 3 = the metric's own):
     2   DANetAttention(64) FORWARD on a (B, 64, 128, 128) feature map, bf16 (attention bring-up; step = one forward)
@@ -47,11 +59,17 @@ def parse():
     ap.add_argument("--precision", default=None, choices=["bf16", "fp16", "fp32", "mixed"])
     ap.add_argument("--no-perceptual", action="store_true", help="exploration only; the reported config has it on")
     ap.add_argument("--no-disc", action="store_true", help="config 5 only: generator forward + backward + AdamW, no discriminator")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the roofline, g_out_rel_err and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-steps", type=int, default=4)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                     "the multi-rank path on a one-GPU box, all ranks on cuda:0)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_baseline(nsteps: int):
@@ -111,6 +129,43 @@ def g_out_rel_err(gd, dev, precision):
     return {"fixture": "tests/golden/generator_8ch_16x16.npz (output of the reference generator)",
             "rel_l2": float((y - ref).norm() / ref.norm()), "rel_max": float((y - ref).abs().max() / ref.abs().max()),
             "north_star": "1e-3 (held by --precision fp32: 4e-6; --precision mixed: 6.5e-5 at full size; 16-bit operand modes: see profiles/r03_parity_attribution.json)"}
+
+
+def seeded_state_reset(modules, optimizers=(), sharded=()):
+    """snapshot of the parameters and buffers of ``modules`` as they are now; the returned reset() copies them back and
+    puts the AdamW ``optimizers`` back to their first step (moments zero), so that the next step starts from this state.
+    ``sharded``: parallel.ShardedParam objects whose all-gather of updated weights may still be in flight."""
+    live = [t for m in modules for t in list(m.parameters()) + list(m.buffers())]
+    saved = [t.detach().clone() for t in live]
+
+    @torch.no_grad()
+    def reset():
+        for sp in sharded:
+            sp.wait_param()
+        for t, s in zip(live, saved):
+            t.copy_(s)
+        for opt in optimizers:
+            for st in opt.state.values():
+                if st:
+                    st["step"] = 0
+                    st["exp_avg"].zero_()
+                    st["exp_avg_sq"].zero_()
+    return reset
+
+
+DUMP_ELEMS = 1 << 22     # per output: larger ones are written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    """arrays (name -> tensor) as outdir/<name>.npy in float32; at most 2^22 elements (16 MB) each"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_ELEMS:
+            idx = torch.randint(t.numel(), (DUMP_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.float().cpu().numpy())
 
 
 def launch_ranks(args) -> int:
@@ -184,6 +239,7 @@ def main():
     torch.manual_seed(1234)
     perc = None
     extra = {}
+    last = {}                                   # what the latest step returned (--dump-outputs)
 
     if cfg == 2:
         # ---- BASELINE config 2: DANetAttention(64) forward on (B, 64, T, T) ----
@@ -197,10 +253,13 @@ def main():
         broadcast_module(A)
         A.train()
         x = torch.randn(B, C2, T, T, device=dev, generator=gen)
+        reset = seeded_state_reset([A])
 
         def step():
             with torch.no_grad():
-                return A(x)
+                y = A(x)
+            last["arrays"] = {"y": y}
+            return y
         workload = (f"DANetAttention({C2}) forward (PAM N={T * T} d_qk={C2 // 8} + CAM + fuse conv3x3/BN/ReLU) on "
                     f"({B},{C2},{T},{T}), batch {B}/GPU")
         metric = f"attention-forward samples/sec, DANetAttention(64) on {T}x{T}x64 feature maps"
@@ -218,6 +277,7 @@ def main():
         red = GradReducer(G.parameters())
         x = torch.randn(B, Cin, T, T, device=dev, generator=gen)
         target = torch.randn(B, 1, 4 * T, 4 * T, device=dev, generator=gen)
+        reset = seeded_state_reset([G], [opt])
 
         def step():
             opt.zero_grad(set_to_none=True)
@@ -226,6 +286,7 @@ def main():
             loss.backward()
             red.reduce()
             opt.step()
+            last["arrays"] = {"loss": loss.detach(), "hr": hr.detach()}
             return loss.detach()
         workload = (f"generator forward + backward + AdamW (MSE + TV loss), {Cin}ch {T}x{T} -> {4 * T}x{4 * T} tiles, "
                     f"PAM N={T * T} tokens with fp16 MFMA operands, batch {B}/GPU (global {B * world}); discriminator "
@@ -256,11 +317,14 @@ def main():
         # synthetic shard, resident in HBM before the timed region
         x = torch.randn(B, Cin, T, T, device=dev, generator=gen)
         target = torch.randn(B, 1, 4 * T, 4 * T, device=dev, generator=gen)
-        last = {}
+        reset = seeded_state_reset([G, D], [trainer.opt_d, trainer.opt_g], trainer.sharded)
 
         def step():
-            last["out"] = trainer.step(x, target, 0.5)
-            return last["out"].loss_g
+            out = trainer.step(x, target, 0.5)
+            last["out"] = out
+            last["arrays"] = {"loss_d": out.loss_d, "loss_g": out.loss_g, "hr": out.hr,
+                              **{f"parts_{k}": v for k, v in out.parts.items()}}
+            return out.loss_g
         workload = (f"full G+D train step, {Cin}ch {T}x{T} -> {4 * T}x{4 * T} tiles, batch {B}/GPU (global {B * world}), "
                     f"perceptual={'on' if perc is not None else 'OFF'}, SSIM evaluated, AdamW x2")
         if cfg == 5:
@@ -276,15 +340,21 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
+        reset()
         step()
     sync()
     kern.PROFILE.clear()
-    kern.PROFILE_ON = True
-    t0 = time.perf_counter()
+    kern.PROFILE_ON = args.full                 # HIP-event brackets around the kernels: the roofline of --full
+    marks = []
     for _ in range(args.steps):
+        reset()                                 # enqueued ahead of the step, outside its events
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
         res_t = step()
+        e1.record()
+        marks.append((e0, e1))
     sync()
-    dt = time.perf_counter() - t0
+    dt = sum(e0.elapsed_time(e1) for e0, e1 in marks) * 1e-3
     kern.PROFILE_ON = False
     if world > 1:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -298,6 +368,8 @@ def main():
         finite = finite and bool(torch.isfinite(out.loss_d).all())
     elif cfg == 5 and args.no_disc:
         extra = {"loss": res_t.item()}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["arrays"])
 
     # ---- roofline of the dominant kernel from the HIP-event brackets recorded around its launches ----
     # `traffic` = HBM bytes per launch from the PMC counters (FETCH_SIZE doubled per MI355X_MICROARCH.md + WRITE_SIZE),
@@ -305,11 +377,11 @@ def main():
     roof = None
     traffic, traffic_commit = {}, None
     tpath = os.path.join(ROOT, "profiles", "r03_pam_traffic.json")
-    if os.path.exists(tpath) and cfg in (3, 4) and B == 32 and T == 256:
+    if args.full and os.path.exists(tpath) and cfg in (3, 4) and B == 32 and T == 256:
         with open(tpath) as f:
             tj = json.load(f)
         traffic, traffic_commit = tj.get("traffic_bytes_per_launch", {}), tj.get("commit")
-    stats = kern.profile_summary()
+    stats = kern.profile_summary() if args.full else None
     if stats:
         name, (n_launch, ms_avg, flops, nbytes) = max(stats.items(), key=lambda kv: kv[1][0] * kv[1][1])
         ach = flops / (ms_avg * 1e-3) / 1e12
@@ -327,7 +399,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_baseline_steps)
         res = {
             "metric": metric,
@@ -356,11 +428,10 @@ def main():
                            args.precision, "fp32 activations/weights, 16-bit MFMA operands (" + args.precision +
                            "; generator stem conv exact, 1x1-shaped products on split-bf16 operands), fp32 accumulate")},
             **extra, "finite": finite,
-            "g_out_rel_err": g_out_rel_err(gd, dev, args.precision),
-            "roofline": roof,
-            "cpu_baseline": cpu,
             "max_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
         }
+        if args.full:
+            res.update({"g_out_rel_err": g_out_rel_err(gd, dev, args.precision), "roofline": roof, "cpu_baseline": cpu})
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()

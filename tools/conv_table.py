@@ -1,4 +1,4 @@
-"""Per-shape convolution time table of one bench step: GD_PROFILE_CONV=1 python tools/conv_table.py < bench-json-line"""
+"""Per-shape convolution time table of one bench step: python tools/conv_table.py < the JSON line of GD_PROFILE_CONV=1 python bench.py --full"""
 import json
 import sys
 

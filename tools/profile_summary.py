@@ -4,7 +4,7 @@
     python tools/profile_summary.py pmc   <rocprof dir>                counter CSVs    -> per-kernel per-dispatch means
 
 Recipes (on the GPU box; `cd /tmp && export TMPDIR=/tmp` is not needed under gpurun):
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_stats -- python3 bench.py --steps 4 --warmup 2
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python3 bench.py --full --steps 4 --warmup 2
     rocprofv3 -i tools/pmc_r02.txt --kernel-trace --output-format csv -d gpurun_out/prof_pmc -- python3 tools/pam_bench.py --batch 2 --iters 1
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/prof_fetch -- python3 tools/pam_bench.py --batch 2 --iters 1
     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/prof_write -- python3 tools/pam_bench.py --batch 2 --iters 1
