@@ -873,6 +873,38 @@ def pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Npad, Cp, dqn, dkn, dv
                                        _ptr(scratch), scratch_bytes, _stream()), "gd_pam_flash_bwd")
 
 
+# wide attention blocks (192 < C <= 511, gd_pam_wide_*): GD_PAM_WIDE=0 keeps them on the product chain (A/B runs)
+PAM_WIDE = os.environ.get("GD_PAM_WIDE", "1") != "0"
+
+
+def pam_wide_slots(r: int) -> int:
+    """q / k slots of the wide kernels: 32 while the spare slot for the running maximum fits (r <= 31), else 64"""
+    return 32 if r <= 31 else 64
+
+
+def pam_wide_fwd(qt, kt, v, B, N, Npad, Cn, Cp, D, gamma, x, out, o_attn, lse, r_alg: int, f16: bool = False):
+    with _Bracket("pam_wide_fwd", 2.0 * N * N * (r_alg + Cn) * B):
+        L.check(lib().gd_pam_wide_fwd(_ptr(qt), _ptr(kt), _ptr(v), B, N, Npad, Cn, Cp, D, int(f16), _ptr(gamma), _ptr(x),
+                                      _bview(x), _ptr(out), _bview(out), _ptr(o_attn), _ptr(lse), _stream()),
+                "gd_pam_wide_fwd")
+
+
+def pam_wide_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Npad, Cp, D, dqn, dkn, dv, r_alg: int, c_alg: int,
+                 f16: bool = False, deterministic: Optional[bool] = None):
+    """dQ through fp32 atomics, or (set_deterministic / ``deterministic``) bf16 parts per key block + a reduction pass"""
+    det = DETERMINISTIC if deterministic is None else bool(deterministic)
+    scratch, scratch_bytes = None, 0
+    per_image = int(lib().gd_pam_wide_scratch_bytes(Npad, D, int(det)))
+    if per_image:
+        nslices = -(-(B * per_image) // PAM_SCRATCH_CAP)
+        scratch_bytes = per_image * max(1, -(-B // nslices))
+        scratch = torch.empty(scratch_bytes, device=dqn.device, dtype=torch.uint8)
+    with _Bracket("pam_wide_bwd", 4.0 * N * N * (r_alg + c_alg) * B):
+        L.check(lib().gd_pam_wide_bwd(_ptr(qt), _ptr(kt), _ptr(kn), _ptr(vt), _ptr(dot_), _ptr(lse), _ptr(delta), B, N,
+                                      Npad, Cp, D, int(f16), int(det), _ptr(dqn), _ptr(dkn), _ptr(dv), _ptr(scratch),
+                                      scratch_bytes, _stream()), "gd_pam_wide_bwd")
+
+
 # =====================================================================================================
 # NHWC bf16 kernels (frozen VGG19 feature stack of PerceptualLoss)
 # =====================================================================================================

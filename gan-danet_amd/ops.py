@@ -428,14 +428,24 @@ def _cp(c: int) -> int:
     return (c + 31) // 32 * 32
 
 
+PAM_WIDE_ROUTE = "wide"     # _pam_forward's route tag for the wide kernels (truthy like the narrow route's True)
+
+
+def _pam_wide(Cn: int, r: int) -> bool:
+    """16-bit modes, 192 < C <= 511 (r <= 63): the wide flash kernels (gd_pam_wide_*) instead of the product chain"""
+    return K.PAM_WIDE and sixteen_bit("pam") and 192 < Cn <= 511 and r <= 63
+
+
 def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
-    """PAM into ``out3`` (B, C, N) view.  Returns (fused?, tensors to keep for backward)."""
+    """PAM into ``out3`` (B, C, N) view.  Returns (route: True = flash, PAM_WIDE_ROUTE = wide flash, False = product
+    chain; tensors to keep for backward)."""
     B, Cn, H, W = x.shape
     N = H * W
     r = wq.shape[0]
     x3 = x.view(B, Cn, N)
     fused = sixteen_bit("pam") and Cn <= 192 and r <= 31
-    if fused and PAM_CAT and (bq is None) == (bk is None) == (bv is None):
+    wide = not fused and _pam_wide(Cn, r)
+    if (fused or wide) and PAM_CAT and (bq is None) == (bk is None) == (bv is None):
         # q, k, v as ONE 1x1 conv over the concatenated weights: x is read once instead of three times
         wc = torch.empty(2 * r + Cn, Cn, 1, 1, device=x.device, dtype=torch.float32)
         for w_, lo in ((wq, 0), (wk, r), (wv, 2 * r)):
@@ -471,6 +481,20 @@ def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
             K.pam_flash_fwd(qt, kt, vn, B, N, Np, Cn, Cp, gamma_p, x3, out3, o_attn, lse, r_alg=r, v_ones=ones >= 0, f16=f16,
                             k_sqmax=k_sqmax)
         return True, (qt, kt, kn, vt, o_attn, lse)
+    if wide:
+        # q / k in D = 32 or 64 slots (k's last slot = 1.0 carries the running maximum), V without a ones row: the
+        # kernels split it into channel chunks of <= 192 and sum each chunk's softmax denominator on the VALU
+        Np, Cp, D = _npad(N), _cp(Cn), K.pam_wide_slots(r)
+        f16 = _pam_f16()
+        _, qt = K.pack_bf16(q, r, N, scale_imm=K.LOG2E, t_shape=(Np, D), f16=f16)
+        kn, kt = K.pack_bf16(k, r, N, plain_shape=(D, Np), t_shape=(Np, D), perm16=True, ones_row=D - 1, f16=f16)
+        vn, vt = K.pack_bf16(v, Cn, N, plain_shape=(Cp, Np), t_shape=(Np, Cp), perm16=True, f16=f16)
+        del q, k, v
+        y3 = None
+        o_attn = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
+        lse = torch.empty(B, N, device=x.device, dtype=torch.float32)
+        K.pam_wide_fwd(qt, kt, vn, B, N, Np, Cn, Cp, D, gamma_p, x3, out3, o_attn, lse, r_alg=r, f16=f16)
+        return PAM_WIDE_ROUTE, (qt, kt, kn, vt, o_attn, lse)
     prec = prec if sixteen_bit("pam") else L.PREC_FP32     # the reference-shaped product chain below
     qt_, kt_ = K.transpose(q), K.transpose(k)              # (B, N, r)
     s = torch.empty(B, N, N, device=x.device, dtype=torch.float32)
@@ -504,7 +528,13 @@ def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
             scales = K.pam_f16_scale(d_pam, gamma_p, delta)
             s_up, s_inv = scales[0:1], scales[1:2]
         _, dot_ = K.pack_bf16(d_pam, Cn, N, scale=s_up, t_shape=(Np, Cp), f16=f16)
-        if PAM_CAT and Np == N and K.pam_bwd_form() == L.PAM_BWD_K64_ATOMIC:
+        if fused == PAM_WIDE_ROUTE:
+            D = qt.shape[2]
+            dqn = torch.empty(B, D, Np, device=x.device, dtype=torch.float32)
+            dkn = torch.empty(B, D, Np, device=x.device, dtype=torch.float32)
+            dvp = torch.empty(B, Cp, Np, device=x.device, dtype=torch.float32)
+            K.pam_wide_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, D, dqn, dkn, dvp, r_alg=r, c_alg=Cn, f16=f16)
+        elif PAM_CAT and Np == N and K.pam_bwd_form() == L.PAM_BWD_K64_ATOMIC:
             # dq | dk | dv as row blocks of ONE buffer: the three projection data / weight / bias gradients below become
             # one GEMM each over it (dx read-modify-written once instead of three times, x read once)
             R = 64 + Cp
@@ -525,10 +555,11 @@ def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
                 grads.append(dwc[lo:lo + n])
                 grads.append(dbc[lo:lo + n] if hb else None)
             return (*grads, dgamma_p)
-        dqn = torch.empty(B, 32, Np, device=x.device, dtype=torch.float32)
-        dkn = torch.empty(B, 32, Np, device=x.device, dtype=torch.float32)
-        dvp = torch.empty(B, Cp, Np, device=x.device, dtype=torch.float32)
-        K.pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, dqn, dkn, dvp, r_alg=r, c_alg=Cn, f16=f16)
+        else:
+            dqn = torch.empty(B, 32, Np, device=x.device, dtype=torch.float32)
+            dkn = torch.empty(B, 32, Np, device=x.device, dtype=torch.float32)
+            dvp = torch.empty(B, Cp, Np, device=x.device, dtype=torch.float32)
+            K.pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, dqn, dkn, dvp, r_alg=r, c_alg=Cn, f16=f16)
         if s_inv is not None:
             for t in (dqn, dkn, dvp):
                 K.scale_dev(t, s_inv, out=t)

@@ -393,6 +393,24 @@ void gd_pam_k64_debug(void* buf);
 int gd_pam_flash_bwd(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
                      const float* lse, const float* delta, int B, int N, int Npad, int Cp, int f16, int form,
                      float* dqn, float* dkn, float* dv, long out_bs, void* scratch, size_t scratch_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * PAM, fused form for WIDE attention blocks (generator.py:115-122 at 192 < C <= 511: FlexibleUpsamplingModule with a larger
+ * growth_rate / num_layers_per_block, generator.py:178-186).  Operand contract as gd_pam_flash_fwd / _bwd with
+ *   D      : q / k slots, 32 (r <= 31) or 64 (r <= 63); qt, kt (B, Npad, D), kt's slot D - 1 = 1.0 (gd_pack_16 ones_row = D - 1),
+ *            kn (B, D, Npad) perm16
+ *   Cp     : C rounded up to 32, 192 < Cp <= 512; v (B, Cp, Npad) perm16 WITHOUT a ones row; vt, dot (B, Npad, Cp)
+ * The value channels are processed in chunks of at most 192 (forward: one sweep per chunk, each recomputing S; backward: a
+ * dK / dQ kernel over all channels and one dV kernel per chunk).  No N x N buffer.  Outputs as the narrow kernels, with
+ * dqn, dkn (B, D, Npad).  deterministic = 0: dQ summed with fp32 atomics, no scratch; 1: bf16 parts per 128-key block
+ * summed in a second pass (bitwise reproducible), scratch >= gd_pam_wide_scratch_bytes(Npad, D, 1) (one image's worth). */
+int gd_pam_wide_fwd(const void* qt, const void* kt, const void* v, int B, int N, int Npad, int C, int Cp, int D, int f16,
+                    const float* gamma, const float* x, long x_bs, float* out, long out_bs, float* o_attn, float* lse,
+                    void* stream);
+/* backward of gd_pam_wide_fwd (autograd of generator.py:115-122) */
+size_t gd_pam_wide_scratch_bytes(int Npad, int D, int deterministic);
+int gd_pam_wide_bwd(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_, const float* lse,
+                    const float* delta, int B, int N, int Npad, int Cp, int D, int f16, int deterministic, float* dqn,
+                    float* dkn, float* dv, void* scratch, size_t scratch_bytes, void* stream);
 
 /* test.ipynb c1:69-85 mild_histogram_matching, per sample of a batch: out[b] = (1 - weight) * src[b] + weight *
  * interp(cdf_src(src[b]), cdf_ref, sorted unique ref[b]) with numpy's np.unique / np.interp semantics (float64 result, as
