@@ -24,8 +24,9 @@ class _Config:
     #           use split-bf16 operands (three bf16 MFMAs per product: still free), the stem conv the exact f32 MFMA;
     #   "fp16"  BASELINE config 5: the fused PAM kernels take IEEE fp16 operands (v_mfma_f32_32x32x16_f16), every other
     #           kernel runs as in "bf16";
-    #   "fp32"  exact v_mfma_f32_32x32x2_f32 everywhere, PAM as the reference's unfused product chain (materialised
-    #           N x N matrices: small tiles only);
+    #   "fp32"  exact v_mfma_f32_32x32x2_f32 everywhere; PAM as the reference's unfused product chain while its N x N
+    #           matrices are small, as the fused flash kernels on exact fp32 operands (gd_pam_f32_*, no N x N buffer) once
+    #           one would pass 2^31 elements (GD_PAM_F32_FLASH = 1 / 0: always / never);
     #   "mixed" the mode that holds the north-star 1e-3 AT the benchmark size: the fused flash PAM (fp16 operands, fp32
     #           accumulate / softmax statistics) and every other product in split-bf16 ("x3": hi*hi + lo*hi + hi*lo,
     #           2^-16 relative); exact f32 MFMA only where it is free (stem, nn.Linear, weight-space products).

@@ -215,9 +215,10 @@ def gemm_nt(*, B: int, M: int, N: int, kseg: int, klen: int, a: Tensor, a_bs: in
 
 
 def conv2d_wgrad(dy: Tensor, x: Tensor, k: int, stride: int, pad: int, precision: int, *, in_scale=None,
-                 in_shift=None, in_relu=False, alpha: Optional[Tensor] = None) -> Tensor:
+                 in_shift=None, in_relu=False, alpha: Optional[Tensor] = None, splits: int = 0) -> Tensor:
     """Gradient of nn.Conv2d w.r.t. its OIHW weight: dW[co][ci,kh,kw] = sum_{b,p} dy[b,co,p] x~[b,ci,p(+)tap].
-    ``alpha`` (1x1 convs only): device scalar multiplying the result."""
+    ``alpha`` (1x1 convs only): device scalar multiplying the result; ``splits`` (1x1 convs only): k-splits of the GEMM
+    (0 = chosen by the kernel and combined with atomics, 1 = unsplit: bitwise reproducible)."""
     if alpha is not None and not (k == 1 and stride == 1 and pad == 0):
         raise L.GandanetError("conv2d_wgrad: alpha is supported for 1x1 convs only")
     dbs, xbs = _bview(dy, "wgrad dy"), _bview(x, "wgrad x")
@@ -226,11 +227,11 @@ def conv2d_wgrad(dy: Tensor, x: Tensor, k: int, stride: int, pad: int, precision
     dw = torch.empty(Cout, Cin, k, k, device=dy.device, dtype=torch.float32)
     with _ConvBracket("wgrad", k, stride, Cin, Cout, Ho, Wo, B):
         return _conv2d_wgrad(dy, x, k, stride, pad, precision, in_scale, in_shift, in_relu, dw, dbs, xbs, B, Cout, Cin, Hi,
-                             Wi, Ho, Wo, alpha)
+                             Wi, Ho, Wo, alpha, splits)
 
 
 def _conv2d_wgrad(dy, x, k, stride, pad, precision, in_scale, in_shift, in_relu, dw, dbs, xbs, B, Cout, Cin, Hi, Wi, Ho, Wo,
-                  alpha=None):
+                  alpha=None, splits=0):
     if USE_CONV3X3_FAST and k == 3 and stride in (1, 2) and pad == 1 and precision == L.PREC_BF16:
         dy16 = x16 = None
         x_ld = 0
@@ -251,7 +252,7 @@ def _conv2d_wgrad(dy, x, k, stride, pad, precision, in_scale, in_shift, in_relu,
         # BN affine (+ReLU) of the input is a per-row transform of the B operand
         gemm_nt(B=1, M=Cout, N=Cin, kseg=B, klen=Ho * Wo, a=dy, a_bs=0, a_ss=dbs, lda=Ho * Wo, bm=x, b_bs=0, b_ss=xbs,
                 ldb=Hi * Wi, c=dw, c_bs=0, ldc=Cin, precision=precision, in_scale=in_scale, in_shift=in_shift,
-                in_relu=in_relu, alpha=alpha)
+                in_relu=in_relu, alpha=alpha, splits=splits)
         return dw
     gemm_nt(B=1, M=Cout, N=Cin * k * k, kseg=B, klen=Ho * Wo, a=dy, a_bs=0, a_ss=dbs, lda=Ho * Wo, bm=x, b_bs=0,
             b_ss=xbs, ldb=0, c=dw, c_bs=0, ldc=Cin * k * k, precision=precision,
@@ -903,6 +904,38 @@ def pam_wide_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Npad, Cp, D, dqn, dkn, 
         L.check(lib().gd_pam_wide_bwd(_ptr(qt), _ptr(kt), _ptr(kn), _ptr(vt), _ptr(dot_), _ptr(lse), _ptr(delta), B, N,
                                       Npad, Cp, D, int(f16), int(det), _ptr(dqn), _ptr(dkn), _ptr(dv), _ptr(scratch),
                                       scratch_bytes, _stream()), "gd_pam_wide_bwd")
+
+
+# exact-operand PAM (operand mode "exact": set_precision("fp32"), layer_override(pam="exact")) through the fused fp32
+# kernels (gd_pam_f32_*) instead of the product chain.  GD_PAM_F32_FLASH=1 always (C <= 511), 0 never, unset = auto: only
+# where one of the chain's N x N matrices would pass PAM_F32_AUTO_ELEMS elements (B N^2 > 2^31 = 8 GiB)
+_f32_flash = os.environ.get("GD_PAM_F32_FLASH", "")
+PAM_F32_FLASH: Optional[bool] = True if _f32_flash == "1" else False if _f32_flash == "0" else None
+PAM_F32_AUTO_ELEMS = 1 << 31
+
+
+def _plane_bs(t: Tensor, name: str) -> int:
+    """(B, R, Npad) fp32 plane whose rows are dense; returns its batch stride"""
+    _chk(t, name)
+    if t.dim() != 3 or t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+        raise L.GandanetError(f"{name}: expected (B, rows, Npad) with dense rows, got strides {t.stride()}")
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]
+
+
+def pam_f32_fwd(q, k, v, B, N, Npad, Cn, r, gamma, x, out, o_attn, lse):
+    """q, k (B, r, Npad), v (B, Cn, Npad) fp32 planes (zero columns past N); see gd_pam_f32_fwd"""
+    with _Bracket("pam_f32_fwd", 2.0 * N * N * (r + Cn) * B):
+        L.check(lib().gd_pam_f32_fwd(_ptr(q), _plane_bs(q, "q"), _ptr(k), _plane_bs(k, "k"), _ptr(v), _plane_bs(v, "v"), B, N,
+                                     Npad, Cn, r, _ptr(gamma), _ptr(x), _bview(x), _ptr(out), _bview(out), _ptr(_dense(o_attn)),
+                                     _ptr(_dense(lse)), _stream()), "gd_pam_f32_fwd")
+
+
+def pam_f32_bwd(q, k, v, gdo, lse, delta, B, N, Npad, Cn, r, dq, dk, dv):
+    """gdo (B, Cn, Npad) = gamma * dOut; dq, dk (B, r, N), dv (B, Cn, N) dense; see gd_pam_f32_bwd"""
+    with _Bracket("pam_f32_bwd", 4.0 * N * N * (r + Cn) * B):
+        L.check(lib().gd_pam_f32_bwd(_ptr(q), _plane_bs(q, "q"), _ptr(k), _plane_bs(k, "k"), _ptr(v), _plane_bs(v, "v"),
+                                     _ptr(gdo), _plane_bs(gdo, "gdo"), _ptr(_dense(lse)), _ptr(_dense(delta)), B, N, Npad, Cn, r,
+                                     _ptr(_dense(dq)), _ptr(_dense(dk)), _ptr(_dense(dv)), _stream()), "gd_pam_f32_bwd")
 
 
 # =====================================================================================================

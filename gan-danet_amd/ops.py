@@ -4,8 +4,10 @@ tape; no ATen compute op runs on the product path.
 
 Precision: ``config.precision`` ("bf16" | "fp32") selects the MFMA operand type of every
 GEMM-shaped kernel (fp32 accumulate in both).  "fp32" is the bit-exact parity mode; in "bf16" mode
-PAM runs the fused flash kernels, in "fp32" mode it runs the unfused reference-shaped product chain
-(materialised N x N matrices, small N only).  CAM always runs in fp32 (its logits scale with N).
+PAM runs the fused flash kernels on 16-bit operands.  In "fp32" mode (and under layer_override(pam="exact")) it runs
+the reference-shaped product chain (materialised N x N matrices) while those are small, and the fused flash kernels on
+exact fp32 operands (gd_pam_f32_*, no N x N buffer) once one of them would pass 2^31 elements or when GD_PAM_F32_FLASH=1.
+CAM always runs in fp32 (its logits scale with N).
 """
 from __future__ import annotations
 
@@ -436,16 +438,40 @@ def _pam_wide(Cn: int, r: int) -> bool:
     return K.PAM_WIDE and sixteen_bit("pam") and 192 < Cn <= 511 and r <= 63
 
 
+PAM_F32_ROUTE = "f32"      # ... and for the fused kernels on exact fp32 operands (gd_pam_f32_*)
+
+
+def _pam_f32(B: int, Cn: int, r: int, N: int) -> bool:
+    """exact operand mode, C <= 511 (r <= 63): the fused fp32 kernels instead of the product chain when GD_PAM_F32_FLASH=1,
+    or (unset) when one of the chain's (B, N, N) matrices would pass K.PAM_F32_AUTO_ELEMS elements"""
+    if operand_mode("pam") != "exact" or not (1 <= Cn <= 511 and 1 <= r <= 63):
+        return False
+    if K.PAM_F32_FLASH is None:
+        return B * N * N > K.PAM_F32_AUTO_ELEMS
+    return bool(K.PAM_F32_FLASH)
+
+
+def _pad_plane(t: torch.Tensor, N: int, Np: int) -> torch.Tensor:
+    """(B, R, N) per-image dense block -> itself when N == Np, else a zero-padded (B, R, Np) copy"""
+    if N == Np:
+        return t
+    B, R = t.shape[0], t.shape[1]
+    out = torch.zeros(B, R, Np, device=t.device, dtype=torch.float32)
+    K.copy_rows(t, K._bview(t), N, out, R * Np, Np, B, R, N)
+    return out
+
+
 def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
-    """PAM into ``out3`` (B, C, N) view.  Returns (route: True = flash, PAM_WIDE_ROUTE = wide flash, False = product
-    chain; tensors to keep for backward)."""
+    """PAM into ``out3`` (B, C, N) view.  Returns (route: True = flash, PAM_WIDE_ROUTE = wide flash, PAM_F32_ROUTE = flash
+    on exact fp32 operands, False = product chain; tensors to keep for backward)."""
     B, Cn, H, W = x.shape
     N = H * W
     r = wq.shape[0]
     x3 = x.view(B, Cn, N)
     fused = sixteen_bit("pam") and Cn <= 192 and r <= 31
     wide = not fused and _pam_wide(Cn, r)
-    if (fused or wide) and PAM_CAT and (bq is None) == (bk is None) == (bv is None):
+    f32 = not fused and not wide and _pam_f32(B, Cn, r, N)
+    if (fused or wide or f32) and PAM_CAT and (bq is None) == (bk is None) == (bv is None):
         # q, k, v as ONE 1x1 conv over the concatenated weights: x is read once instead of three times
         wc = torch.empty(2 * r + Cn, Cn, 1, 1, device=x.device, dtype=torch.float32)
         for w_, lo in ((wq, 0), (wk, r), (wv, 2 * r)):
@@ -495,18 +521,65 @@ def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
         lse = torch.empty(B, N, device=x.device, dtype=torch.float32)
         K.pam_wide_fwd(qt, kt, vn, B, N, Np, Cn, Cp, D, gamma_p, x3, out3, o_attn, lse, r_alg=r, f16=f16)
         return PAM_WIDE_ROUTE, (qt, kt, kn, vt, o_attn, lse)
-    prec = prec if sixteen_bit("pam") else L.PREC_FP32     # the reference-shaped product chain below
+    if f32:
+        # the projections' own fp32 planes are the MFMA operands (channel-major = one channel pair per k-step); only a
+        # ragged N costs a zero-padded copy
+        Np = _npad(N)
+        q, k, v = _pad_plane(q, N, Np), _pad_plane(k, N, Np), _pad_plane(v, N, Np)
+        o_attn = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
+        lse = torch.empty(B, N, device=x.device, dtype=torch.float32)
+        K.pam_f32_fwd(q, k, v, B, N, Np, Cn, r, gamma_p, x3, out3, o_attn, lse)
+        return PAM_F32_ROUTE, (q, k, v, o_attn, lse)
+    prec = prec if sixteen_bit("pam") else L.PREC_FP32
+    return False, _pam_chain_fwd(q, k, v, x3, gamma_p, out3, prec)
+
+
+def _pam_chain_fwd(q, k, v, x3, gamma_p, out3, prec):
+    """the reference-shaped product chain on the projections q, k (B, r, N), v (B, C, N): materialises the (B, N, N)
+    logits / attention matrix; returns the tensors its backward needs"""
+    B, r, N = q.shape
+    Cn = v.shape[1]
     qt_, kt_ = K.transpose(q), K.transpose(k)              # (B, N, r)
-    s = torch.empty(B, N, N, device=x.device, dtype=torch.float32)
+    s = torch.empty(B, N, N, device=q.device, dtype=torch.float32)
     K.gemm_nt(B=B, M=N, N=N, kseg=1, klen=r, a=qt_, a_bs=N * r, a_ss=0, lda=r, bm=kt_, b_bs=N * r, b_ss=0,
               ldb=r, c=s, c_bs=N * N, ldc=N, precision=prec, splits=1)
     p = K.softmax_rows(s, 1.0, out=s)
-    o_attn = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
+    o_attn = torch.empty(B, Cn, N, device=q.device, dtype=torch.float32)
     K.gemm_nt(B=B, M=Cn, N=N, kseg=1, klen=N, a=v, a_bs=Cn * N, a_ss=0, lda=N, bm=p, b_bs=N * N, b_ss=0,
               ldb=N, c=o_attn, c_bs=Cn * N, ldc=N, precision=prec, splits=1)
     K.copy_slab(x3, out3)
     _axpy_dev3(o_attn, gamma_p, out3)
-    return False, (qt_, kt_, v, p, o_attn)
+    return qt_, kt_, v, p, o_attn
+
+
+def _pam_chain_bwd(pam_saved, gamma_p, d_pam, pprec):
+    """backward of _pam_chain_fwd: (dq, dk (B, r, N), dv (B, C, N), dgamma) from dOut (B, C, N) view ``d_pam``"""
+    qt_, kt_, v, p, o_attn = pam_saved
+    B, N, r = qt_.shape
+    Cn = v.shape[1]
+    dev = v.device
+    dop = torch.empty(B, Cn, N, device=dev, dtype=torch.float32)
+    K.copy_slab(d_pam, dop)
+    dgamma_p = K.dot(dop, o_attn)
+    K.scale_dev(dop, gamma_p, out=dop)                       # gamma * dOut (in place)
+    dp = torch.empty(B, N, N, device=dev, dtype=torch.float32)
+    # dP[i][j] = sum_c dO'[c][i] V[c][j]
+    K.conv_nn(B=B, M=N, Ck=Cn, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=N, Ho=1, Wo=N, a=dop,
+              a_bs=Cn * N, a_sm=1, a_sc=N, a_st=0, x=v, x_bs=Cn * N, y=dp, y_bs=N * N, precision=pprec)
+    ds = K.softmax_rows_bwd(p, dp, 1.0)
+    del dp
+    # dV[c][j] = sum_i dO'[c][i] P[i][j]
+    dv = torch.empty(B, Cn, N, device=dev, dtype=torch.float32)
+    K.conv_nn(B=B, M=Cn, Ck=N, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=N, Ho=1, Wo=N, a=dop,
+              a_bs=Cn * N, a_sm=N, a_sc=1, a_st=0, x=p, x_bs=N * N, y=dv, y_bs=Cn * N, precision=pprec)
+    # dQt[i][d] = sum_j dS[i][j] Kt[j][d] ; dKt[j][d] = sum_i dS[i][j] Qt[i][d]
+    dqt = torch.empty(B, N, r, device=dev, dtype=torch.float32)
+    dkt = torch.empty(B, N, r, device=dev, dtype=torch.float32)
+    K.conv_nn(B=B, M=N, Ck=N, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=r, Ho=1, Wo=r, a=ds,
+              a_bs=N * N, a_sm=N, a_sc=1, a_st=0, x=kt_, x_bs=N * r, y=dqt, y_bs=N * r, precision=pprec)
+    K.conv_nn(B=B, M=N, Ck=N, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=r, Ho=1, Wo=r, a=ds,
+              a_bs=N * N, a_sm=1, a_sc=N, a_st=0, x=qt_, x_bs=N * r, y=dkt, y_bs=N * r, precision=pprec)
+    return K.transpose(dqt), K.transpose(dkt), dv, dgamma_p               # dq, dk: (B, r, N)
 
 
 def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has_bias):
@@ -515,7 +588,22 @@ def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
     B, Cn, H, W = x.shape
     N = H * W
     r = wq.shape[0]
-    if fused:
+    if fused == PAM_F32_ROUTE:
+        q, k, v, o_attn, lse = pam_saved
+        Np = q.shape[2]
+        d_raw, delta = K.chan_dot(d_pam, o_attn, gamma_p)
+        dgamma_p = K.dot(d_raw, None)
+        if Np == N:
+            gdo = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
+            K.copy_slab(d_pam, gdo)
+        else:
+            gdo = _pad_plane(d_pam, N, Np)
+        K.scale_dev(gdo, gamma_p, out=gdo)                       # gamma * dOut (in place)
+        dq = torch.empty(B, r, N, device=x.device, dtype=torch.float32)
+        dk = torch.empty(B, r, N, device=x.device, dtype=torch.float32)
+        dv = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
+        K.pam_f32_bwd(q, k, v, gdo, lse, delta, B, N, Np, Cn, r, dq, dk, dv)
+    elif fused:
         qt, kt, kn, vt, o_attn, lse = pam_saved
         Np, Cp = _npad(N), _cp(Cn)
         d_raw, delta = K.chan_dot(d_pam, o_attn, gamma_p)
@@ -565,34 +653,14 @@ def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
                 K.scale_dev(t, s_inv, out=t)
         dq, dk, dv = _compact(dqn, r, N), _compact(dkn, r, N), _compact(dvp, Cn, N)
     else:
-        qt_, kt_, v, p, o_attn = pam_saved
         pprec = prec if sixteen_bit("pam") else L.PREC_FP32
-        dop = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
-        K.copy_slab(d_pam, dop)
-        dgamma_p = K.dot(dop, o_attn)
-        K.scale_dev(dop, gamma_p, out=dop)                       # gamma * dOut (in place)
-        dp = torch.empty(B, N, N, device=x.device, dtype=torch.float32)
-        # dP[i][j] = sum_c dO'[c][i] V[c][j]
-        K.conv_nn(B=B, M=N, Ck=Cn, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=N, Ho=1, Wo=N, a=dop,
-                  a_bs=Cn * N, a_sm=1, a_sc=N, a_st=0, x=v, x_bs=Cn * N, y=dp, y_bs=N * N, precision=pprec)
-        ds = K.softmax_rows_bwd(p, dp, 1.0)
-        del dp
-        # dV[c][j] = sum_i dO'[c][i] P[i][j]
-        dv = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
-        K.conv_nn(B=B, M=Cn, Ck=N, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=N, Ho=1, Wo=N, a=dop,
-                  a_bs=Cn * N, a_sm=N, a_sc=1, a_st=0, x=p, x_bs=N * N, y=dv, y_bs=Cn * N, precision=pprec)
-        # dQt[i][d] = sum_j dS[i][j] Kt[j][d] ; dKt[j][d] = sum_i dS[i][j] Qt[i][d]
-        dqt = torch.empty(B, N, r, device=x.device, dtype=torch.float32)
-        dkt = torch.empty(B, N, r, device=x.device, dtype=torch.float32)
-        K.conv_nn(B=B, M=N, Ck=N, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=r, Ho=1, Wo=r, a=ds,
-                  a_bs=N * N, a_sm=N, a_sc=1, a_st=0, x=kt_, x_bs=N * r, y=dqt, y_bs=N * r, precision=pprec)
-        K.conv_nn(B=B, M=N, Ck=N, ks=1, stride=1, pad=0, transposed=False, Hi=1, Wi=r, Ho=1, Wo=r, a=ds,
-                  a_bs=N * N, a_sm=1, a_sc=N, a_st=0, x=qt_, x_bs=N * r, y=dkt, y_bs=N * r, precision=pprec)
-        dq, dk = K.transpose(dqt), K.transpose(dkt)               # (B, r, N)
+        dq, dk, dv, dgamma_p = _pam_chain_bwd(pam_saved, gamma_p, d_pam, pprec)
     grads = []
+    # the exact-fp32 fused route is reproducible end to end: its weight-gradient GEMMs run unsplit (no atomic combine)
+    splits = 1 if fused == PAM_F32_ROUTE else 0
     for dy3, w, hb in ((dq, wq, has_bias[0]), (dk, wk, has_bias[1]), (dv, wv, has_bias[2])):
         dy4 = dy3.view(B, dy3.shape[1], H, W)
-        grads.append(K.conv2d_wgrad(dy4, x, 1, 1, 0, prec))
+        grads.append(K.conv2d_wgrad(dy4, x, 1, 1, 0, prec, splits=splits))
         grads.append(K.channel_sum(dy4) if hb else None)
         K.conv2d_dgrad(dy4, w, (H, W), 1, 0, prec, out=dx.view(B, Cn, H, W), accumulate=True)
     return (*grads, dgamma_p)

@@ -411,6 +411,27 @@ size_t gd_pam_wide_scratch_bytes(int Npad, int D, int deterministic);
 int gd_pam_wide_bwd(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_, const float* lse,
                     const float* delta, int B, int N, int Npad, int Cp, int D, int f16, int deterministic, float* dqn,
                     float* dkn, float* dv, void* scratch, size_t scratch_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * PAM, fused form on EXACT fp32 operands (generator.py:115-122; the parity mode's attention without the N x N matrices).
+ * Every product is a v_mfma_f32_32x32x2_f32; the softmax is online (running maximum, fp32 statistics).  8 <= C <= 511 in
+ * practice (1 <= C <= 511 accepted), 1 <= r <= 63; r is padded to the MFMA k-step (2) inside the kernels only.
+ *   q, k   : (B, r, Npad) fp32 planes, UNSCALED projection outputs, batch strides q_bs / k_bs (elements)
+ *   v      : (B, C, Npad), batch stride v_bs
+ *   Npad   : row length of those planes, a multiple of 256 >= N; columns >= N must be zero.  With N % 256 == 0 the
+ *            projections' own outputs are the operands (no copy).  Planes 16-byte aligned, batch strides % 4 == 0.
+ *   out    : gamma * attn + x, (B, C, N) with batch stride out_bs (may be a channel slice of the 2C DANet slab); x likewise
+ *   o_attn : (B, C, N) dense, the un-scaled attention output; lse (B, N): natural-log sum-exp of the energies
+ * No scratch, no N x N or N x keys buffer.  Returns 0, or -1 with gd_last_error naming the argument. */
+int gd_pam_f32_fwd(const float* q, long q_bs, const float* k, long k_bs, const float* v, long v_bs, int B, int N, int Npad,
+                   int C, int r, const float* gamma, const float* x, long x_bs, float* out, long out_bs, float* o_attn,
+                   float* lse, void* stream);
+/* backward of gd_pam_f32_fwd (autograd of generator.py:115-122): gdo (B, C, Npad) = gamma * dOut (zero columns >= N),
+ * delta[b][i] = sum_c gdo[c][i] o_attn[c][i] (gd_chan_dot); dq, dk (B, r, N) and dv (B, C, N) dense, gradients w.r.t. the
+ * unscaled q, k, v.  A key-parallel dV kernel per chunk of <= 192 channels, a key-parallel dK and a query-parallel dQ
+ * kernel: no atomics, no scratch, bitwise reproducible. */
+int gd_pam_f32_bwd(const float* q, long q_bs, const float* k, long k_bs, const float* v, long v_bs, const float* gdo,
+                   long gdo_bs, const float* lse, const float* delta, int B, int N, int Npad, int C, int r, float* dq,
+                   float* dk, float* dv, void* stream);
 
 /* test.ipynb c1:69-85 mild_histogram_matching, per sample of a batch: out[b] = (1 - weight) * src[b] + weight *
  * interp(cdf_src(src[b]), cdf_ref, sorted unique ref[b]) with numpy's np.unique / np.interp semantics (float64 result, as
