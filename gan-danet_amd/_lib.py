@@ -111,8 +111,6 @@ SIGNATURES = {
     "gd_pam_flash_fwd_shift": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _l, _p, _p, _i, _p, _sz, _p]),
     "gd_pam_flash_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _l, _p, _sz, _p]),
     "gd_pam_bwd_scratch_bytes": (_sz, [_i, _i]),
-    "gd_pam_k64_variant": (None, [_i, _i]),
-    "gd_pam_k64_debug": (None, [_p]),
     "gd_pam_wide_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p, _l, _p, _p, _p]),
     "gd_pam_wide_scratch_bytes": (_sz, [_i, _i, _i]),
     "gd_pam_wide_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),

@@ -877,7 +877,7 @@ extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int 
 extern "C" size_t gd_pam_bwd64_scratch_bytes(int Npad, int deterministic);
 extern "C" int gd_pam_bwd64_slice(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
                                   const float* lse, const float* delta, int nb, int N, int Npad, int Cp, int f16,
-                                  int vreg, int deterministic, float* dqn, float* dkn, float* dv, long out_bs,
+                                  int deterministic, float* dqn, float* dkn, float* dv, long out_bs,
                                   void* scratch, void* stream);
 
 // Backward forms (gandanet.h GD_PAM_BWD_*):
@@ -889,13 +889,6 @@ extern "C" size_t gd_pam_bwd_scratch_bytes(int Npad, int form) {
     if (form == 0 || form == 1) return gd_pam_bwd64_scratch_bytes(Npad, form == 1);
     if (form == 2) return (size_t)(Npad / 256) * (size_t)Npad * 32 * sizeof(unsigned short);
     return 0;
-}
-
-// V fragments of both key tiles of a wave in registers (default; 15.9 ms at B=4, N=65536, C=184) or, GD_PAM_K64_VREG=1,
-// one in registers and one in LDS (16.6 ms)
-static int pam_k64_vreg() {
-    static const int v = getenv("GD_PAM_K64_VREG") ? atoi(getenv("GD_PAM_K64_VREG")) : 2;
-    return v == 1 ? 1 : 2;
 }
 
 extern "C" int gd_pam_flash_bwd(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
@@ -922,8 +915,8 @@ extern "C" int gd_pam_flash_bwd(const void* qt, const void* kt, const void* kn, 
             if (form <= 1) {
                 const long oq = out_bs ? (long)b0 * out_bs : o32, ov = out_bs ? (long)b0 * out_bs : oc;
                 const int rcode = gd_pam_bwd64_slice(q + o32, k + o32, kT + o32, v + oc, dO + oc, lse + on, delta + on, nb, N,
-                                                     Npad, Cp, f16, pam_k64_vreg(), form == 1, dqn + oq, dkn + oq, dv + ov,
-                                                     out_bs, scratch, stream);
+                                                     Npad, Cp, f16, form == 1, dqn + oq, dkn + oq, dv + ov, out_bs,
+                                                     scratch, stream);
                 if (rcode) return rcode;
             } else {
                 PAM_DISPATCH_CT(Cp / 32, hipLaunchKernelGGL((pam_bwd_dkv3_kernel<CT, true, 8>), dim3(Npad / 256, nb), dim3(512), 0, s,

@@ -421,7 +421,6 @@ class DenseBlockFn(Function):
 # =====================================================================================================
 # dual attention: PAM || CAM into one 2C slab      generator.py:104-157
 # =====================================================================================================
-# the pre-v3 dK/dV kernels (GD_PAM_DKV_V3=0, kept for A/B runs) also need q and gamma*dOut channel-major
 def _npad(n: int) -> int:
     return (n + 255) // 256 * 256
 

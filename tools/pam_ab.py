@@ -1,5 +1,5 @@
-"""Interleaved A/B timing of the K64 backward schedule variants in ONE process (guide rule 24).
-    python tools/pam_ab.py --variants 0:1,0:2,1:2,3:2 --rounds 5        (order:vreg pairs)"""
+"""Interleaved A/B timing of the PAM backward forms (gandanet.h GD_PAM_BWD_*) in ONE process (guide rule 24).
+    python tools/pam_ab.py --forms 0,1,2,3 --rounds 5"""
 import argparse
 import os
 import statistics
@@ -16,8 +16,7 @@ ap.add_argument("--tile", type=int, default=256)
 ap.add_argument("--channels", type=int, default=184)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=3)
-ap.add_argument("--variants", default="0:1,0:2")
-ap.add_argument("--form", type=int, default=0)
+ap.add_argument("--forms", default="0,1")
 a = ap.parse_args()
 dev = torch.device("cuda")
 B, C, N = a.batch, a.channels, a.tile * a.tile
@@ -42,29 +41,27 @@ dkn = torch.empty(B, 32, Np, device=dev)
 dv = torch.empty(B, Cp, Np, device=dev)
 K.pam_flash_fwd(qt, kt, vn, B, N, Np, C, Cp, gamma, x, out, o, lse, r_alg=r, v_ones=ones >= 0)
 _, delta = K.chan_dot(do, o, gamma)
-variants = [tuple(int(t) for t in s.split(":")) for s in a.variants.split(",")]
-times = {vv: [] for vv in variants}
+forms = [int(f) for f in a.forms.split(",")]
+times = {f: [] for f in forms}
 ref = None
 for rnd in range(a.rounds + 1):
-    for vv in variants:
-        K.lib().gd_pam_k64_variant(vv[0], vv[1])
+    for form in forms:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.iters):
-            K.pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, dqn, dkn, dv, r_alg=r, c_alg=C, form=a.form)
+            K.pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, dqn, dkn, dv, r_alg=r, c_alg=C, form=form)
         e1.record()
         torch.cuda.synchronize()
-        if rnd == 0:     # warm-up round doubles as a cross-variant numerics check
+        if rnd == 0:     # warm-up round doubles as a cross-form numerics check
             cur = torch.cat([dqn[:, :r, :N].flatten(), dkn[:, :r, :N].flatten(), dv[:, :C, :N].flatten()])
             if ref is None:
                 ref = cur.clone()
             else:
-                print(f"variant {vv}: rel diff vs first {((cur - ref).norm() / ref.norm()).item():.2e}", flush=True)
+                print(f"form {form}: rel diff vs first {((cur - ref).norm() / ref.norm()).item():.2e}", flush=True)
         else:
-            times[vv].append(e0.elapsed_time(e1) / a.iters)
-K.lib().gd_pam_k64_variant(0, 0)
+            times[form].append(e0.elapsed_time(e1) / a.iters)
 fl = 4.0 * N * N * (r + C) * B
-for vv in variants:
-    t = times[vv]
-    print(f"order {vv[0]} vreg {vv[1]}: median {statistics.median(t):7.3f} ms  min {min(t):7.3f}  "
+for form in forms:
+    t = times[form]
+    print(f"form {form}: median {statistics.median(t):7.3f} ms  min {min(t):7.3f}  "
           f"{fl / statistics.median(t) / 1e9:7.1f} TF", flush=True)
