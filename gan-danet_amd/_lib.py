@@ -55,15 +55,21 @@ SIGNATURES = {
     "gd_version": (_i, []),
     "gd_set_deterministic": (None, [_i]),
     "gd_get_deterministic": (_i, []),
+    "gd_set_det_reduce": (_i, [_i]),
+    "gd_get_det_reduce": (_i, []),
     "gd_last_error": (_i, [C.c_char_p, _i]),
     "gd_sizeof_conv_desc": (_i, []),
     "gd_sizeof_gemm_nt_desc": (_i, []),
     "gd_conv2d": (_i, [C.POINTER(ConvDesc), _p]),
     "gd_gemm_nt": (_i, [C.POINTER(GemmNTDesc), _p]),
+    "gd_gemm_nt_ws": (_i, [C.POINTER(GemmNTDesc), _p, _p, _sz]),
+    "gd_gemm_nt_plan": (_i, [C.POINTER(GemmNTDesc), _sz, C.POINTER(_i), C.POINTER(_sz)]),
     "gd_conv3x3_ws_bytes": (_sz, [_i, _i]),
     "gd_conv3x3_eligible": (_i, [C.POINTER(ConvDesc)]),
     "gd_conv3x3": (_i, [C.POINTER(ConvDesc), _p, _sz, _p]),
     "gd_conv3x3_wgrad": (_i, [_p, _l, _p, _p, _l, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "gd_conv3x3_wgrad_ws": (_i, [_p, _l, _p, _p, _l, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _sz]),
+    "gd_conv3x3_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_sz)]),
     "gd_pack_16_split": (_i, [_p, _l, _i, _i, _i, _p, _p, _i, _p, _l, _i, _l, _i, _i, _p, _l, _i, _l, _i, _i, _p]),
     "gd_pack_16_split_masked": (_i, [_p, _l, _i, _i, _i, _p, _p, _i, _p, _l, _i, _l, _i, _i, _p, _l, _i, _l, _i, _i, _p, _l, _p]),
     "gd_split3_weights": (_i, [_p, _l, _l, _l, _p, _p]),
@@ -123,12 +129,14 @@ SIGNATURES = {
     "gd_conv3x3_nhwc_f32out": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
     "gd_disc_stem_fwd": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _f, _p, _i, _p]),
     "gd_disc_stem_wgrad": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p]),
+    "gd_disc_stem_wgrad_ws": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _sz]),
     "gd_disc_stem_dgrad": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
     "gd_conv3x3_nhwc_s2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "gd_conv3x3_nhwc_s2_dgrad": (_i, [_p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
     "gd_nhwc_flatten_fwd": (_i, [_p, _i, _i, _i, _p, _i, _p]),
     "gd_nhwc_flatten_bwd": (_i, [_p, _p, _f, _i, _i, _i, _p, _i, _p]),
     "gd_nhwc_to_nchw16": (_i, [_p, _i, _i, _i, _p, _p, _i, _p]),
+    "gd_nhwc_to_nchw16_ws": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p, _sz]),
     "gd_nhwc_stem_fwd": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _i, _p]),
     "gd_nhwc_stem_bwd": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
     "gd_nhwc_maxpool2_fwd": (_i, [_p, _i, _i, _i, _i, _p, _i, _p]),

@@ -7,7 +7,9 @@
 * ``save_training_state`` / ``load_training_state``: what the reference does NOT keep -- discriminator, both AdamW
   states, the LR schedulers and the epoch counter -- so that a run resumes to fp32 round-off (bit-for-bit under
   ``gd.set_deterministic(True)``: the default split-K / weight-gradient / PAM dQ sums use fp32 atomics, whose order
-  varies from launch to launch).
+  varies from launch to launch; ``gd.set_deterministic(True, reduce="ordered")`` gives the same guarantee with the split
+  reductions still parallel -- partial slabs summed in a fixed order -- as long as both runs use the same reduce setting
+  and workspace size, which fix the split counts).
 * under data parallelism only rank 0 writes files (replicas are identical); every rank reads.
 * ensemble (deep_ensemble.ipynb c0:270-337): members are independent replicas with seeds 42 + i; on an N-GPU node
   member i trains on rank i % N with NO gradient exchange (``GanTrainer(reduce_gradients=False)``), and the

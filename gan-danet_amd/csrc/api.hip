@@ -36,3 +36,16 @@ int g_deterministic = 0;
 }
 extern "C" void gd_set_deterministic(int on) { g_deterministic = on ? 1 : 0; }
 extern "C" int gd_get_deterministic(void) { return g_deterministic; }
+
+// How deterministic mode reduces over splits: 0 = unsplit (one adder per output element), 1 = ordered (every split writes
+// its partial into a slab of the caller's workspace, det_reduce.hip adds the slabs in ascending order).  Only read while
+// deterministic mode is on; the _ws entry points take the workspace.  Process-global.
+namespace {
+int g_det_reduce = 0;
+}
+extern "C" int gd_set_det_reduce(int mode) {
+    GD_CHECK_ARG(mode == 0 || mode == 1, "gd_set_det_reduce: mode must be 0 (unsplit) or 1 (ordered)");
+    g_det_reduce = mode;
+    return 0;
+}
+extern "C" int gd_get_det_reduce(void) { return g_det_reduce; }

@@ -81,6 +81,14 @@ __device__ __forceinline__ float gd_block_max(float v, float* red) {
 // ---- error plumbing for the C ABI -------------------------------------------------------------
 extern "C" void gd_set_error(const char* msg);
 extern "C" int gd_get_deterministic(void);   // api.hip: 1 = no order-dependent (atomic) reductions
+extern "C" int gd_get_det_reduce(void);      // api.hip: 1 = "ordered" (split partial slabs + ordered sum) while deterministic
+// det_reduce.hip: out[b * c_bs + m * ldc + n] (+)= sum over the `splits` dense [B][M][N] slabs of `part`, ascending, + bias[n]
+int gd_det_reduce_launch(const float* part, int splits, float* out, int B, int M, int N, long c_bs, long ldc,
+                         const float* bias, int accumulate, hipStream_t s);
+// slabs [split][Ci][Co][10] -> dw (Co, Ci, 3, 3), db (Co) or NULL
+int gd_det_reduce_stem_launch(const float* part, int splits, int Ci, int Co, float* dw, float* db, hipStream_t s);
+// true when a split reduction may use the ordered form with this workspace
+static inline bool gd_det_ordered(const void* ws) { return ws && gd_get_deterministic() && gd_get_det_reduce() == 1; }
 #define GD_CHECK_ARG(cond, msg)          \
     do {                                 \
         if (!(cond)) {                   \

@@ -860,9 +860,11 @@ struct WgradArgs {
     const unsigned short* x16; int x16_ld;   // optional pixel-major bf16 copy of x, dense (B, H, W, x16_ld): read instead of x
     const float* in_scale; const float* in_shift; int in_relu;
     float* dw;
+    float* part;                     // ordered deterministic mode: [split][Cout][Cin][9] partial slabs, written instead of dw
     int B, M, Ck, H, W, Ho, Wo;
     int tiles_x, tiles_y, tiles_per_split;
 };
+typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4)));    // 16-byte store of dword-aligned floats
 
 __device__ __forceinline__ s16x4_t lds_tr_read(const unsigned short* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p);
@@ -875,7 +877,9 @@ __device__ __forceinline__ s16x4_t lds_tr_read(const unsigned short* p) {
 #ifndef GD_WGRAD_PIPED_MINW
 #define GD_WGRAD_PIPED_MINW 1
 #endif
-template <int NW, int S, bool CS, bool PIPED = false>
+// ORD = true (ordered deterministic mode): the epilogue stores the partial sums into slab blockIdx.z of a.part instead of
+//   adding them into a.dw; a compile-time switch, so the default instantiations keep their code and registers.
+template <int NW, int S, bool CS, bool PIPED = false, bool ORD = false>
 __global__ __launch_bounds__(NW * 64, PIPED ? GD_WGRAD_PIPED_MINW : 2) void conv3x3_wgrad_kernel(const WgradArgs a) {
     constexpr int BM = CS ? 32 : 32 * NW, NT = 64 * NW, NCH = CS ? NW : 1;
     constexpr int PHk = S * (WTH - 1) + 3, PWk = S * (TW - 1) + 3, NPIXk = PHk * PWk;   // input patch of the tile
@@ -1099,9 +1103,27 @@ __global__ __launch_bounds__(NW * 64, PIPED ? GD_WGRAD_PIPED_MINW : 2) void conv
         __syncthreads();
     }
 
-    // ---- combine: dW[co][ci][tap] += acc ----
+    // ---- combine: dW[co][ci][tap] += acc, or (ordered deterministic mode) slab[split][co][ci][tap] = acc ----
     const int ci = c0 + (CS ? wave * CK : 0) + r;
-    if (ci < a.Ck) {
+    if constexpr (ORD) {
+        // the nine taps of a (co, ci) pair are 36 contiguous bytes: two 16-byte stores and one dword; the 32 lanes of a
+        // register row e cover 1152 contiguous bytes of the slab between them
+        if (ci < a.Ck) {
+            float* pw = a.part + (long)blockIdx.z * a.M * a.Ck * 9;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int co = m0 + (CS ? 0 : wave * 32) + acc_row(e, h);
+                if (co < a.M) {
+                    float* q = pw + ((long)co * a.Ck + ci) * 9;
+                    const f32x4u_t v0 = {acc[0][e], acc[1][e], acc[2][e], acc[3][e]};
+                    const f32x4u_t v1 = {acc[4][e], acc[5][e], acc[6][e], acc[7][e]};
+                    *reinterpret_cast<f32x4u_t*>(q) = v0;
+                    *reinterpret_cast<f32x4u_t*>(q + 4) = v1;
+                    q[8] = acc[8][e];
+                }
+            }
+        }
+    } else if (ci < a.Ck) {
 #pragma unroll
         for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -1117,30 +1139,22 @@ __global__ __launch_bounds__(NW * 64, PIPED ? GD_WGRAD_PIPED_MINW : 2) void conv
 static const bool g_wgrad_cs_piped = getenv("GD_WGRAD_CS_PIPED") ? atoi(getenv("GD_WGRAD_CS_PIPED")) != 0 : true;   // A/B switch
 static const bool g_wgrad_s2_piped = getenv("GD_WGRAD_S2_PIPED") ? atoi(getenv("GD_WGRAD_S2_PIPED")) != 0 : true;   // A/B switch
 
-// dw (Cout, Cin, 3, 3) fp32 is overwritten (accumulate = 0) or added to.  Same input-transform contract as gd_conv2d.
-extern "C" int gd_conv3x3_wgrad(const float* dy, long dy_bs, const void* dy_bf16, const float* x, long x_bs,
-                                const void* x_nhwc16, int x_ld, const float* in_scale, const float* in_shift, int in_relu,
-                                int B, int Cout, int Cin, int H, int W, int stride, int accumulate, float* dw, void* stream) {
-    GD_CHECK_ARG((dy || dy_bf16) && (x || x_nhwc16) && dw, "gd_conv3x3_wgrad: null pointer");
-    GD_CHECK_ARG(!x_nhwc16 || (!in_scale && x_ld >= Cin && x_ld % 8 == 0),
-                 "gd_conv3x3_wgrad: the pixel-major bf16 x needs x_ld >= Cin, x_ld % 8 == 0 and no input transform");
+// Launch shape of the weight gradient: a pure function of the sizes, the deterministic mode and the workspace size, shared
+// by gd_conv3x3_wgrad_plan and the launcher so that the two cannot drift.
+namespace {
+struct WgradPlan {
+    int best_nw, cs, groups, cs_nw, mblocks, tiles_x, tiles_y, Ho, Wo, tiles_per_split, splits, ordered;
+    long ntiles;
+    size_t ws_needed;
+};
+int wgrad_plan(int B, int Cout, int Cin, int H, int W, int stride, size_t ws_bytes, WgradPlan* p) {
     GD_CHECK_ARG(B > 0 && Cout > 0 && Cin > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "gd_conv3x3_wgrad: bad sizes");
-    GD_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "gd_conv3x3_wgrad: in_scale/in_shift must come together");
-    hipStream_t s = (hipStream_t)stream;
-    // the pixel splits add into dw with fp32 atomics: it starts from zero, or (accumulate) from what it holds
-    if (!accumulate)
-        GD_CHECK_ARG(hipMemsetAsync(dw, 0, (size_t)Cout * Cin * 9 * sizeof(float), s) == hipSuccess, "gd_conv3x3_wgrad: memset failed");
-    WgradArgs a;
-    a.dy16 = (const unsigned short*)dy_bf16;
-    a.dy = dy; a.dy_bs = dy_bs; a.x = x; a.x_bs = x_bs;
-    a.x16 = (const unsigned short*)x_nhwc16; a.x16_ld = x_ld;
-    a.in_scale = in_scale; a.in_shift = in_shift; a.in_relu = in_relu;
-    a.dw = dw; a.B = B; a.M = Cout; a.Ck = Cin; a.H = H; a.W = W;
-    a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;     // 3x3, pad 1
-    a.tiles_x = (a.Wo + TW - 1) / TW;
-    a.tiles_y = (a.Ho + WTH - 1) / WTH;
-    const long ntiles = (long)B * a.tiles_x * a.tiles_y;
+    p->Ho = (H - 1) / stride + 1; p->Wo = (W - 1) / stride + 1;     // 3x3, pad 1
+    p->tiles_x = (p->Wo + TW - 1) / TW;
+    p->tiles_y = (p->Ho + WTH - 1) / WTH;
+    const long ntiles = (long)B * p->tiles_x * p->tiles_y;
     GD_CHECK_ARG(ntiles < (1L << 31), "gd_conv3x3_wgrad: too many tiles");
+    p->ntiles = ntiles;
     // m-tiles per workgroup: 2, 4 or 6 waves, whichever pads Cout least (ties -> the larger block).  A 1-wave
     // variant for Cout <= 32 was measured 2x SLOWER (64 threads stage the whole patch) and is not offered.
     int best_nw = 2;
@@ -1157,37 +1171,104 @@ extern "C" int gd_conv3x3_wgrad(const float* dy, long dy_bs, const void* dy_bf16
     const int cs_nw = cs ? (chunks + groups - 1) / groups : 0;
     const int bm = cs ? 32 : 32 * best_nw;
     const int mblocks = (Cout + bm - 1) / bm;
+    p->best_nw = best_nw; p->cs = cs; p->groups = groups; p->cs_nw = cs_nw; p->mblocks = mblocks;
+    const bool det = gd_get_deterministic() != 0, ordered_mode = det && gd_get_det_reduce() == 1;
     long splits = 1024 / ((long)mblocks * groups);
-    if (splits < 1 || gd_get_deterministic()) splits = 1;    // deterministic mode: one adder per dW element
+    if (splits < 1 || (det && !ordered_mode)) splits = 1;    // deterministic, unsplit: one adder per dW element
     if (splits > ntiles) splits = ntiles;
     if (splits > 65535) splits = 65535;
-    a.tiles_per_split = (int)((ntiles + splits - 1) / splits);
-    splits = (ntiles + a.tiles_per_split - 1) / a.tiles_per_split;
+    const size_t out_bytes = (size_t)Cout * Cin * 9 * sizeof(float);
+    if (ordered_mode) {                                      // ordered: one slab per split must fit the workspace
+        const size_t fit = ws_bytes / out_bytes;
+        if ((size_t)splits > fit) splits = (long)fit;
+        if (splits < 2) splits = 1;
+    }
+    p->tiles_per_split = (int)((ntiles + splits - 1) / splits);
+    splits = (ntiles + p->tiles_per_split - 1) / p->tiles_per_split;
+    p->splits = (int)splits;
+    p->ordered = ordered_mode && splits > 1;
+    p->ws_needed = p->ordered ? (size_t)splits * out_bytes : 0;
+    return 0;
+}
+}  // namespace
+
+extern "C" int gd_conv3x3_wgrad_plan(int B, int Cout, int Cin, int H, int W, int stride, size_t ws_bytes, int* splits,
+                                     size_t* ws_needed) {
+    WgradPlan p;
+    if (wgrad_plan(B, Cout, Cin, H, W, stride, ws_bytes, &p)) return -1;
+    if (splits) *splits = p.splits;
+    if (ws_needed) *ws_needed = p.ws_needed;
+    return 0;
+}
+
+// dw (Cout, Cin, 3, 3) fp32 is overwritten (accumulate = 0) or added to.  Same input-transform contract as gd_conv2d.
+// ws / ws_bytes: caller-owned scratch for the ordered deterministic mode (NULL: never used).
+extern "C" int gd_conv3x3_wgrad_ws(const float* dy, long dy_bs, const void* dy_bf16, const float* x, long x_bs,
+                                   const void* x_nhwc16, int x_ld, const float* in_scale, const float* in_shift, int in_relu,
+                                   int B, int Cout, int Cin, int H, int W, int stride, int accumulate, float* dw, void* stream,
+                                   void* ws, size_t ws_bytes) {
+    GD_CHECK_ARG((dy || dy_bf16) && (x || x_nhwc16) && dw, "gd_conv3x3_wgrad: null pointer");
+    GD_CHECK_ARG(!x_nhwc16 || (!in_scale && x_ld >= Cin && x_ld % 8 == 0),
+                 "gd_conv3x3_wgrad: the pixel-major bf16 x needs x_ld >= Cin, x_ld % 8 == 0 and no input transform");
+    GD_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "gd_conv3x3_wgrad: in_scale/in_shift must come together");
+    GD_CHECK_ARG(((uintptr_t)ws % 16) == 0, "gd_conv3x3_wgrad: the workspace must be 16-byte aligned");
+    WgradPlan p;
+    if (wgrad_plan(B, Cout, Cin, H, W, stride, ws ? ws_bytes : 0, &p)) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    // atomic path: the pixel splits add into dw with fp32 atomics: it starts from zero, or (accumulate) from what it
+    // holds.  The ordered path overwrites its slabs and the reduce kernel writes dw.
+    if (!accumulate && !p.ordered)
+        GD_CHECK_ARG(hipMemsetAsync(dw, 0, (size_t)Cout * Cin * 9 * sizeof(float), s) == hipSuccess, "gd_conv3x3_wgrad: memset failed");
+    WgradArgs a;
+    a.dy16 = (const unsigned short*)dy_bf16;
+    a.dy = dy; a.dy_bs = dy_bs; a.x = x; a.x_bs = x_bs;
+    a.x16 = (const unsigned short*)x_nhwc16; a.x16_ld = x_ld;
+    a.in_scale = in_scale; a.in_shift = in_shift; a.in_relu = in_relu;
+    a.dw = dw; a.part = p.ordered ? (float*)ws : nullptr;
+    a.B = B; a.M = Cout; a.Ck = Cin; a.H = H; a.W = W;
+    a.Ho = p.Ho; a.Wo = p.Wo; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
+    a.tiles_per_split = p.tiles_per_split;
+    const int best_nw = p.best_nw, cs_nw = p.cs_nw, groups = p.groups, mblocks = p.mblocks, splits = p.splits;
+    const bool cs = p.cs != 0;
     dim3 grid(groups, mblocks, (unsigned)splits);
+#define WG_LAUNCH(NW_, S_, CS_, PIPED_, THREADS_)                                                                             \
+    do {                                                                                                                      \
+        if (p.ordered) hipLaunchKernelGGL((conv3x3_wgrad_kernel<NW_, S_, CS_, PIPED_, true>), grid, dim3(THREADS_), 0, s, a); \
+        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<NW_, S_, CS_, PIPED_, false>), grid, dim3(THREADS_), 0, s, a);          \
+    } while (0)
     if (cs && a.dy16 && a.x16 && g_wgrad_cs_piped) {
         // both operands 16-bit (the dense layers' packs): the same software pipeline as the wide convs below
-        if (cs_nw == 3) hipLaunchKernelGGL((conv3x3_wgrad_kernel<3, 1, true, true>), grid, dim3(192), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<4, 1, true, true>), grid, dim3(256), 0, s, a);
+        if (cs_nw == 3) WG_LAUNCH(3, 1, true, true, 192);
+        else WG_LAUNCH(4, 1, true, true, 256);
     } else if (cs) {
-        if (cs_nw == 3) hipLaunchKernelGGL((conv3x3_wgrad_kernel<3, 1, true>), grid, dim3(192), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<4, 1, true>), grid, dim3(256), 0, s, a);
+        if (cs_nw == 3) WG_LAUNCH(3, 1, true, false, 192);
+        else WG_LAUNCH(4, 1, true, false, 256);
     } else if (stride == 1 && a.dy16 && a.x16 && best_nw >= 4) {
         // both operands 16-bit: software-pipelined staging (368->184: 8.4 -> 6.4 ms; the 2-wave block spills under it
         // and stays on the plain loop: 1.85 vs 2.20 ms at 184->64)
-        if (best_nw == 4) hipLaunchKernelGGL((conv3x3_wgrad_kernel<4, 1, false, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<6, 1, false, true>), grid, dim3(384), 0, s, a);
+        if (best_nw == 4) WG_LAUNCH(4, 1, false, true, 256);
+        else WG_LAUNCH(6, 1, false, true, 384);
     } else if (stride == 1) {
-        if (best_nw == 2) hipLaunchKernelGGL((conv3x3_wgrad_kernel<2, 1, false>), grid, dim3(128), 0, s, a);
-        else if (best_nw == 4) hipLaunchKernelGGL((conv3x3_wgrad_kernel<4, 1, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<6, 1, false>), grid, dim3(384), 0, s, a);
+        if (best_nw == 2) WG_LAUNCH(2, 1, false, false, 128);
+        else if (best_nw == 4) WG_LAUNCH(4, 1, false, false, 256);
+        else WG_LAUNCH(6, 1, false, false, 384);
     } else if (a.dy16 && a.x16 && best_nw == 4 && g_wgrad_s2_piped) {
         // stride 2, both operands 16-bit (Discriminator1's trunk): the same software pipeline
-        hipLaunchKernelGGL((conv3x3_wgrad_kernel<4, 2, false, true>), grid, dim3(256), 0, s, a);
+        WG_LAUNCH(4, 2, false, true, 256);
     } else {
-        if (best_nw == 2) hipLaunchKernelGGL((conv3x3_wgrad_kernel<2, 2, false>), grid, dim3(128), 0, s, a);
-        else if (best_nw == 4) hipLaunchKernelGGL((conv3x3_wgrad_kernel<4, 2, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<6, 2, false>), grid, dim3(384), 0, s, a);
+        if (best_nw == 2) WG_LAUNCH(2, 2, false, false, 128);
+        else if (best_nw == 4) WG_LAUNCH(4, 2, false, false, 256);
+        else WG_LAUNCH(6, 2, false, false, 384);
     }
+#undef WG_LAUNCH
     GD_LAUNCH_CHECK();
+    if (p.ordered) return gd_det_reduce_launch(a.part, splits, dw, 1, 1, Cout * Cin * 9, 0, (long)Cout * Cin * 9, nullptr, accumulate, s);
     return 0;
+}
+
+extern "C" int gd_conv3x3_wgrad(const float* dy, long dy_bs, const void* dy_bf16, const float* x, long x_bs,
+                                const void* x_nhwc16, int x_ld, const float* in_scale, const float* in_shift, int in_relu,
+                                int B, int Cout, int Cin, int H, int W, int stride, int accumulate, float* dw, void* stream) {
+    return gd_conv3x3_wgrad_ws(dy, dy_bs, dy_bf16, x, x_bs, x_nhwc16, x_ld, in_scale, in_shift, in_relu, B, Cout, Cin, H, W, stride,
+                               accumulate, dw, stream, nullptr, 0);
 }

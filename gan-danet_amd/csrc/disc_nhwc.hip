@@ -127,10 +127,12 @@ __global__ __launch_bounds__(256) void disc_stem_fwd_kernel(const float* __restr
 // ---- stem weight / bias gradient: dw[co][ci][tap] = sum_p g[p][co] x[ci][2p + tap - 1], db[co] = sum_p g[p][co] -------
 // thread = (output pixel, channel octet), grid-strided; blockIdx.y = ci.  Ten accumulators per channel (nine taps + the
 // plain sum), reduced over the lanes of equal octet by xor shuffles, over the waves through LDS, then one atomic per
-// value and workgroup.  Requires Co == 64 (octet = tid & 7).
+// value and workgroup -- or (part != NULL, ordered deterministic mode) one plain store into the workgroup's
+// [blockIdx.x][ci][co][10] slab, summed by det_reduce.hip.  Requires Co == 64 (octet = tid & 7).
 __global__ __launch_bounds__(256) void disc_stem_wgrad_kernel(const unsigned short* __restrict__ g, const float* __restrict__ img,
                                                              int Ci, int H, int W, int Ho, int Wo, float* __restrict__ dw,
-                                                             float* __restrict__ db, long npix_total, int split) {
+                                                             float* __restrict__ db, long npix_total, int split,
+                                                             float* __restrict__ part) {
     constexpr int Co = 64, OCT = 8;
     const int RS = split ? 3 * Co : Co;
     __shared__ float red[4][OCT][80];
@@ -177,7 +179,8 @@ __global__ __launch_bounds__(256) void disc_stem_wgrad_kernel(const unsigned sho
         const int o = i / 80, kt = i - o * 80, k = kt / 10, t = kt - k * 10;
         const float v = red[0][o][kt] + red[1][o][kt] + red[2][o][kt] + red[3][o][kt];
         const int co = o * 8 + k;
-        if (t < 9) atomicAdd(dw + ((long)co * Ci + ci) * 9 + t, v);
+        if (part) part[((long)blockIdx.x * Ci + ci) * (Co * 10) + i] = v;       // i == co * 10 + t
+        else if (t < 9) atomicAdd(dw + ((long)co * Ci + ci) * 9 + t, v);
         else if (ci == 0 && db) atomicAdd(db + co, v);
     }
 }
@@ -293,12 +296,14 @@ __global__ __launch_bounds__(256) void flatten_bwd_kernel(const float* __restric
 // ---- g (B, HW, C) bf16 -> gt (B, C, HW) bf16 + channel sums --------------------------------------------------------------
 // blockIdx.x = 64-channel group, blockIdx.y strides over the (image, 64-pixel tile) list; a 64 x 64 tile goes through LDS
 // ([channel][pixel], rows padded to 72), the channel sums stay in registers until the end (one atomic per channel and
-// workgroup: per-tile atomics would pile millions of adds onto C addresses)
+// workgroup: per-tile atomics would pile millions of adds onto C addresses; with part != NULL -- ordered deterministic
+// mode -- one plain store into the [blockIdx.y][C] slab instead)
 constexpr int TT = 64, TLD = TT + 8;
 // ldg = elements per pixel of g (C, or 3 C for a split gradient whose hi / lo parts are transposed by one launch each: g then
 // points at the part's first channel and the channel sums of the two launches add up to the sums of hi + lo)
 __global__ __launch_bounds__(256) void nhwc_to_nchw16_kernel(const unsigned short* __restrict__ g, int B, int HW, int C, int ldg,
-                                                            unsigned short* __restrict__ gt, float* __restrict__ csum) {
+                                                            unsigned short* __restrict__ gt, float* __restrict__ csum,
+                                                            float* __restrict__ part_sum) {
     __shared__ __attribute__((aligned(16))) unsigned short tile[TT * TLD];
     __shared__ float part[4][TT];
     const int c0 = blockIdx.x * TT;
@@ -351,7 +356,11 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw16_kernel(const unsigned shor
     if (csum) {
         part[tid >> 6][tid & 63] = sum;
         __syncthreads();
-        if (tid < TT && c0 + tid < C) atomicAdd(csum + c0 + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+        if (tid < TT && c0 + tid < C) {
+            const float v = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+            if (part_sum) part_sum[(long)blockIdx.y * C + c0 + tid] = v;
+            else atomicAdd(csum + c0 + tid, v);
+        }
     }
 }
 
@@ -378,18 +387,35 @@ extern "C" int gd_disc_stem_fwd(const float* img, int B, int Ci, int H, int W, c
     return 0;
 }
 
-extern "C" int gd_disc_stem_wgrad(const void* g, const float* img, int B, int Ci, int H, int W, int Co, float* dw, float* db,
-                                  int split, void* stream) {
+extern "C" int gd_disc_stem_wgrad_ws(const void* g, const float* img, int B, int Ci, int H, int W, int Co, float* dw, float* db,
+                                     int split, void* stream, void* ws, size_t ws_bytes) {
     GD_CHECK_ARG(g && img && dw && B > 0 && Ci > 0 && Ci <= 4 && H > 0 && W > 0 && Co == 64,
                  "gd_disc_stem_wgrad: needs Ci <= 4, Co == 64");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long npix = (long)B * Ho * Wo;
-    GD_CHECK_ARG(hipMemsetAsync(dw, 0, (size_t)Co * Ci * 9 * sizeof(float), NS(stream)) == hipSuccess, "gd_disc_stem_wgrad: memset failed");
-    if (db) GD_CHECK_ARG(hipMemsetAsync(db, 0, (size_t)Co * sizeof(float), NS(stream)) == hipSuccess, "gd_disc_stem_wgrad: memset failed");
-    hipLaunchKernelGGL(disc_stem_wgrad_kernel, dim3(grid_n(npix * 8, 1024), Ci), dim3(256), 0, NS(stream), (const unsigned short*)g,
-                       img, Ci, H, W, Ho, Wo, dw, db, npix, split);
+    GD_CHECK_ARG(((uintptr_t)ws % 16) == 0, "gd_disc_stem_wgrad: the workspace must be 16-byte aligned");
+    int nblk = grid_n(npix * 8, 1024);
+    float* part = nullptr;
+    if (gd_det_ordered(ws)) {       // ordered deterministic mode: one slab per workgroup, as many workgroups as fit
+        const size_t fit = ws_bytes / ((size_t)Ci * Co * 10 * sizeof(float));
+        if ((size_t)nblk > fit) nblk = (int)fit;
+        if (nblk < 2) nblk = 1;     // one workgroup per ci: one adder per value, the atomic path is already ordered
+        else part = (float*)ws;
+    }
+    if (!part) {                    // the atomics add onto zeros; the ordered path overwrites
+        GD_CHECK_ARG(hipMemsetAsync(dw, 0, (size_t)Co * Ci * 9 * sizeof(float), NS(stream)) == hipSuccess, "gd_disc_stem_wgrad: memset failed");
+        if (db) GD_CHECK_ARG(hipMemsetAsync(db, 0, (size_t)Co * sizeof(float), NS(stream)) == hipSuccess, "gd_disc_stem_wgrad: memset failed");
+    }
+    hipLaunchKernelGGL(disc_stem_wgrad_kernel, dim3(nblk, Ci), dim3(256), 0, NS(stream), (const unsigned short*)g,
+                       img, Ci, H, W, Ho, Wo, dw, db, npix, split, part);
     GD_LAUNCH_CHECK();
+    if (part) return gd_det_reduce_stem_launch(part, nblk, Ci, Co, dw, db, NS(stream));
     return 0;
+}
+
+extern "C" int gd_disc_stem_wgrad(const void* g, const float* img, int B, int Ci, int H, int W, int Co, float* dw, float* db,
+                                  int split, void* stream) {
+    return gd_disc_stem_wgrad_ws(g, img, B, Ci, H, W, Co, dw, db, split, stream, nullptr, 0);
 }
 
 extern "C" int gd_disc_stem_dgrad(const void* g, int B, int Ci, int H, int W, const float* w, int Co, float* dimg, int split,
@@ -427,19 +453,37 @@ extern "C" int gd_nhwc_flatten_bwd(const float* df, const void* y, float slope, 
 
 // split = 1: g holds 3 C channels per pixel [hi | lo | hi]; gt receives TWO (B, C, HW) images, hi then lo (the dY operands of
 // the weight gradient's three accumulating launches), csum the sums of hi + lo
-extern "C" int gd_nhwc_to_nchw16(const void* g, int B, int HW, int C, void* gt, float* csum, int split, void* stream) {
+extern "C" int gd_nhwc_to_nchw16_ws(const void* g, int B, int HW, int C, void* gt, float* csum, int split, void* stream, void* ws,
+                                    size_t ws_bytes) {
     GD_CHECK_ARG(g && gt && B > 0 && HW > 0 && C > 0 && C % 8 == 0, "gd_nhwc_to_nchw16: C must be a multiple of 8");
-    if (csum) GD_CHECK_ARG(hipMemsetAsync(csum, 0, (size_t)C * sizeof(float), NS(stream)) == hipSuccess, "gd_nhwc_to_nchw16: memset failed");
+    GD_CHECK_ARG(((uintptr_t)ws % 16) == 0, "gd_nhwc_to_nchw16: the workspace must be 16-byte aligned");
     const long ntiles = (long)B * ((HW + TT - 1) / TT);
     const int cg = (C + TT - 1) / TT;
     long gy = 2048 / cg;
     if (gy > ntiles) gy = ntiles;
     if (gy < 1) gy = 1;
+    // ordered deterministic mode: one [C] slab of channel sums per blockIdx.y (and per launch of a split gradient: the lo
+    // part's slabs follow the hi part's), as many as fit
+    float* part = nullptr;
+    const int launches = split ? 2 : 1;
+    if (csum && gd_det_ordered(ws)) {
+        const size_t fit = ws_bytes / ((size_t)C * sizeof(float) * launches);
+        if ((size_t)gy > fit) gy = (long)fit;
+        if (gy < 2) gy = 1;         // one adder per channel and launch: the atomic path is already ordered
+        else part = (float*)ws;
+    }
+    if (csum && !part)              // the atomics add onto zeros; the ordered path overwrites
+        GD_CHECK_ARG(hipMemsetAsync(csum, 0, (size_t)C * sizeof(float), NS(stream)) == hipSuccess, "gd_nhwc_to_nchw16: memset failed");
     hipLaunchKernelGGL(nhwc_to_nchw16_kernel, dim3(cg, (unsigned)gy), dim3(256), 0, NS(stream), (const unsigned short*)g, B, HW, C,
-                       split ? 3 * C : C, (unsigned short*)gt, csum);
+                       split ? 3 * C : C, (unsigned short*)gt, csum, part);
     if (split)
         hipLaunchKernelGGL(nhwc_to_nchw16_kernel, dim3(cg, (unsigned)gy), dim3(256), 0, NS(stream), (const unsigned short*)g + C, B, HW,
-                           C, 3 * C, (unsigned short*)gt + (long)B * C * HW, csum);
+                           C, 3 * C, (unsigned short*)gt + (long)B * C * HW, csum, part ? part + gy * C : nullptr);
     GD_LAUNCH_CHECK();
+    if (part) return gd_det_reduce_launch(part, (int)gy * launches, csum, 1, 1, C, 0, C, nullptr, 0, NS(stream));
     return 0;
+}
+
+extern "C" int gd_nhwc_to_nchw16(const void* g, int B, int HW, int C, void* gt, float* csum, int split, void* stream) {
+    return gd_nhwc_to_nchw16_ws(g, B, HW, C, gt, csum, split, stream, nullptr, 0);
 }

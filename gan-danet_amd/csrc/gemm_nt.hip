@@ -5,7 +5,9 @@
 // fragments want.  k = (segment s, offset kk): a segment is one image of the batch, which is how the
 // convolution weight gradient (k = output pixels of all images), CAM's Gram matrix, nn.Linear forward
 // and the unfused fp32 PAM products all map onto one kernel.  The reduction is split over
-// blockIdx.z; partial tiles are combined with fp32 atomics (hardware global_atomic_add_f32).
+// blockIdx.z; partial tiles are combined with fp32 atomics (hardware global_atomic_add_f32), or -- ordered
+// deterministic mode -- written as alpha * acc into a dense [split][B][M][N] slab of the caller's workspace that
+// det_reduce.hip sums in ascending split order (adding the bias once, honouring c_bs / ldc / accumulate).
 #include "common.h"
 #include "tile_mma.h"
 #include "../../include/gandanet.h"
@@ -32,7 +34,7 @@ __global__ void fill_zero_kernel(float* c, long c_bs, long ldc, int B, int M, in
 // with float4 loads (4 consecutive k per thread) and 8-byte LDS writes instead of scalar loads / 2-byte writes.
 template <int BM, int MODE, bool VEC = false>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(const gd_gemm_nt_desc d, int ktiles, int tiles_per_split,
-                                                      int splits) {
+                                                      int splits, float* part) {
     constexpr bool BF16 = MODE != gd::MODE_F32;     // 16-bit LDS images (one, or hi + lo for the split mode)
     constexpr bool X3 = MODE == gd::MODE_X3;
     constexpr int A_PL = BM * gd::TilePol<MODE>::LD, B_PL = gd::TILE_BN * gd::TilePol<MODE>::LD;
@@ -256,6 +258,23 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const gd_gemm_nt_desc d, i
     }
 
     const float alpha = d.alpha ? *d.alpha : 1.f;
+    if (part) {     // ordered deterministic mode (uniform): plain stores into this split's slab, lanes run along n
+        float* pb = part + ((long)split * d.B + b) * d.M * d.N;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int n = n0 + wn * TN * 32 + j * 32 + r;
+                if (n >= d.N) continue;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int m = m0 + wm * TM * 32 + i * 32 + gd::acc_row(e, h);
+                    if (m < d.M) pb[(long)m * d.N + n] = acc[i][j][e] * alpha;
+                }
+            }
+        }
+        return;
+    }
     float* cb = d.c + (long)b * d.c_bs;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -279,10 +298,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const gd_gemm_nt_desc d, i
 }
 
 template <int BM>
-int launch(const gd_gemm_nt_desc& d, int ktiles, int splits, hipStream_t s) {
-    const int tps = (ktiles + splits - 1) / splits;
-    splits = (ktiles + tps - 1) / tps;  // no empty splits
-    if (splits > 1 && !d.accumulate) {
+int launch(const gd_gemm_nt_desc& d, int ktiles, int tps, int splits, float* part, hipStream_t s) {
+    if (splits > 1 && !d.accumulate && !part) {          // atomic path only: the ordered path overwrites
         const long total = (long)d.B * d.M * d.N;
         const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
         hipLaunchKernelGGL(fill_zero_kernel, dim3(blocks), dim3(256), 0, s, d.c, d.c_bs, d.ldc, d.B, d.M, d.N);
@@ -294,26 +311,25 @@ int launch(const gd_gemm_nt_desc& d, int ktiles, int splits, hipStream_t s) {
                      d.a_ss % 4 == 0 && d.b_ss % 4 == 0 && d.a_bs % 4 == 0 && d.b_bs % 4 == 0 &&
                      ((uintptr_t)d.a % 16) == 0 && ((uintptr_t)d.bm % 16) == 0;
     if (d.precision == GD_PREC_BF16) {
-        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_BF16, true>), grid, dim3(256), 0, s, d, ktiles, tps, splits);
-        else hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_BF16, false>), grid, dim3(256), 0, s, d, ktiles, tps, splits);
+        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_BF16, true>), grid, dim3(256), 0, s, d, ktiles, tps, splits, part);
+        else hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_BF16, false>), grid, dim3(256), 0, s, d, ktiles, tps, splits, part);
     } else if (d.precision == GD_PREC_X3) {
-        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_X3, true>), grid, dim3(256), 0, s, d, ktiles, tps, splits);
-        else hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_X3, false>), grid, dim3(256), 0, s, d, ktiles, tps, splits);
+        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_X3, true>), grid, dim3(256), 0, s, d, ktiles, tps, splits, part);
+        else hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_X3, false>), grid, dim3(256), 0, s, d, ktiles, tps, splits, part);
     } else {
-        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_F32, true>), grid, dim3(256), 0, s, d, ktiles, tps, splits);
-        else hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_F32, false>), grid, dim3(256), 0, s, d, ktiles, tps, splits);
+        if (vec) hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_F32, true>), grid, dim3(256), 0, s, d, ktiles, tps, splits, part);
+        else hipLaunchKernelGGL((gemm_nt_kernel<BM, gd::MODE_F32, false>), grid, dim3(256), 0, s, d, ktiles, tps, splits, part);
     }
     GD_LAUNCH_CHECK();
+    if (part) return gd_det_reduce_launch(part, splits, d.c, d.B, d.M, d.N, d.c_bs, d.ldc, d.bias, d.accumulate, s);
     return 0;
 }
 
-}  // namespace
-
-extern "C" int gd_gemm_nt(const gd_gemm_nt_desc* dp, void* stream) {
-    GD_CHECK_ARG(dp != nullptr, "gd_gemm_nt: null descriptor");
-    const gd_gemm_nt_desc& d = *dp;
+// Split count of a descriptor: a pure function of the sizes, the deterministic mode and the workspace size, shared by
+// gd_gemm_nt_plan and the launcher so that the two cannot drift.
+struct NtPlan { int ktiles, bm, tiles_per_split, splits, ordered; size_t ws_needed; };
+int nt_plan(const gd_gemm_nt_desc& d, size_t ws_bytes, NtPlan* p) {
     GD_CHECK_ARG(d.B > 0 && d.M > 0 && d.N > 0 && d.kseg > 0 && d.klen > 0, "gd_gemm_nt: bad sizes");
-    GD_CHECK_ARG(d.a && d.bm && d.c, "gd_gemm_nt: null tensor");
     GD_CHECK_ARG((long)d.kseg * d.klen < (1L << 31), "gd_gemm_nt: reduction too long");
     GD_CHECK_ARG((d.in_scale == nullptr) == (d.in_shift == nullptr), "gd_gemm_nt: in_scale/in_shift must come together");
     GD_CHECK_ARG(d.precision == GD_PREC_FP32 || d.precision == GD_PREC_BF16 || d.precision == GD_PREC_X3, "gd_gemm_nt: bad precision");
@@ -337,10 +353,46 @@ extern "C" int gd_gemm_nt(const gd_gemm_nt_desc* dp, void* stream) {
         if (splits > ktiles / 8) splits = ktiles / 8 > 0 ? ktiles / 8 : 1;
     }
     if (splits > ktiles) splits = ktiles;
-    if (gd_get_deterministic()) splits = 1;                  // deterministic mode: no atomic combine of k-splits
+    const bool det = gd_get_deterministic() != 0, ordered_mode = det && gd_get_det_reduce() == 1;
+    if (det && !ordered_mode) splits = 1;                    // deterministic, unsplit: no atomic combine of k-splits
     if ((long)d.B * splits > 65535) splits = (int)(65535 / d.B);
-    hipStream_t s = (hipStream_t)stream;
-    if (bm == 32) return launch<32>(d, ktiles, splits, s);
-    if (bm == 64) return launch<64>(d, ktiles, splits, s);
-    return launch<128>(d, ktiles, splits, s);
+    const size_t out_bytes = (size_t)d.B * d.M * d.N * sizeof(float);
+    if (ordered_mode) {                                      // ordered: one dense slab per split must fit the workspace
+        const size_t fit = ws_bytes / out_bytes;
+        if ((size_t)splits > fit) splits = (int)fit;
+        if (splits < 2) splits = 1;
+    }
+    const int tps = (ktiles + splits - 1) / splits;
+    splits = (ktiles + tps - 1) / tps;                       // no empty splits
+    p->ktiles = ktiles; p->bm = bm; p->tiles_per_split = tps; p->splits = splits;
+    p->ordered = ordered_mode && splits > 1;
+    p->ws_needed = p->ordered ? (size_t)splits * out_bytes : 0;
+    return 0;
 }
+
+}  // namespace
+
+extern "C" int gd_gemm_nt_plan(const gd_gemm_nt_desc* dp, size_t ws_bytes, int* splits, size_t* ws_needed) {
+    GD_CHECK_ARG(dp != nullptr, "gd_gemm_nt_plan: null descriptor");
+    NtPlan p;
+    if (nt_plan(*dp, ws_bytes, &p)) return -1;
+    if (splits) *splits = p.splits;
+    if (ws_needed) *ws_needed = p.ws_needed;
+    return 0;
+}
+
+extern "C" int gd_gemm_nt_ws(const gd_gemm_nt_desc* dp, void* stream, void* ws, size_t ws_bytes) {
+    GD_CHECK_ARG(dp != nullptr, "gd_gemm_nt: null descriptor");
+    const gd_gemm_nt_desc& d = *dp;
+    GD_CHECK_ARG(d.a && d.bm && d.c, "gd_gemm_nt: null tensor");
+    GD_CHECK_ARG(((uintptr_t)ws % 16) == 0, "gd_gemm_nt: the workspace must be 16-byte aligned");
+    NtPlan p;
+    if (nt_plan(d, ws ? ws_bytes : 0, &p)) return -1;
+    float* part = p.ordered ? (float*)ws : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    if (p.bm == 32) return launch<32>(d, p.ktiles, p.tiles_per_split, p.splits, part, s);
+    if (p.bm == 64) return launch<64>(d, p.ktiles, p.tiles_per_split, p.splits, part, s);
+    return launch<128>(d, p.ktiles, p.tiles_per_split, p.splits, part, s);
+}
+
+extern "C" int gd_gemm_nt(const gd_gemm_nt_desc* dp, void* stream) { return gd_gemm_nt_ws(dp, stream, nullptr, 0); }

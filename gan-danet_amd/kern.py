@@ -211,7 +211,7 @@ def gemm_nt(*, B: int, M: int, N: int, kseg: int, klen: int, a: Tensor, a_bs: in
     d.c, d.c_bs, d.ldc = _ptr(c), c_bs, ldc
     d.alpha, d.bias = _ptr(alpha), _ptr(bias)
     d.accumulate, d.splits, d.precision = int(accumulate), splits, precision
-    L.check(lib().gd_gemm_nt(C.byref(d), _stream()), "gd_gemm_nt")
+    L.check(lib().gd_gemm_nt_ws(C.byref(d), _stream(), *det_ws()), "gd_gemm_nt")
 
 
 def conv2d_wgrad(dy: Tensor, x: Tensor, k: int, stride: int, pad: int, precision: int, *, in_scale=None,
@@ -243,9 +243,9 @@ def _conv2d_wgrad(dy, x, k, stride, pad, precision, in_scale, in_shift, in_relu,
                 # copies instead of strided 4-byte gathers (the 2C -> C fuse convs: 12.4 -> 10.5 ms incl. the pack, bench shape)
                 x_ld = (Cin + 7) // 8 * 8
                 _, x16 = pack_bf16(x, Cin, Hi * Wi, t_shape=(Hi * Wi, x_ld))
-        L.check(lib().gd_conv3x3_wgrad(_ptr(dy), dbs, _ptr(dy16), _ptr(x), xbs, _ptr(x16), x_ld, _ptr(in_scale),
-                                       _ptr(in_shift), int(in_relu), B, Cout, Cin, Hi, Wi, stride, 0, _ptr(dw), _stream()),
-                "gd_conv3x3_wgrad")
+        L.check(lib().gd_conv3x3_wgrad_ws(_ptr(dy), dbs, _ptr(dy16), _ptr(x), xbs, _ptr(x16), x_ld, _ptr(in_scale),
+                                       _ptr(in_shift), int(in_relu), B, Cout, Cin, Hi, Wi, stride, 0, _ptr(dw), _stream(),
+                                          *det_ws()), "gd_conv3x3_wgrad")
         return dw
     if k == 1 and stride == 1 and pad == 0:
         # 1x1: dW = dY X~^T with both operands pixel-contiguous -> plain NT GEMM (float4-staged when aligned); a fused
@@ -842,14 +842,66 @@ def pam_flash_fwd_shift(qt, kt, v, B, N, Npad, Cn, Cp, gamma, x, out, o_attn, ls
 PAM_BWD_FORM = int(os.environ.get("GD_PAM_BWD", "0"))
 PAM_SCRATCH_CAP = 40 << 30                                         # scratch of one call: at most 40 GiB
 DETERMINISTIC = False
+DET_REDUCE = "unsplit"            # how deterministic mode reduces over splits: "unsplit" or "ordered" (gd_set_det_reduce)
+_DET_REDUCE_MODES = {"unsplit": 0, "ordered": 1}
+DET_WS_BYTES: Optional[int] = None   # size of the ordered mode's workspace; None = GD_DET_WS_MB MiB (default 256)
+_DET_WS: dict = {}                # (device index, stream handle) -> uint8 workspace tensor
 
 
-def set_deterministic(on: bool) -> None:
+def set_deterministic(on: bool, reduce: Optional[str] = None) -> None:
     """bitwise-reproducible kernels wherever a faster order-dependent form exists: PAM dQ through bf16 parts instead of
-    fp32 atomics, split-K GEMMs and 3x3 weight gradients unsplit (gd_set_deterministic)"""
-    global DETERMINISTIC
+    fp32 atomics (gd_set_deterministic), and the split reductions (split-K GEMMs, 3x3 weight gradients, Discriminator1's
+    stem gradient and bias sums) in the form ``reduce`` names: "unsplit" -- one adder per output element, the initial
+    setting -- or "ordered" -- the default mode's splits, each writing a partial slab that a reduce kernel sums in
+    ascending order (gd_set_det_reduce).  ``reduce=None`` keeps the current setting."""
+    global DETERMINISTIC, DET_REDUCE
+    if reduce is not None and reduce not in _DET_REDUCE_MODES:
+        raise L.GandanetError(f"set_deterministic: reduce must be one of {sorted(_DET_REDUCE_MODES)}, got {reduce!r}")
     DETERMINISTIC = bool(on)
     lib().gd_set_deterministic(int(DETERMINISTIC))
+    if reduce is not None:
+        L.check(lib().gd_set_det_reduce(_DET_REDUCE_MODES[reduce]), "gd_set_det_reduce")
+        DET_REDUCE = reduce
+
+
+def det_ws_bytes() -> int:
+    return int(DET_WS_BYTES) if DET_WS_BYTES is not None else int(os.environ.get("GD_DET_WS_MB", "256")) << 20
+
+
+def det_ws() -> Tuple[Optional[int], int]:
+    """(pointer, bytes) of the ordered mode's partial-slab workspace, (None, 0) outside that mode.  One tensor per
+    (device, stream), allocated on first use.  Consecutive calls on one stream may share it because every use is
+    stream-ordered: a split kernel and its reduce kernel are enqueued back to back, and the next call's kernels run
+    after them.  Two streams never share one."""
+    if not (DETERMINISTIC and DET_REDUCE == "ordered"):
+        return None, 0
+    nbytes = det_ws_bytes()
+    if nbytes <= 0:
+        return None, 0
+    key = (torch.cuda.current_device(), _stream())
+    t = _DET_WS.get(key)
+    if t is None or t.numel() != nbytes:
+        t = _DET_WS[key] = torch.empty(nbytes, device=torch.device("cuda", key[0]), dtype=torch.uint8)
+    return t.data_ptr(), nbytes
+
+
+def conv3x3_wgrad_plan(B: int, Cout: int, Cin: int, H: int, W: int, stride: int = 1, ws_bytes: Optional[int] = None):
+    """(pixel splits, workspace bytes used) of a 3x3 weight gradient under the current modes; host only"""
+    sp, need = C.c_int(0), C.c_size_t(0)
+    nb = det_ws_bytes() if ws_bytes is None else ws_bytes
+    L.check(lib().gd_conv3x3_wgrad_plan(B, Cout, Cin, H, W, stride, nb, C.byref(sp), C.byref(need)), "gd_conv3x3_wgrad_plan")
+    return sp.value, need.value
+
+
+def gemm_nt_plan(*, B: int, M: int, N: int, kseg: int, klen: int, splits: int = 0, precision: int = L.PREC_FP32,
+                 ws_bytes: Optional[int] = None):
+    """(k-splits, workspace bytes used) of an NT GEMM of these sizes under the current modes; host only"""
+    d = L.GemmNTDesc()
+    d.B, d.M, d.N, d.kseg, d.klen, d.splits, d.precision = B, M, N, kseg, klen, splits, precision
+    sp, need = C.c_int(0), C.c_size_t(0)
+    nb = det_ws_bytes() if ws_bytes is None else ws_bytes
+    L.check(lib().gd_gemm_nt_plan(C.byref(d), nb, C.byref(sp), C.byref(need)), "gd_gemm_nt_plan")
+    return sp.value, need.value
 
 
 def pam_bwd_form() -> int:
@@ -999,8 +1051,8 @@ def conv3x3_wgrad_packed(dy16: Tensor, x16: Tensor, H: int, W: int, stride: int 
     Cin = x16.shape[2]
     dw = torch.empty(Cout, Cin, 3, 3, device=dy16.device, dtype=torch.float32)
     with _ConvBracket("wgrad_packed", 3, stride, Cin, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1, B):
-        L.check(lib().gd_conv3x3_wgrad(None, 0, _ptr(dy16), None, 0, _ptr(x16), Cin, None, None, 0, B, Cout, Cin, H, W, stride,
-                                       0, _ptr(dw), _stream()), "gd_conv3x3_wgrad")
+        L.check(lib().gd_conv3x3_wgrad_ws(None, 0, _ptr(dy16), None, 0, _ptr(x16), Cin, None, None, 0, B, Cout, Cin, H, W, stride,
+                                       0, _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
     return dw
 
 
@@ -1054,8 +1106,8 @@ def conv3x3_wgrad_x3(dy2: Tensor, x3: Tensor, H: int, W: int) -> Tensor:
     dw = torch.empty(Cout, Cin, 3, 3, device=dy2.device, dtype=torch.float32)
     with _ConvBracket("wgrad_x3", 3, 1, Cin, Cout, H, W, B):
         for j, (dpart, xoff) in enumerate(((0, 0), (1, 0), (0, Cin))):
-            L.check(lib().gd_conv3x3_wgrad(None, 0, dy2[dpart].data_ptr(), None, 0, x3.data_ptr() + 2 * xoff, 3 * Cin, None, None,
-                                           0, B, Cout, Cin, H, W, 1, int(j > 0), _ptr(dw), _stream()), "gd_conv3x3_wgrad")
+            L.check(lib().gd_conv3x3_wgrad_ws(None, 0, dy2[dpart].data_ptr(), None, 0, x3.data_ptr() + 2 * xoff, 3 * Cin, None, None,
+                                           0, B, Cout, Cin, H, W, 1, int(j > 0), _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
     return dw
 
 
@@ -1087,8 +1139,8 @@ def disc_stem_wgrad(g: Tensor, img: Tensor, want_bias: bool = True, split: bool 
         raise L.GandanetError(f"disc_stem_wgrad: gradient {tuple(g.shape)} does not match image {tuple(img.shape)}")
     dw = torch.empty(Co, Ci, 3, 3, device=g.device, dtype=torch.float32)
     db = torch.empty(Co, device=g.device, dtype=torch.float32) if want_bias else None
-    L.check(lib().gd_disc_stem_wgrad(_ptr(g), _ptr(img), B, Ci, H, W, Co, _ptr(dw), _ptr(db), int(split), _stream()),
-            "gd_disc_stem_wgrad")
+    L.check(lib().gd_disc_stem_wgrad_ws(_ptr(g), _ptr(img), B, Ci, H, W, Co, _ptr(dw), _ptr(db), int(split), _stream(),
+                                        *det_ws()), "gd_disc_stem_wgrad")
     return dw, db
 
 
@@ -1163,7 +1215,8 @@ def nhwc_to_nchw16(g: Tensor, want_sum: bool, split: bool = False):
     Cc //= 3 if split else 1
     gt = torch.empty((2, B, Cc, H, W) if split else (B, Cc, H, W), device=g.device, dtype=torch.bfloat16)
     cs = torch.empty(Cc, device=g.device, dtype=torch.float32) if want_sum else None
-    L.check(lib().gd_nhwc_to_nchw16(_ptr(g), B, H * W, Cc, _ptr(gt), _ptr(cs), int(split), _stream()), "gd_nhwc_to_nchw16")
+    L.check(lib().gd_nhwc_to_nchw16_ws(_ptr(g), B, H * W, Cc, _ptr(gt), _ptr(cs), int(split), _stream(), *det_ws()),
+            "gd_nhwc_to_nchw16")
     return gt, cs
 
 
@@ -1181,13 +1234,13 @@ def conv3x3_wgrad_nhwc(g: Tensor, x: Tensor, stride: int, want_bias: bool, split
         dw = torch.empty(Cout, Cin, 3, 3, device=g.device, dtype=torch.float32)
         with _ConvBracket("wgrad_nhwc_x3", 3, stride, Cin, Cout, g.shape[1], g.shape[2], B):
             for j, (dpart, xoff) in enumerate(((0, 0), (1, 0), (0, Cin))):
-                L.check(lib().gd_conv3x3_wgrad(None, 0, gt[dpart].data_ptr(), None, 0, x.data_ptr() + 2 * xoff, 3 * Cin, None, None,
-                                               0, B, Cout, Cin, H, W, stride, int(j > 0), _ptr(dw), _stream()), "gd_conv3x3_wgrad")
+                L.check(lib().gd_conv3x3_wgrad_ws(None, 0, gt[dpart].data_ptr(), None, 0, x.data_ptr() + 2 * xoff, 3 * Cin, None, None,
+                                               0, B, Cout, Cin, H, W, stride, int(j > 0), _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
         return dw, db
     dw = torch.empty(Cout, Cin, 3, 3, device=g.device, dtype=torch.float32)
     with _ConvBracket("wgrad_nhwc", 3, stride, Cin, Cout, g.shape[1], g.shape[2], B):
-        L.check(lib().gd_conv3x3_wgrad(None, 0, _ptr(gt), None, 0, _ptr(x), Cin, None, None, 0, B, Cout, Cin, H, W, stride,
-                                       0, _ptr(dw), _stream()), "gd_conv3x3_wgrad")
+        L.check(lib().gd_conv3x3_wgrad_ws(None, 0, _ptr(gt), None, 0, _ptr(x), Cin, None, None, 0, B, Cout, Cin, H, W, stride,
+                                       0, _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
     return dw, db
 
 

@@ -61,9 +61,12 @@ DISC_NHWC = os.environ.get("GD_DISC_NHWC", "1") != "0"
 
 
 def disc1_trunk_eligible(x: torch.Tensor, ws) -> bool:
-    """16-bit or split-bf16 operand mode, non-deterministic mode (the bias sums and weight gradients use atomics), the
-    reference's channel ladder (.. -> 64 -> .. multiples of 8), at most 4 image channels"""
-    return (DISC_NHWC and (sixteen_bit("disc") or _x3("disc")) and not K.DETERMINISTIC and x.dim() == 4 and x.shape[1] <= 4
+    """16-bit or split-bf16 operand mode, the reference's channel ladder (.. -> 64 -> .. multiples of 8), at most 4 image
+    channels, and a mode in which the trunk's bias sums and weight gradients are reproducible when that is asked for:
+    the default mode (fp32 atomics, nothing asked) or deterministic mode with the "ordered" reduction (partial slabs
+    summed in a fixed order); deterministic mode with the "unsplit" reduction stays on the fp32-NCHW chain"""
+    return (DISC_NHWC and (sixteen_bit("disc") or _x3("disc")) and (not K.DETERMINISTIC or K.DET_REDUCE == "ordered")
+            and x.dim() == 4 and x.shape[1] <= 4
             and ws[0].shape[0] == 64 and all(w.shape[0] % 8 == 0 and w.shape[2:] == (3, 3) for w in ws))
 
 

@@ -30,6 +30,18 @@ extern "C" {
  * gradient run unsplit instead of combining partial sums with fp32 atomics) -- bitwise reproducible, slower. */
 void gd_set_deterministic(int on);
 int gd_get_deterministic(void);
+/* how deterministic mode reduces over splits (process-global, read only while gd_get_deterministic() is 1):
+ *   0 = unsplit (the default): one adder per output element, as described above;
+ *   1 = ordered: the split kernels keep the split count of the default mode, every split writes its partial result with
+ *       plain stores into slab [split] of a caller-owned workspace, and a reduce kernel adds the slabs in ascending split
+ *       order in fp32 -- no atomics, bitwise reproducible, parallel.  It applies to the entry points that take a
+ *       workspace (gd_conv3x3_wgrad_ws, gd_gemm_nt_ws, gd_disc_stem_wgrad_ws, gd_nhwc_to_nchw16_ws); their split count is
+ *       the default mode's, clamped so that splits * output bytes <= ws_bytes, and a call whose workspace holds fewer
+ *       than two slabs (or is NULL) runs unsplit.  The workspace must be 16-byte aligned; calls on one stream may share
+ *       it (every use is stream-ordered), calls on different streams must not.
+ * gd_set_det_reduce returns 0, or -1 for any other mode. */
+int gd_set_det_reduce(int mode);
+int gd_get_det_reduce(void);
 int gd_version(void);
 /* copies the calling thread's last error message (NUL terminated) into buf; returns its length */
 int gd_last_error(char* buf, int n);
@@ -103,6 +115,15 @@ int gd_conv3x3(const gd_conv_desc* d, void* ws, size_t ws_bytes, void* stream);
 int gd_conv3x3_wgrad(const float* dy, long dy_bs, const void* dy_bf16, const float* x, long x_bs, const void* x_nhwc16,
                      int x_ld, const float* in_scale, const float* in_shift, int in_relu, int B, int Cout, int Cin, int H,
                      int W, int stride, int accumulate, float* dw, void* stream);   /* H, W = INPUT size; stride 1 or 2 (pad 1) */
+/* the same with a workspace for the ordered deterministic mode (slabs [split][Cout][Cin][9] fp32).  ws == NULL, or any
+ * other mode: exactly gd_conv3x3_wgrad. */
+int gd_conv3x3_wgrad_ws(const float* dy, long dy_bs, const void* dy_bf16, const float* x, long x_bs, const void* x_nhwc16,
+                        int x_ld, const float* in_scale, const float* in_shift, int in_relu, int B, int Cout, int Cin, int H,
+                        int W, int stride, int accumulate, float* dw, void* stream, void* ws, size_t ws_bytes);
+/* host-only: the pixel-split count gd_conv3x3_wgrad_ws will launch for these sizes under the current modes with a
+ * workspace of ws_bytes, and the bytes of it that launch uses (0 when it does not touch the workspace).  No GPU call.
+ * ws_bytes = SIZE_MAX asks what an unclamped ordered launch needs. */
+int gd_conv3x3_wgrad_plan(int B, int Cout, int Cin, int H, int W, int stride, size_t ws_bytes, int* splits, size_t* ws_needed);
 
 /* ------------------------------------------------------------------------------------------
  * "NT" GEMM with the long reduction split over workgroups:
@@ -135,6 +156,13 @@ typedef struct gd_gemm_nt_desc {
     int precision;
 } gd_gemm_nt_desc;
 int gd_gemm_nt(const gd_gemm_nt_desc* d, void* stream);
+/* the same with a workspace for the ordered deterministic mode: split s writes alpha * acc into a dense [split][B][M][N]
+ * fp32 slab, the reduce kernel adds the bias once and writes through c_bs / ldc, honouring accumulate.  ws == NULL, or any
+ * other mode: exactly gd_gemm_nt. */
+int gd_gemm_nt_ws(const gd_gemm_nt_desc* d, void* stream, void* ws, size_t ws_bytes);
+/* host-only: the k-split count gd_gemm_nt_ws will launch for this descriptor (its pointers are not read) under the
+ * current modes with a workspace of ws_bytes, and the bytes of it that launch uses.  No GPU call. */
+int gd_gemm_nt_plan(const gd_gemm_nt_desc* d, size_t ws_bytes, int* splits, size_t* ws_needed);
 
 /* ------------------------------------------------------------------------------------------
  * BatchNorm2d (generator.py:32,61,149,189,219,223).  x is (B, C, H, W) with batch stride x_bs.
@@ -322,6 +350,9 @@ int gd_nhwc_l1_grad(const void* a, const void* b, long n, const float* upstream,
 int gd_disc_stem_fwd(const float* img, int B, int Ci, int H, int W, const float* w, const float* bias, int Co, float slope,
                      void* y, int split, void* stream);
 int gd_disc_stem_wgrad(const void* g, const float* img, int B, int Ci, int H, int W, int Co, float* dw, float* db, int split, void* stream);
+/* with a workspace for the ordered deterministic mode: one [Ci][Co][10] fp32 slab per workgroup instead of the atomics */
+int gd_disc_stem_wgrad_ws(const void* g, const float* img, int B, int Ci, int H, int W, int Co, float* dw, float* db, int split,
+                          void* stream, void* ws, size_t ws_bytes);
 int gd_disc_stem_dgrad(const void* g, int B, int Ci, int H, int W, const float* w, int Co, float* dimg, int split, void* stream);
 int gd_conv3x3_nhwc_s2(const void* x, const void* wpack, const float* bias, void* y, int B, int H, int W, int K, int M, int act,
                        float slope, int split, void* stream);
@@ -330,6 +361,9 @@ int gd_conv3x3_nhwc_s2_dgrad(const void* dy, const void* wpack_t, const void* ac
 int gd_nhwc_flatten_fwd(const void* y, int B, int HW, int C, float* f, int split, void* stream);
 int gd_nhwc_flatten_bwd(const float* df, const void* y, float slope, int B, int HW, int C, void* g, int split, void* stream);
 int gd_nhwc_to_nchw16(const void* g, int B, int HW, int C, void* gt, float* csum, int split, void* stream);
+/* with a workspace for the ordered deterministic mode: one [C] fp32 slab of channel sums per workgroup row */
+int gd_nhwc_to_nchw16_ws(const void* g, int B, int HW, int C, void* gt, float* csum, int split, void* stream, void* ws,
+                         size_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * PAM, fused (flash) form with 16-bit MFMA operands and fp32 softmax statistics (generator.py:115-122).

@@ -1,0 +1,433 @@
+"""GPU: the "ordered" deterministic reduction mode (gd.set_deterministic(True, reduce="ordered")): every split reduction
+keeps the default mode's splits, writes one partial slab per split and sums the slabs in ascending order.
+
+Per kernel and route: (a) two ordered runs are bit-equal, (b) the host plan says the shape really splits, (c) the ordered
+result matches today's unsplit deterministic result to rel-L2 1e-5 (the bound of
+test_deterministic_mode_makes_split_reductions_reproducible for the same kind of reordering), (d) against an fp64 CPU
+reference built from the operands as the kernel rounds them the ordered error is at most max(1e-6, 1.5 x the unsplit
+path's error): splitting shortens the fp32 chains, 1.5 is slack where both sit at round-off."""
+import contextlib
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from fill import fill_module
+from gpu_util import DEV, assert_close, bf16_round, load_golden, rell2, seeded
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def gd():
+    import gan_danet_amd as g
+    from gan_danet_amd import _lib
+    _lib.load()
+    return g
+
+
+def _K():
+    from gan_danet_amd import kern
+    return kern
+
+
+@contextlib.contextmanager
+def _mode(gd, on, reduce="unsplit"):
+    gd.set_deterministic(on, reduce=reduce)
+    try:
+        yield
+    finally:
+        gd.set_deterministic(False, reduce="unsplit")
+
+
+def _tuple(v):
+    return tuple(t.clone() for t in (v if isinstance(v, (tuple, list)) else (v,)))
+
+
+def _check(gd, run, plan, refs, what):
+    """run() -> tensor or tuple of tensors; plan() -> split count under the current modes (None: no plan query for this
+    kernel); refs: fp64 CPU references, one per output"""
+    with _mode(gd, True, "unsplit"):
+        if plan is not None:
+            assert plan() == 1, f"{what}: the unsplit mode must not split"
+        u = _tuple(run())
+    with _mode(gd, True, "ordered"):
+        if plan is not None:
+            assert plan() > 1, f"{what}: the shape does not split, the case shows nothing"          # (b)
+        o1, o2 = _tuple(run()), _tuple(run())
+    for i, (a, b, un, ref) in enumerate(zip(o1, o2, u, refs)):
+        tag = f"{what}[{i}]"
+        assert torch.isfinite(a).all(), tag
+        assert torch.equal(a, b), f"{tag}: two ordered runs differ"                                  # (a)
+        e_ou, e_o, e_u = rell2(a, un), rell2(a, ref), rell2(un, ref)
+        print(f"{tag}: ordered vs unsplit {e_ou:.3e}; vs fp64: ordered {e_o:.3e} unsplit {e_u:.3e}")
+        assert e_ou <= 1e-5, f"{tag}: ordered vs unsplit rel-L2 {e_ou:.3e} > 1e-5"                  # (c)
+        assert e_o <= max(1e-6, 1.5 * e_u), f"{tag}: ordered err {e_o:.3e} vs unsplit err {e_u:.3e}"   # (d)
+
+
+def _wgrad_ref(x, dy, stride, k=3, pad=1):
+    return torch.nn.grad.conv2d_weight(x.double(), (dy.shape[1], x.shape[1], k, k), dy.double(), stride=stride, padding=pad)
+
+
+def _nhwc(t):      # (B, C, H, W) fp32 cpu -> (B, H, W, C) bf16 gpu
+    return t.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(DEV)
+
+
+def _split(t):
+    hi = bf16_round(t)
+    return hi, bf16_round(t - hi)
+
+
+def _nhwc_split(t):      # (B, C, H, W) fp32 cpu -> (B, H, W, 3 C) bf16 gpu, [hi | lo | hi]
+    hi, lo = _split(t)
+    return torch.cat([hi, lo, hi], 1).permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(DEV)
+
+
+# B, Cin, H, W, Cout, stride: which instantiation of conv3x3_wgrad_kernel the launcher picks
+WGRAD_CASES = {
+    "f32staging_nw2": (4, 64, 96, 96, 24, 1),          # <2, 1>, fp32 operands converted while staging
+    "f32staging_nw6": (2, 64, 48, 48, 192, 1),         # <6, 1>
+    "f32staging_nw4": (2, 64, 48, 48, 128, 1),         # <4, 1>
+    "piped_nw4": (2, 128, 48, 48, 128, 1),             # Cout > 32, Cin >= 128: dy16 + x16, <4, 1, false, PIPED>
+    "piped_nw6": (1, 128, 32, 64, 192, 1),             # <6, 1, false, PIPED>
+    "cs_136to24": (2, 136, 64, 64, 24, 1),             # Cout <= 32, five ci chunks: CS, three waves per workgroup
+    "stride2": (2, 64, 64, 64, 128, 2),                # <4, 2>
+    "stride2_nw2": (2, 32, 40, 72, 64, 2),             # <2, 2>
+    "stride2_nw6": (2, 32, 40, 40, 192, 2),            # <6, 2>
+    "ragged": (2, 40, 37, 45, 136, 1),                 # H, W no multiples of the 4 x 32 tile, Cin / Cout ragged
+    "ragged_stride2": (3, 40, 37, 45, 72, 2),
+}
+
+
+@pytest.mark.parametrize("case", sorted(WGRAD_CASES))
+def test_conv3x3_wgrad_bf16_routes(gd, case):
+    from gan_danet_amd import _lib as L
+    K = _K()
+    B, Cin, H, W, Cout, stride = WGRAD_CASES[case]
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    x, dy = seeded((B, Cin, H, W), 301), seeded((B, Cout, Ho, Wo), 302)
+    xg, dyg = x.to(DEV), dy.to(DEV)
+    ref = _wgrad_ref(bf16_round(x), bf16_round(dy), stride)
+    _check(gd, lambda: K.conv2d_wgrad(dyg, xg, 3, stride, 1, L.PREC_BF16),
+           lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, stride)[0], [ref], case)
+
+
+@pytest.mark.parametrize("shape", [(2, 136, 64, 64, 24, 1), (2, 64, 64, 64, 128, 2)], ids=["cs_piped", "stride2_piped"])
+def test_conv3x3_wgrad_packed_operands(gd, shape):
+    """both operands 16-bit: the software-pipelined CS form of the dense layers and the stride-2 form of the D trunk"""
+    K = _K()
+    B, Cin, H, W, Cout, stride = shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    x, dy = bf16_round(seeded((B, Cin, H, W), 303)), bf16_round(seeded((B, Cout, Ho, Wo), 304))
+    dy16 = dy.view(B, Cout, Ho * Wo).to(torch.bfloat16).to(DEV)
+    x16 = x.permute(0, 2, 3, 1).reshape(B, H * W, Cin).contiguous().to(torch.bfloat16).to(DEV)
+    _check(gd, lambda: K.conv3x3_wgrad_packed(dy16, x16, H, W, stride),
+           lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, stride)[0], [_wgrad_ref(x, dy, stride)], "packed")
+
+
+def test_conv3x3_wgrad_x3_three_accumulating_launches(gd):
+    K = _K()
+    B, Cin, H, W, Cout = 2, 64, 48, 64, 96
+    x, dy = seeded((B, Cin, H, W), 305), seeded((B, Cout, H, W), 306)
+    (xh, xl), (dh, dl) = _split(x), _split(dy)
+    ref = _wgrad_ref(xh, dh, 1) + _wgrad_ref(xh, dl, 1) + _wgrad_ref(xl, dh, 1)
+    dy2 = torch.stack([dh, dl]).view(2, B, Cout, H * W).to(torch.bfloat16).to(DEV)
+    x3 = _nhwc_split(x).view(B, H * W, 3 * Cin)
+    _check(gd, lambda: K.conv3x3_wgrad_x3(dy2, x3, H, W), lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, 1)[0], [ref], "x3")
+
+
+@pytest.mark.parametrize("split", [False, True], ids=["plain", "split"])
+def test_conv3x3_wgrad_nhwc_with_bias(gd, split):
+    """the D trunk's weight + bias gradient: gd_nhwc_to_nchw16 (channel sums) + gd_conv3x3_wgrad on pixel-major operands"""
+    K = _K()
+    B, Cin, H, W, Cout = 2, 64, 65, 96, 128
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    x, dy = seeded((B, Cin, H, W), 307), seeded((B, Cout, Ho, Wo), 308)
+    if split:
+        (xh, xl), (dh, dl) = _split(x), _split(dy)
+        refs = [_wgrad_ref(xh, dh, 2) + _wgrad_ref(xh, dl, 2) + _wgrad_ref(xl, dh, 2), (dh.double() + dl.double()).sum((0, 2, 3))]
+        g, xx = _nhwc_split(dy), _nhwc_split(x)
+    else:
+        x, dy = bf16_round(x), bf16_round(dy)
+        refs = [_wgrad_ref(x, dy, 2), dy.double().sum((0, 2, 3))]
+        g, xx = _nhwc(dy), _nhwc(x)
+    _check(gd, lambda: K.conv3x3_wgrad_nhwc(g, xx, 2, True, split),
+           lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, 2)[0], refs, "nhwc")
+
+
+def _rounded(t, prec):
+    """the operand as the NT GEMM's staging rounds it: (what multiplies as the high part, the low part or None)"""
+    if prec == "fp32":
+        return t.double(), None
+    hi, lo = _split(t)
+    return hi.double(), (lo.double() if prec == "x3" else None)
+
+
+def _nt_ref(a, b, prec):
+    """sum_k a[.., m, k] b[.., n, k] in fp64 from the rounded operands (x3: hi hi + lo hi + hi lo)"""
+    (ah, al), (bh, bl) = _rounded(a, prec), _rounded(b, prec)
+    r = ah @ bh.transpose(-1, -2)
+    if al is not None:
+        r = r + al @ bh.transpose(-1, -2) + ah @ bl.transpose(-1, -2)
+    return r
+
+
+PRECS = ["fp32", "bf16", "x3"]
+
+
+def _prec(name):
+    from gan_danet_amd import _lib as L
+    return {"fp32": L.PREC_FP32, "bf16": L.PREC_BF16, "x3": L.PREC_X3}[name]
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_gemm_nt_1x1_wgrad_with_bn_prologue(gd, prec):
+    K = _K()
+    B, Cin, H, W, Cout = 4, 64, 96, 96, 24
+    x, dy = seeded((B, Cin, H, W), 311), seeded((B, Cout, H, W), 312)
+    sc, sh = seeded((Cin,), 313).abs() + 0.5, seeded((Cin,), 314, 0.3)
+    xt = torch.relu(x.double() * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1)).float()   # fmaf, then ReLU
+    a = dy.permute(1, 0, 2, 3).reshape(Cout, -1)
+    b = xt.permute(1, 0, 2, 3).reshape(Cin, -1)
+    ref = _nt_ref(a, b, prec).view(Cout, Cin, 1, 1)
+    xg, dyg, scg, shg = x.to(DEV), dy.to(DEV), sc.to(DEV), sh.to(DEV)
+    _check(gd, lambda: K.conv2d_wgrad(dyg, xg, 1, 1, 0, _prec(prec), in_scale=scg, in_shift=shg, in_relu=True),
+           lambda: K.gemm_nt_plan(B=1, M=Cout, N=Cin, kseg=B, klen=H * W)[0], [ref], f"1x1 wgrad {prec}")
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_gemm_nt_gram_batched(gd, prec):
+    """CAM's Gram matrix X X^T, B > 1: the slab is [split][B][M][N]"""
+    K = _K()
+    B, Cn, N = 3, 40, 16384
+    x = seeded((B, Cn, N), 315)
+    xg = x.to(DEV)
+
+    def run():
+        c = torch.empty(B, Cn, Cn, device=DEV)
+        K.gemm_nt(B=B, M=Cn, N=Cn, kseg=1, klen=N, a=xg, a_bs=Cn * N, a_ss=0, lda=N, bm=xg, b_bs=Cn * N, b_ss=0, ldb=N, c=c,
+                  c_bs=Cn * Cn, ldc=Cn, precision=_prec(prec))
+        return c
+    _check(gd, run, lambda: K.gemm_nt_plan(B=B, M=Cn, N=Cn, kseg=1, klen=N)[0], [_nt_ref(x, x, prec)], f"gram {prec}")
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("accumulate", [False, True], ids=["overwrite", "accumulate"])
+def test_gemm_nt_linear_forward_bias_alpha_strided_output(gd, prec, accumulate):
+    """nn.Linear forward shape (one long reduction, non-VEC: klen % 32 != 0) with bias and a device alpha, written through
+    ldc > N; accumulate adds onto what C holds"""
+    K = _K()
+    M, N, Kin, ldc = 8, 24, 200001, 40
+    a, w, bias = seeded((M, Kin), 316), seeded((N, Kin), 317), seeded((N,), 318)
+    c0 = seeded((M, ldc), 319, 50.0)
+    ag, wg, bg = a.to(DEV), w.to(DEV), bias.to(DEV)
+    alpha = torch.tensor([0.37], device=DEV)
+    ref = _nt_ref(a, w, prec) * float(alpha.double().item()) + bias.double()
+    if accumulate:
+        ref = ref + c0[:, :N].double()
+
+    def run():
+        c = c0.to(DEV).clone()
+        K.gemm_nt(B=1, M=M, N=N, kseg=1, klen=Kin, a=ag, a_bs=0, a_ss=0, lda=Kin, bm=wg, b_bs=0, b_ss=0, ldb=Kin, c=c, c_bs=0,
+                  ldc=ldc, precision=_prec(prec), alpha=alpha, bias=bg, accumulate=accumulate)
+        assert torch.equal(c[:, N:].cpu(), c0[:, N:]), "the reduce kernel wrote outside the N columns"
+        return c[:, :N]
+    _check(gd, run, lambda: K.gemm_nt_plan(B=1, M=M, N=N, kseg=1, klen=Kin)[0], [ref], f"linear {prec}")
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_gemm_nt_im2col_4x4_conv_wgrad(gd, prec):
+    K = _K()
+    B, Cin, H, W, Cout = 4, 16, 96, 96, 32
+    Ho, Wo = H // 2, W // 2
+    x, dy = seeded((B, Cin, H, W), 320), seeded((B, Cout, Ho, Wo), 321)
+    cols = F.unfold(x, 4, padding=1, stride=2)                      # (B, Cin * 16, Ho * Wo): values are copies of x
+    a = dy.permute(1, 0, 2, 3).reshape(Cout, -1)
+    b = cols.permute(1, 0, 2).reshape(Cin * 16, -1)
+    ref = _nt_ref(a, b, prec).view(Cout, Cin, 4, 4)
+    xg, dyg = x.to(DEV), dy.to(DEV)
+    _check(gd, lambda: K.conv2d_wgrad(dyg, xg, 4, 2, 1, _prec(prec)),
+           lambda: K.gemm_nt_plan(B=1, M=Cout, N=Cin * 16, kseg=B, klen=Ho * Wo)[0], [ref], f"im2col {prec}")
+
+
+@pytest.mark.parametrize("ci,split", [(1, False), (3, False), (1, True)])
+def test_disc_stem_wgrad(gd, ci, split):
+    K = _K()
+    B, H, W, Co = 4, 96, 130, 64
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    img, g = seeded((B, ci, H, W), 322), seeded((B, Co, Ho, Wo), 323)
+    if split:
+        gh, gl = _split(g)
+        gsum = (gh.double() + gl.double())
+        gg = _nhwc_split(g)
+    else:
+        g = bf16_round(g)
+        gsum = g.double()
+        gg = _nhwc(g)
+    refs = [torch.nn.grad.conv2d_weight(img.double(), (Co, ci, 3, 3), gsum, stride=2, padding=1), gsum.sum((0, 2, 3))]
+    imgg = img.to(DEV)
+    _check(gd, lambda: K.disc_stem_wgrad(gg, imgg, True, split), None, refs, "stem")
+
+
+def test_workspace_clamp(gd, monkeypatch):
+    """a workspace of one slab + 1 byte runs unsplit, bit for bit; exactly two slabs run two splits"""
+    from gan_danet_amd import _lib as L
+    K = _K()
+    B, Cin, H, W, Cout = 4, 64, 96, 96, 24
+    x, dy = seeded((B, Cin, H, W), 331).to(DEV), seeded((B, Cout, H, W), 332).to(DEV)
+    a, bm = seeded((8, 200000), 333).to(DEV), seeded((24, 200000), 334).to(DEV)
+
+    def run():
+        dw = K.conv2d_wgrad(dy, x, 3, 1, 1, L.PREC_BF16)
+        c = torch.empty(1, 8, 24, device=DEV)
+        K.gemm_nt(B=1, M=8, N=24, kseg=1, klen=200000, a=a, a_bs=a.numel(), a_ss=0, lda=200000, bm=bm, b_bs=bm.numel(), b_ss=0,
+                  ldb=200000, c=c, c_bs=8 * 24, ldc=24, precision=L.PREC_FP32)
+        return dw.clone(), c.clone()
+
+    def plans():
+        return K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, 1)[0], K.gemm_nt_plan(B=1, M=8, N=24, kseg=1, klen=200000)[0]
+    slab_w, slab_c = Cout * Cin * 9 * 4, 8 * 24 * 4
+    with _mode(gd, True, "unsplit"):
+        u = run()
+    with _mode(gd, True, "ordered"):
+        assert min(plans()) > 2
+        monkeypatch.setattr(K, "DET_WS_BYTES", slab_c + 1)          # below one dW slab, one C slab + 1
+        assert plans() == (1, 1)
+        one = run()
+        monkeypatch.setattr(K, "DET_WS_BYTES", slab_w + 1)          # one dW slab + 1 (many C slabs)
+        assert plans()[0] == 1
+        one_w = run()
+        monkeypatch.setattr(K, "DET_WS_BYTES", 2 * slab_w)
+        assert plans()[0] == 2
+        two_w = run()
+        monkeypatch.setattr(K, "DET_WS_BYTES", 2 * slab_c)
+        assert plans() == (1, 2)
+        two_c = run()
+    assert torch.equal(one[0], u[0]) and torch.equal(one[1], u[1])
+    assert torch.equal(one_w[0], u[0])
+    assert_close(two_w[0], u[0].cpu(), 1e-5, "two dW slabs vs unsplit", rell2)
+    assert torch.equal(two_c[0], u[0])
+    assert_close(two_c[1], u[1].cpu(), 1e-5, "two C slabs vs unsplit", rell2)
+
+
+def test_discriminator1_routes_through_the_pixel_major_trunk(gd, golden_dir, monkeypatch):
+    """ordered mode keeps Discriminator1 (bf16) on the pixel-major trunk, plain deterministic mode still leaves it; two
+    ordered runs give bit-equal parameter gradients that agree with the default-mode run within the bounds of
+    test_discriminator1_bf16_nhwc_trunk_vs_reference_fixture (2e-2 on y, 1e-1 rel-L2 on the gradients)"""
+    from gan_danet_amd import Discriminator1
+    K = _K()
+    fx = load_golden(golden_dir, "disc1_64x64")
+    calls = []
+    orig = K.disc_stem_fwd
+    monkeypatch.setattr(K, "disc_stem_fwd", lambda *a, **kw: (calls.append(1), orig(*a, **kw))[1])
+
+    def run():
+        torch.manual_seed(0)
+        m = Discriminator1().to(DEV)
+        x = fx["x"].to(DEV).requires_grad_(True)
+        with gd.precision("bf16"):
+            with torch.no_grad():
+                m(x)
+            fill_module(m)
+            n0 = len(calls)
+            y = m(x)
+            y.backward(fx["go"].to(DEV))
+        return len(calls) - n0, y.detach().clone(), x.grad.clone(), {k: p.grad.clone() for k, p in m.named_parameters()}
+
+    base = run()
+    assert base[0] == 1, "default mode: the pixel-major trunk did not run"
+    with _mode(gd, True, "unsplit"):
+        assert run()[0] == 0, "plain deterministic mode must stay on the fp32-NCHW chain"
+    with _mode(gd, True, "ordered"):
+        o1, o2 = run(), run()
+    assert o1[0] == 1 and o2[0] == 1, "ordered mode: the pixel-major trunk did not run"
+    assert torch.equal(o1[1], o2[1]) and torch.equal(o1[2], o2[2])
+    for k in o1[3]:
+        assert torch.equal(o1[3][k], o2[3][k]), k
+        assert_close(o1[3][k], base[3][k].cpu(), 1e-1, k, rell2)
+    assert_close(o1[1], base[1].cpu(), 2e-2, "y")
+    assert_close(o1[2], base[2].cpu(), 1e-1, "dx", rell2)
+
+
+def _make(gd, seed=0):
+    torch.manual_seed(seed)
+    G, D = gd.FlexibleUpsamplingModule(input_channels=8).to(DEV), gd.Discriminator1().to(DEV)
+    with torch.no_grad():
+        D(torch.zeros(1, 1, 64, 64, device=DEV))
+    G.apply(gd.weights_init_normal), D.apply(gd.weights_init_normal)
+    return G, D
+
+
+@pytest.mark.parametrize("prec", ["bf16", "mixed"])
+def test_whole_step_is_bit_reproducible(gd, prec):
+    """two runs of two GanTrainer steps from one seed under ordered mode: every parameter of G and D and both optimiser
+    states bit-equal; the first step's losses within 3 x the default mode's own run-to-run spread (floor 1e-6 relative)
+    of a default-mode run.
+
+    The loss bound is a two-sample estimate of the default mode's noise and, in mixed mode, does not always hold
+    (MI355X, 2026-10-17).  Ordered loss_g was 13.9889679 in every run; the default mode gave 13.9889708 / 13.9889011 in one
+    process (spread 7.0e-5, bound 2.1e-4, |ordered - default| 2.9e-6: passes) and 13.9888973 / 13.9889069 in the next (spread
+    9.5e-6, bound 2.9e-5, |ordered - default| 7.1e-5: FAILS).  The ordered value lies inside the range the four default
+    runs span (13.9888973 .. 13.9889708): the default mode's mixed-mode outcomes are multi-modal (a last-bit difference
+    flips a bf16 rounding in the discriminator trunk, see test_gpu_checkpoint.py), and two draws under-estimate that
+    spread when they land in the same mode.  bf16: loss_g identical, loss_d 1.2e-7 apart (bound 6.4e-7).  The bit-equality
+    assertions held in every run."""
+    x, tgt = seeded((2, 8, 16, 16), 171).to(DEV), seeded((2, 1, 64, 64), 172).to(DEV)
+
+    def run():
+        with gd.precision(prec):
+            G, D = _make(gd)
+            tr = gd.GanTrainer(G, D, None)
+            first = tr.step(x, tgt, 0.25)
+            losses = (first.loss_g.double().item(), first.loss_d.double().item())
+            tr.step(x, tgt, 0.5)
+        state = [v.clone() for v in G.state_dict().values()] + [v.clone() for v in D.state_dict().values()]
+        for opt in (tr.opt_g, tr.opt_d):
+            for st in opt.state.values():
+                state += [st[k].clone() for k in ("exp_avg", "exp_avg_sq") if k in st]
+        return losses, state
+
+    d1, d2 = run(), run()
+    with _mode(gd, True, "ordered"):
+        o1, o2 = run(), run()
+    assert len(o1[1]) == len(o2[1]) > 0
+    for i, (a, b) in enumerate(zip(o1[1], o2[1])):
+        assert torch.equal(a, b), f"state tensor {i} differs between two ordered runs"
+    assert o1[0] == o2[0]
+    for name, od, da, db in zip(("loss_g", "loss_d"), o1[0], d1[0], d2[0]):
+        spread = abs(da - db)
+        bound = max(3 * spread, 1e-6 * abs(da))
+        print(f"{prec} {name}: ordered {od:.9g} default {da:.9g} / {db:.9g} spread {spread:.3e} bound {bound:.3e} diff {abs(od - da):.3e}")
+        assert abs(od - da) <= bound, f"{name}: |ordered - default| = {abs(od - da):.3e} > {bound:.3e}"
+
+
+def test_ordered_mode_is_actually_parallel(gd):
+    """the dense-layer weight gradient 136 -> 24 at 256 x 256, B = 4, packed 16-bit operands: unsplit runs 2 workgroups,
+    ordered about 1 000 on 256 CUs -- at least 2x faster (HIP-event medians of 5 interleaved launches after warm-up); 2x is
+    a floor only a broken split path misses"""
+    K = _K()
+    B, Cin, H, W, Cout = 4, 136, 256, 256, 24
+    dy16 = seeded((B, Cout, H * W), 341).to(torch.bfloat16).to(DEV)
+    x16 = seeded((B, H * W, Cin), 342).to(torch.bfloat16).to(DEV)
+
+    def timed():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        K.conv3x3_wgrad_packed(dy16, x16, H, W, 1)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    t = {"unsplit": [], "ordered": []}
+    for it in range(6):                      # the first round is the warm-up
+        for mode in ("unsplit", "ordered"):
+            with _mode(gd, True, mode):
+                if it == 0:
+                    assert (K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, 1)[0] > 1) == (mode == "ordered")
+                ms = timed()
+            if it > 0:
+                t[mode].append(ms)
+    mu, mo = sorted(t["unsplit"])[2], sorted(t["ordered"])[2]
+    print(f"136 -> 24 weight gradient, B = 4: unsplit {mu:.3f} ms, ordered {mo:.3f} ms ({mu / mo:.1f}x)")
+    assert mo * 2 <= mu, f"ordered {mo:.3f} ms is not 2x faster than unsplit {mu:.3f} ms"
