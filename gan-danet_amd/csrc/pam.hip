@@ -777,17 +777,6 @@ __global__ __launch_bounds__(256) void pam_key_sqnorm_max_kernel(const unsigned 
 
 }  // namespace
 
-#define PAM_DISPATCH_CT(CT_, CALL)                         \
-    switch (CT_) {                                         \
-        case 1: { constexpr int CT = 1; CALL; } break;     \
-        case 2: { constexpr int CT = 2; CALL; } break;     \
-        case 3: { constexpr int CT = 3; CALL; } break;     \
-        case 4: { constexpr int CT = 4; CALL; } break;     \
-        case 5: { constexpr int CT = 5; CALL; } break;     \
-        case 6: { constexpr int CT = 6; CALL; } break;     \
-        default: gd_set_error("pam: Cp must be 32..192"); return -1; \
-    }
-
 static int pam_fwd_launch(const void* qt, const void* kt, const void* v, int B, int N, int Npad, int C, int Cp,
                           int v_ones, int f16, const float* gamma, const float* x, long x_bs, float* out,
                           long out_bs, float* o_attn, float* lse, const float* k_sqnorm_max, const float* mshift, int* redo,
@@ -872,13 +861,6 @@ extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int 
     hipLaunchKernelGGL(pam_dq_reduce_kernel, dim3(Npad / 64, nb), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)part, KB, Npad, dqn);
 }
-
-// pam_bwd64.hip
-extern "C" size_t gd_pam_bwd64_scratch_bytes(int Npad, int deterministic);
-extern "C" int gd_pam_bwd64_slice(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
-                                  const float* lse, const float* delta, int nb, int N, int Npad, int Cp, int f16,
-                                  int deterministic, float* dqn, float* dkn, float* dv, long out_bs,
-                                  void* scratch, void* stream);
 
 // Backward forms (gandanet.h GD_PAM_BWD_*):
 //   0 K64_ATOMIC : 4 waves x 64 keys, one wave per SIMD, fp32 atomics for dQ            (default, fastest)

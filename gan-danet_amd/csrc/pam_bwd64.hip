@@ -652,8 +652,6 @@ void launch_k64(dim3 grid, hipStream_t s, const unsigned short* q, const unsigne
 }
 }  // namespace
 
-extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int nb, float* dqn, void* stream);   // pam.hip
-
 // one batch slice through the 64-keys-per-wave backward; scratch holds `images` images' worth
 extern "C" int gd_pam_bwd64_slice(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
                                   const float* lse, const float* delta, int nb, int N, int Npad, int Cp, int f16,

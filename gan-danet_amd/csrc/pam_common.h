@@ -1,4 +1,4 @@
-// Helpers shared by the PAM kernels (pam.hip, pam_bwd64.hip): 16-bit MFMA wrappers for both operand types
+// Helpers shared by the PAM kernels (pam*.hip): 16-bit MFMA wrappers for both operand types
 // (bf16 = the training default, f16 = BASELINE config 5), accumulator-as-operand packing, LDS transpose reads.
 #pragma once
 #include "common.h"
@@ -91,4 +91,40 @@ __device__ __forceinline__ bf16x8_t read_tr_frag_sw(const unsigned short* X, int
 
 constexpr int B_QLD = 40;   // Q tile rows [i][32 d] (80 B): 16-B reads
 
+// ---- host side ----
+// V channel chunks: `tiles` 32-channel tiles split into the fewest chunks of at most 6 tiles (the forward's register
+// ceiling), as even as possible
+struct Chunks {
+    int n, ct[3], c0[3];
+    explicit Chunks(int tiles) {
+        n = (tiles + 5) / 6;
+        int c = 0;
+        for (int i = 0; i < n; ++i) {
+            ct[i] = tiles / n + (i < tiles % n ? 1 : 0);
+            c0[i] = c;
+            c += ct[i] * 32;
+        }
+    }
+};
+
 }  // namespace pam
+
+// runs the statement(s) with `constexpr int CT` = the number of 32-channel tiles of one launch, 1..6
+#define PAM_DISPATCH_CT(CT_, ...)                                \
+    switch (CT_) {                                               \
+        case 1: { constexpr int CT = 1; __VA_ARGS__; } break;    \
+        case 2: { constexpr int CT = 2; __VA_ARGS__; } break;    \
+        case 3: { constexpr int CT = 3; __VA_ARGS__; } break;    \
+        case 4: { constexpr int CT = 4; __VA_ARGS__; } break;    \
+        case 5: { constexpr int CT = 5; __VA_ARGS__; } break;    \
+        case 6: { constexpr int CT = 6; __VA_ARGS__; } break;    \
+        default: gd_set_error("pam: Cp must be 32..192"); return -1; \
+    }
+
+// entry points that one PAM translation unit calls in another
+extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int nb, float* dqn, void* stream);   // pam.hip
+extern "C" size_t gd_pam_bwd64_scratch_bytes(int Npad, int deterministic);                                       // pam_bwd64.hip
+extern "C" int gd_pam_bwd64_slice(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
+                                  const float* lse, const float* delta, int nb, int N, int Npad, int Cp, int f16,
+                                  int deterministic, float* dqn, float* dkn, float* dv, long out_bs,
+                                  void* scratch, void* stream);                                                  // pam_bwd64.hip

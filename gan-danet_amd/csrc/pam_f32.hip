@@ -451,34 +451,10 @@ __global__ __launch_bounds__(256) void pam_f32_dkq_kernel(const float* __restric
     }
 }
 
-// value-channel chunks: the ceil(C / 32) tiles split into the fewest chunks of at most 6 tiles, as even as possible
-struct Chunks {
-    int n, ct[3], c0[3];
-    explicit Chunks(int C) {
-        const int tiles = (C + 31) / 32;
-        n = (tiles + 5) / 6;
-        int c = 0;
-        for (int i = 0; i < n; ++i) {
-            ct[i] = tiles / n + (i < tiles % n ? 1 : 0);
-            c0[i] = c;
-            c += ct[i] * 32;
-        }
-    }
-};
-
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 
-#define PAM_F32_DISPATCH_CHUNK(CT_, ...)                       \
-    switch (CT_) {                                             \
-        case 1: { constexpr int CT = 1; __VA_ARGS__; } break;  \
-        case 2: { constexpr int CT = 2; __VA_ARGS__; } break;  \
-        case 3: { constexpr int CT = 3; __VA_ARGS__; } break;  \
-        case 4: { constexpr int CT = 4; __VA_ARGS__; } break;  \
-        case 5: { constexpr int CT = 5; __VA_ARGS__; } break;  \
-        default: { constexpr int CT = 6; __VA_ARGS__; } break; \
-    }
 #define PAM_F32_DISPATCH_ALL(TILES_, ...)                                    \
     do {                                                                     \
         if ((TILES_) <= 3) { constexpr int CTMAX = 3; __VA_ARGS__; }         \
@@ -503,10 +479,10 @@ extern "C" int gd_pam_f32_fwd(const float* q, long q_bs, const float* k, long k_
     GD_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && q_bs % 4 == 0 && k_bs % 4 == 0 && v_bs % 4 == 0,
                  "gd_pam_f32_fwd: q / k / v must be 16-byte aligned with batch strides that are multiples of 4");
     hipStream_t s = (hipStream_t)stream;
-    const Chunks ch(C);
+    const pam::Chunks ch((C + 31) / 32);
     const dim3 grid(Npad / 128, B), block(256);
     for (int i = 0; i < ch.n; ++i) {
-        PAM_F32_DISPATCH_CHUNK(ch.ct[i], {
+        PAM_DISPATCH_CT(ch.ct[i], {
             hipLaunchKernelGGL((pam_f32_fwd_kernel<CT>), grid, block, 0, s, q, q_bs, k, k_bs, v, v_bs, ch.c0[i], N, Npad, C, r,
                                gamma, x, x_bs, out, out_bs, o_attn, lse);
         });
@@ -525,9 +501,9 @@ extern "C" int gd_pam_f32_bwd(const float* q, long q_bs, const float* k, long k_
                  "gd_pam_f32_bwd: q / k / v / gdo must be 16-byte aligned with batch strides that are multiples of 4");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(Npad / 128, B), block(256);
-    const Chunks ch(C);
+    const pam::Chunks ch((C + 31) / 32);
     for (int i = 0; i < ch.n; ++i) {
-        PAM_F32_DISPATCH_CHUNK(ch.ct[i], {
+        PAM_DISPATCH_CT(ch.ct[i], {
             hipLaunchKernelGGL((pam_f32_dv_kernel<CT>), grid, block, 0, s, q, q_bs, k, k_bs, gdo, gdo_bs, ch.c0[i], lse, N, Npad,
                                C, r, dv);
         });

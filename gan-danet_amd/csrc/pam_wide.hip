@@ -490,21 +490,6 @@ __global__ __launch_bounds__(256, 2) void pam_wide_bwd_dv_kernel(
         for (int e = 0; e < 16; ++e) dv[((long)b * Cp_all + c0 + ct * 32 + acc_row(e, h)) * Npad + j] = dvacc[ct][e];
 }
 
-// V channel chunks: the Cp / 32 tiles split into the fewest chunks of at most 6 tiles, as even as possible
-struct Chunks {
-    int n, ct[3], c0[3];
-    explicit Chunks(int Cp) {
-        const int tiles = Cp / 32;
-        n = (tiles + 5) / 6;
-        int c = 0;
-        for (int i = 0; i < n; ++i) {
-            ct[i] = tiles / n + (i < tiles % n ? 1 : 0);
-            c0[i] = c;
-            c += ct[i] * 32;
-        }
-    }
-};
-
 }  // namespace
 
 #define PAM_WIDE_DISPATCH_D(D_, ...)                            \
@@ -512,13 +497,6 @@ struct Chunks {
         if ((D_) == 32) { constexpr int D = 32; __VA_ARGS__; }  \
         else { constexpr int D = 64; __VA_ARGS__; }             \
     } while (0)
-#define PAM_WIDE_DISPATCH_CHUNK(CT_, ...)                      \
-    switch (CT_) {                                             \
-        case 3: { constexpr int CT = 3; __VA_ARGS__; } break;  \
-        case 4: { constexpr int CT = 4; __VA_ARGS__; } break;  \
-        case 5: { constexpr int CT = 5; __VA_ARGS__; } break;  \
-        default: { constexpr int CT = 6; __VA_ARGS__; } break; \
-    }
 #define PAM_WIDE_DISPATCH_ALL(CT_, ...)                          \
     switch (CT_) {                                               \
         case 7: { constexpr int CT = 7; __VA_ARGS__; } break;    \
@@ -547,14 +525,14 @@ extern "C" int gd_pam_wide_fwd(const void* qt, const void* kt, const void* v, in
     if (pam_wide_check(B, N, Npad, Cp, D)) return -1;
     GD_CHECK_ARG(C > Cp - 32 && C <= Cp, "gd_pam_wide_fwd: Cp must be C rounded up to a multiple of 32");
     hipStream_t s = (hipStream_t)stream;
-    const Chunks ch(Cp);
+    const Chunks ch(Cp / 32);
     const dim3 grid(Npad / 256, B), block(512);
     const unsigned short *q16 = (const unsigned short*)qt, *k16 = (const unsigned short*)kt, *v16 = (const unsigned short*)v;
     const long v_bs = (long)Cp * Npad;
     for (int i = 0; i < ch.n; ++i) {
         // 64-key tiles: at D = 64 and 6 channel tiles the 128-key form leaves no registers for the S tiles
 #define PAM_WIDE_FWD_ARGS q16, k16, v16, v_bs, ch.c0[i], N, Npad, C, gamma, x, x_bs, out, out_bs, o_attn, lse
-        PAM_WIDE_DISPATCH_D(D, PAM_WIDE_DISPATCH_CHUNK(ch.ct[i], {
+        PAM_WIDE_DISPATCH_D(D, PAM_DISPATCH_CT(ch.ct[i], if constexpr (CT >= 3) {
             if (f16) hipLaunchKernelGGL((pam_wide_fwd_kernel<CT, D, 64, true>), grid, block, 0, s, PAM_WIDE_FWD_ARGS);
             else hipLaunchKernelGGL((pam_wide_fwd_kernel<CT, D, 64, false>), grid, block, 0, s, PAM_WIDE_FWD_ARGS);
         }));
@@ -569,8 +547,6 @@ extern "C" size_t gd_pam_wide_scratch_bytes(int Npad, int D, int deterministic) 
     if (!deterministic) return 0;
     return (size_t)(D / 32) * (size_t)(Npad / 128) * (size_t)Npad * 32 * sizeof(unsigned short);
 }
-
-extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int nb, float* dqn, void* stream);   // pam.hip
 
 extern "C" int gd_pam_wide_bwd(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
                                const float* lse, const float* delta, int B, int N, int Npad, int Cp, int D, int f16,
@@ -603,9 +579,9 @@ extern "C" int gd_pam_wide_bwd(const void* qt, const void* kt, const void* kn, c
         }));
         if (deterministic) gd_pam_dq_reduce_launch(part, Npad / 128, Npad, nb * (D / 32), dqn + oD, stream);
     }
-    const Chunks ch(Cp);
+    const Chunks ch(Cp / 32);
     for (int i = 0; i < ch.n; ++i) {
-        PAM_WIDE_DISPATCH_D(D, PAM_WIDE_DISPATCH_CHUNK(ch.ct[i], {
+        PAM_WIDE_DISPATCH_D(D, PAM_DISPATCH_CT(ch.ct[i], if constexpr (CT >= 3) {
             if (f16)
                 hipLaunchKernelGGL((pam_wide_bwd_dv_kernel<CT, D, true>), dim3(Npad / 128, B), dim3(256), 0, s, q, k, dO, Cp,
                                    ch.c0[i], lse, N, Npad, dv);

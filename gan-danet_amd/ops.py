@@ -432,15 +432,9 @@ def _cp(c: int) -> int:
     return (c + 31) // 32 * 32
 
 
-PAM_WIDE_ROUTE = "wide"     # _pam_forward's route tag for the wide kernels (truthy like the narrow route's True)
-
-
 def _pam_wide(Cn: int, r: int) -> bool:
     """16-bit modes, 192 < C <= 511 (r <= 63): the wide flash kernels (gd_pam_wide_*) instead of the product chain"""
     return K.PAM_WIDE and sixteen_bit("pam") and 192 < Cn <= 511 and r <= 63
-
-
-PAM_F32_ROUTE = "f32"      # ... and for the fused kernels on exact fp32 operands (gd_pam_f32_*)
 
 
 def _pam_f32(B: int, Cn: int, r: int, N: int) -> bool:
@@ -463,17 +457,36 @@ def _pad_plane(t: torch.Tensor, N: int, Np: int) -> torch.Tensor:
     return out
 
 
+def _pam_pack16(q, k, v, r, Cn, N, D, ones_row, f16):
+    """the 16-bit operands of the narrow and wide flash kernels from the projections q, k (B, r, N), v (B, C, N): q goes in
+    pre-scaled by log2 e, q / k in D slots with 1.0 in k's last slot (it carries the running maximum), v with ones in
+    row ``ones_row`` (-1: none).  Returns (qt, kt, kn, vn, vt).  (The outputs o_attn and lse are the caller's to allocate,
+    once it has let go of the fp32 projections.)"""
+    Np, Cp = _npad(N), _cp(Cn)
+    _, qt = K.pack_bf16(q, r, N, scale_imm=K.LOG2E, t_shape=(Np, D), f16=f16)
+    kn, kt = K.pack_bf16(k, r, N, plain_shape=(D, Np), t_shape=(Np, D), perm16=True, ones_row=D - 1, f16=f16)
+    vn, vt = K.pack_bf16(v, Cn, N, plain_shape=(Cp, Np), t_shape=(Np, Cp), perm16=True, ones_row=ones_row, f16=f16)
+    return qt, kt, kn, vn, vt
+
+
+def _pam_route(B: int, Cn: int, r: int, N: int) -> str:
+    """"narrow" / "wide": the flash kernels on 16-bit operands; "f32": those on exact fp32 operands; "chain": the
+    product chain with its N x N matrices"""
+    if sixteen_bit("pam") and Cn <= 192 and r <= 31:
+        return "narrow"
+    if _pam_wide(Cn, r):
+        return "wide"
+    return "f32" if _pam_f32(B, Cn, r, N) else "chain"
+
+
 def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
-    """PAM into ``out3`` (B, C, N) view.  Returns (route: True = flash, PAM_WIDE_ROUTE = wide flash, PAM_F32_ROUTE = flash
-    on exact fp32 operands, False = product chain; tensors to keep for backward)."""
+    """PAM into ``out3`` (B, C, N) view.  Returns (route, see _pam_route; tensors to keep for backward)."""
     B, Cn, H, W = x.shape
     N = H * W
     r = wq.shape[0]
     x3 = x.view(B, Cn, N)
-    fused = sixteen_bit("pam") and Cn <= 192 and r <= 31
-    wide = not fused and _pam_wide(Cn, r)
-    f32 = not fused and not wide and _pam_f32(B, Cn, r, N)
-    if (fused or wide or f32) and PAM_CAT and (bq is None) == (bk is None) == (bv is None):
+    route = _pam_route(B, Cn, r, N)
+    if route != "chain" and PAM_CAT and (bq is None) == (bk is None) == (bv is None):
         # q, k, v as ONE 1x1 conv over the concatenated weights: x is read once instead of three times
         wc = torch.empty(2 * r + Cn, Cn, 1, 1, device=x.device, dtype=torch.float32)
         for w_, lo in ((wq, 0), (wk, r), (wv, 2 * r)):
@@ -489,41 +502,29 @@ def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
         q = K.conv2d_fwd(x, wq, bq, 1, 0, prec).view(B, r, N)
         k = K.conv2d_fwd(x, wk, bk, 1, 0, prec).view(B, r, N)
         v = K.conv2d_fwd(x, wv, bv, 1, 0, prec).view(B, Cn, N)
-    if fused:
+    if route in ("narrow", "wide"):
         Np, Cp = _npad(N), _cp(Cn)
-        # q goes in pre-scaled by log2 e; a spare padded channel of V carries ones (softmax denominator by MFMA)
-        ones = Cp - 1 if Cn < Cp else -1
         f16 = _pam_f16()
-        _, qt = K.pack_bf16(q, r, N, scale_imm=K.LOG2E, t_shape=(Np, 32), f16=f16)
-        kn, kt = K.pack_bf16(k, r, N, plain_shape=(32, Np), t_shape=(Np, 32), perm16=True, ones_row=31, f16=f16)
-        vn, vt = K.pack_bf16(v, Cn, N, plain_shape=(Cp, Np), t_shape=(Np, Cp), perm16=True, ones_row=ones, f16=f16)
+        # narrow: a spare padded channel of V carries ones (softmax denominator by MFMA).  wide: q / k in 32 or 64 slots
+        # and no ones row: the kernels split V into channel chunks of <= 192 and sum each chunk's denominator on the VALU
+        D = 32 if route == "narrow" else K.pam_wide_slots(r)
+        ones = Cp - 1 if route == "narrow" and Cn < Cp else -1
+        qt, kt, kn, vn, vt = _pam_pack16(q, k, v, r, Cn, N, D, ones, f16)
         del q, k, v
         y3 = None
         o_attn = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
         lse = torch.empty(B, N, device=x.device, dtype=torch.float32)
-        if K.PAM_SHIFT and not f16:
+        if route == "wide":
+            K.pam_wide_fwd(qt, kt, vn, B, N, Np, Cn, Cp, D, gamma_p, x3, out3, o_attn, lse, r_alg=r, f16=f16)
+        elif K.PAM_SHIFT and not f16:
             # bf16 operands: per-query softmax shift from a strided key sample, max-free sweep for logits of any magnitude
             K.pam_flash_fwd_shift(qt, kt, vn, B, N, Np, Cn, Cp, gamma_p, x3, out3, o_attn, lse, r_alg=r, v_ones=ones >= 0)
         else:
             k_sqmax = K.pam_key_sqnorm_max(kt, N, f16) if K.PAM_NOMAX else None
             K.pam_flash_fwd(qt, kt, vn, B, N, Np, Cn, Cp, gamma_p, x3, out3, o_attn, lse, r_alg=r, v_ones=ones >= 0, f16=f16,
                             k_sqmax=k_sqmax)
-        return True, (qt, kt, kn, vt, o_attn, lse)
-    if wide:
-        # q / k in D = 32 or 64 slots (k's last slot = 1.0 carries the running maximum), V without a ones row: the
-        # kernels split it into channel chunks of <= 192 and sum each chunk's softmax denominator on the VALU
-        Np, Cp, D = _npad(N), _cp(Cn), K.pam_wide_slots(r)
-        f16 = _pam_f16()
-        _, qt = K.pack_bf16(q, r, N, scale_imm=K.LOG2E, t_shape=(Np, D), f16=f16)
-        kn, kt = K.pack_bf16(k, r, N, plain_shape=(D, Np), t_shape=(Np, D), perm16=True, ones_row=D - 1, f16=f16)
-        vn, vt = K.pack_bf16(v, Cn, N, plain_shape=(Cp, Np), t_shape=(Np, Cp), perm16=True, f16=f16)
-        del q, k, v
-        y3 = None
-        o_attn = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
-        lse = torch.empty(B, N, device=x.device, dtype=torch.float32)
-        K.pam_wide_fwd(qt, kt, vn, B, N, Np, Cn, Cp, D, gamma_p, x3, out3, o_attn, lse, r_alg=r, f16=f16)
-        return PAM_WIDE_ROUTE, (qt, kt, kn, vt, o_attn, lse)
-    if f32:
+        return route, (qt, kt, kn, vt, o_attn, lse)
+    if route == "f32":
         # the projections' own fp32 planes are the MFMA operands (channel-major = one channel pair per k-step); only a
         # ragged N costs a zero-padded copy
         Np = _npad(N)
@@ -531,9 +532,9 @@ def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
         o_attn = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
         lse = torch.empty(B, N, device=x.device, dtype=torch.float32)
         K.pam_f32_fwd(q, k, v, B, N, Np, Cn, r, gamma_p, x3, out3, o_attn, lse)
-        return PAM_F32_ROUTE, (q, k, v, o_attn, lse)
+        return route, (q, k, v, o_attn, lse)
     prec = prec if sixteen_bit("pam") else L.PREC_FP32
-    return False, _pam_chain_fwd(q, k, v, x3, gamma_p, out3, prec)
+    return route, _pam_chain_fwd(q, k, v, x3, gamma_p, out3, prec)
 
 
 def _pam_chain_fwd(q, k, v, x3, gamma_p, out3, prec):
@@ -584,13 +585,13 @@ def _pam_chain_bwd(pam_saved, gamma_p, d_pam, pprec):
     return K.transpose(dqt), K.transpose(dkt), dv, dgamma_p               # dq, dk: (B, r, N)
 
 
-def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has_bias):
+def _pam_backward(route, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has_bias):
     """d_pam: (B, C, N) view of dOut.  Accumulates the projection data-gradients into ``dx`` (B, C, N; the
     residual term is added by the caller).  Returns (dwq, dbq, dwk, dbk, dwv, dbv, dgamma)."""
     B, Cn, H, W = x.shape
     N = H * W
     r = wq.shape[0]
-    if fused == PAM_F32_ROUTE:
+    if route == "f32":
         q, k, v, o_attn, lse = pam_saved
         Np = q.shape[2]
         d_raw, delta = K.chan_dot(d_pam, o_attn, gamma_p)
@@ -605,7 +606,7 @@ def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
         dk = torch.empty(B, r, N, device=x.device, dtype=torch.float32)
         dv = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
         K.pam_f32_bwd(q, k, v, gdo, lse, delta, B, N, Np, Cn, r, dq, dk, dv)
-    elif fused:
+    elif route in ("narrow", "wide"):
         qt, kt, kn, vt, o_attn, lse = pam_saved
         Np, Cp = _npad(N), _cp(Cn)
         d_raw, delta = K.chan_dot(d_pam, o_attn, gamma_p)
@@ -618,7 +619,7 @@ def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
             scales = K.pam_f16_scale(d_pam, gamma_p, delta)
             s_up, s_inv = scales[0:1], scales[1:2]
         _, dot_ = K.pack_bf16(d_pam, Cn, N, scale=s_up, t_shape=(Np, Cp), f16=f16)
-        if fused == PAM_WIDE_ROUTE:
+        if route == "wide":
             D = qt.shape[2]
             dqn = torch.empty(B, D, Np, device=x.device, dtype=torch.float32)
             dkn = torch.empty(B, D, Np, device=x.device, dtype=torch.float32)
@@ -659,7 +660,7 @@ def _pam_backward(fused, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
         dq, dk, dv, dgamma_p = _pam_chain_bwd(pam_saved, gamma_p, d_pam, pprec)
     grads = []
     # the exact-fp32 fused route is reproducible end to end: its weight-gradient GEMMs run unsplit (no atomic combine)
-    splits = 1 if fused == PAM_F32_ROUTE else 0
+    splits = 1 if route == "f32" else 0
     for dy3, w, hb in ((dq, wq, has_bias[0]), (dk, wk, has_bias[1]), (dv, wv, has_bias[2])):
         dy4 = dy3.view(B, dy3.shape[1], H, W)
         grads.append(K.conv2d_wgrad(dy4, x, 1, 1, 0, prec, splits=splits))
@@ -713,20 +714,20 @@ class PamFn(Function):
         x = _c(x)
         prec = _prec("conv1x1")
         out = torch.empty_like(x)
-        fused, saved = _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, _as3(out), prec)
+        route, saved = _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, _as3(out), prec)
         ctx.save_for_backward(x, wq, wk, wv, gamma_p, *saved)
-        ctx.cfg = (prec, fused, (bq is not None, bk is not None, bv is not None))
+        ctx.cfg = (prec, route, (bq is not None, bk is not None, bv is not None))
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, wq, wk, wv, gamma_p, *saved = ctx.saved_tensors
-        prec, fused, has_bias = ctx.cfg
+        prec, route, has_bias = ctx.cfg
         B, Cn, H, W = x.shape
         d3 = _as3(_c(dout))
         dx = torch.empty(B, Cn, H * W, device=x.device, dtype=torch.float32)
         K.copy_slab(d3, dx)
-        dwq, dbq, dwk, dbk, dwv, dbv, dg = _pam_backward(fused, saved, x, wq, wk, wv, gamma_p, d3, dx, prec, has_bias)
+        dwq, dbq, dwk, dbk, dwv, dbv, dg = _pam_backward(route, saved, x, wq, wk, wv, gamma_p, d3, dx, prec, has_bias)
         return dx.view(B, Cn, H, W), dwq, dbq, dwk, dbk, dwv, dbv, dg
 
 
@@ -763,16 +764,16 @@ class DualAttentionFn(Function):
         B, Cn, H, W = x.shape
         prec, cprec = _prec("conv1x1"), _prec("cam_apply")
         feats = torch.empty(B, 2 * Cn, H, W, device=x.device, dtype=torch.float32)
-        fused, saved = _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, _as3(feats[:, :Cn]), prec)
+        route, saved = _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, _as3(feats[:, :Cn]), prec)
         att = _cam_forward(x, gamma_c, _as3(feats[:, Cn:]), cprec)
         ctx.save_for_backward(x, wq, wk, wv, gamma_p, gamma_c, att, *saved)
-        ctx.cfg = (prec, fused, (bq is not None, bk is not None, bv is not None), cprec)
+        ctx.cfg = (prec, route, (bq is not None, bk is not None, bv is not None), cprec)
         return feats
 
     @staticmethod
     def backward(ctx, dfeat):
         x, wq, wk, wv, gamma_p, gamma_c, att, *saved = ctx.saved_tensors
-        prec, fused, has_bias, cprec = ctx.cfg
+        prec, route, has_bias, cprec = ctx.cfg
         B, Cn, H, W = x.shape
         dfeat = _c(dfeat)
         d_pam, d_cam = _as3(dfeat[:, :Cn]), _as3(dfeat[:, Cn:])
@@ -780,7 +781,7 @@ class DualAttentionFn(Function):
         K.copy_slab(d_pam, dx)                     # residual path of PAM
         K.copy_slab(d_cam, dx, accumulate=True)    # residual path of CAM
         dgc = _cam_backward(att, x, gamma_c, d_cam, dx, cprec)
-        dwq, dbq, dwk, dbk, dwv, dbv, dgp = _pam_backward(fused, saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has_bias)
+        dwq, dbq, dwk, dbk, dwv, dbv, dgp = _pam_backward(route, saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has_bias)
         return dx.view(B, Cn, H, W), dwq, dbq, dwk, dbk, dwv, dbv, dgp, dgc
 
 

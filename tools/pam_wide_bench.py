@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import gan_danet_amd as gd  # noqa: E402
-from gan_danet_amd import kern as K  # noqa: E402
+from gan_danet_amd import kern as K, ops  # noqa: E402
 
 PEAK = 2.5e15
 
@@ -57,9 +57,7 @@ def problem(B, C, N, f16):
     wide = C > 192
     D = K.pam_wide_slots(r) if wide else 32
     ones = -1 if wide or C == Cp else Cp - 1
-    _, qt = K.pack_bf16(q, r, N, scale_imm=K.LOG2E, t_shape=(Np, D), f16=f16)
-    kn, kt = K.pack_bf16(k, r, N, plain_shape=(D, Np), t_shape=(Np, D), perm16=True, ones_row=D - 1, f16=f16)
-    vn, vt = K.pack_bf16(v, C, N, plain_shape=(Cp, Np), t_shape=(Np, Cp), perm16=True, ones_row=ones, f16=f16)
+    qt, kt, kn, vn, vt = ops._pam_pack16(q, k, v, r, C, N, D, ones, f16)
     _, dot_ = K.pack_bf16(do, C, N, t_shape=(Np, Cp), f16=f16)
     gamma = torch.tensor([0.7], device=dev)
     out, o_attn = torch.empty_like(x), torch.empty_like(x)
