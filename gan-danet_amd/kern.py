@@ -1044,18 +1044,6 @@ def conv3x3_nhwc_f32out(x16: Tensor, wpack: Tensor, bias: Optional[Tensor], M: i
     return out
 
 
-def conv3x3_wgrad_packed(dy16: Tensor, x16: Tensor, H: int, W: int, stride: int = 1) -> Tensor:
-    """weight gradient from the two 16-bit copies: dy16 (B, Cout, Ho*Wo) channel-major, x16 (B, H*W, Cin) pixel-major"""
-    _bf(dy16, "dy16"), _bf(x16, "x16")
-    B, Cout = dy16.shape[0], dy16.shape[1]
-    Cin = x16.shape[2]
-    dw = torch.empty(Cout, Cin, 3, 3, device=dy16.device, dtype=torch.float32)
-    with _ConvBracket("wgrad_packed", 3, stride, Cin, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1, B):
-        L.check(lib().gd_conv3x3_wgrad_ws(None, 0, _ptr(dy16), None, 0, _ptr(x16), Cin, None, None, 0, B, Cout, Cin, H, W, stride,
-                                       0, _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
-    return dw
-
-
 # ---- split-bf16 ("x3") operands: set_precision("mixed") -------------------------------------------------------------
 HLH, HL, H_ONLY = 0b010, 0b10, 0b0      # copy patterns of pack_split: bit j set = copy j holds the lo part
 
@@ -1096,19 +1084,38 @@ def split3_weights(w: Tensor, axis: int) -> Tensor:
     return out
 
 
-def conv3x3_wgrad_x3(dy2: Tensor, x3: Tensor, H: int, W: int) -> Tensor:
-    """weight gradient from split operands: dy2 (2, B, Cout, N) [hi, lo] channel-major, x3 (B, N, 3 Cin) [hi | lo | hi]
-    pixel-major (the forward's own pack): dW = dy_hi (x) x_hi + dy_lo (x) x_hi + dy_hi (x) x_lo, three launches adding
-    into one dW"""
-    _bf(dy2, "dy2"), _bf(x3, "x3")
-    _, B, Cout, _ = dy2.shape
-    Cin = x3.shape[2] // 3
-    dw = torch.empty(Cout, Cin, 3, 3, device=dy2.device, dtype=torch.float32)
-    with _ConvBracket("wgrad_x3", 3, 1, Cin, Cout, H, W, B):
-        for j, (dpart, xoff) in enumerate(((0, 0), (1, 0), (0, Cin))):
-            L.check(lib().gd_conv3x3_wgrad_ws(None, 0, dy2[dpart].data_ptr(), None, 0, x3.data_ptr() + 2 * xoff, 3 * Cin, None, None,
-                                           0, B, Cout, Cin, H, W, 1, int(j > 0), _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
+# the split weight gradient dW = dy_hi (x) x_hi + dy_lo (x) x_hi + dy_hi (x) x_lo, one launch per row:
+# (part of dy16 [hi, lo], column block of x16 [hi | lo | hi], accumulate); the plain one is the first row alone
+_WGRAD16_SPLIT = ((0, 0, 0), (1, 0, 1), (0, 1, 1))
+
+
+def conv3x3_wgrad16(dy16: Tensor, x16: Tensor, H: int, W: int, stride: int = 1, split: bool = False,
+                    tag: str = "wgrad_packed") -> Tensor:
+    """weight gradient of a 3x3 / pad 1 conv from 16-bit copies of both operands (one launch):
+    dy16 (B, Cout, Ho*Wo) channel-major, x16 (B, H*W, Cin) pixel-major (the forward's own pack).
+    split: dy16 (2, B, Cout, Ho*Wo) [hi, lo], x16 (B, H*W, 3 Cin) [hi | lo | hi]; three launches adding into one dW"""
+    _bf(dy16, "dy16"), _bf(x16, "x16")
+    parts = dy16 if split else dy16[None]
+    _, B, Cout, _ = parts.shape
+    x_ld = x16.shape[2]
+    Cin = x_ld // 3 if split else x_ld
+    dw = torch.empty(Cout, Cin, 3, 3, device=dy16.device, dtype=torch.float32)
+    with _ConvBracket(tag, 3, stride, Cin, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1, B):
+        for part, xblk, acc in _WGRAD16_SPLIT if split else _WGRAD16_SPLIT[:1]:
+            L.check(lib().gd_conv3x3_wgrad_ws(None, 0, parts[part].data_ptr(), None, 0, x16.data_ptr() + 2 * xblk * Cin, x_ld,
+                                              None, None, 0, B, Cout, Cin, H, W, stride, acc, _ptr(dw), _stream(), *det_ws()),
+                    "gd_conv3x3_wgrad")
     return dw
+
+
+_CONV3X3_ROLES = {"fwd": (1, 0), "dgrad": (0, 1), "dgrad_s2": (0, 2)}     # role -> (split3_weights axis, transposed)
+
+
+def conv3x3_operator(w: Tensor, role: str, split: bool = False) -> Tensor:
+    """the packed operator of w (Cout, Cin, 3, 3) for the pixel-major kernels: "fwd" the forward, "dgrad" / "dgrad_s2" the
+    stride-1 / stride-2 data gradient; split: of the weights split [hi ; hi ; lo] along that role's contraction axis"""
+    axis, transposed = _CONV3X3_ROLES[role]
+    return conv3x3_nhwc_pack(split3_weights(w, axis) if split else w, transposed)
 
 
 # ---- Discriminator1 on pixel-major bf16 (discriminator.py:57-77) ------------------------------------------------------
@@ -1223,25 +1230,12 @@ def nhwc_to_nchw16(g: Tensor, want_sum: bool, split: bool = False):
 def conv3x3_wgrad_nhwc(g: Tensor, x: Tensor, stride: int, want_bias: bool, split: bool = False):
     """Weight (and bias) gradient of a 3x3 / pad 1 conv whose input x (B, H, W, Cin) and output gradient g
     (B, Ho, Wo, Cout) are pixel-major bf16: g goes channel-major once (fused with the bias sums), x is staged as is.
-    split: both carry [hi | lo | hi]; dW = g_hi (x) x_hi + g_lo (x) x_hi + g_hi (x) x_lo in three accumulating launches."""
+    split: both carry [hi | lo | hi] (conv3x3_wgrad16)"""
     _bf(g, "nhwc gradient"), _bf(x, "nhwc input")
-    B, H, W, Cin = x.shape
-    Cout = g.shape[3]
+    B, H, W, Kc = x.shape
     gt, db = nhwc_to_nchw16(g, want_bias, split)
-    if split:
-        Cin //= 3
-        Cout //= 3
-        dw = torch.empty(Cout, Cin, 3, 3, device=g.device, dtype=torch.float32)
-        with _ConvBracket("wgrad_nhwc_x3", 3, stride, Cin, Cout, g.shape[1], g.shape[2], B):
-            for j, (dpart, xoff) in enumerate(((0, 0), (1, 0), (0, Cin))):
-                L.check(lib().gd_conv3x3_wgrad_ws(None, 0, gt[dpart].data_ptr(), None, 0, x.data_ptr() + 2 * xoff, 3 * Cin, None, None,
-                                               0, B, Cout, Cin, H, W, stride, int(j > 0), _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
-        return dw, db
-    dw = torch.empty(Cout, Cin, 3, 3, device=g.device, dtype=torch.float32)
-    with _ConvBracket("wgrad_nhwc", 3, stride, Cin, Cout, g.shape[1], g.shape[2], B):
-        L.check(lib().gd_conv3x3_wgrad_ws(None, 0, _ptr(gt), None, 0, _ptr(x), Cin, None, None, 0, B, Cout, Cin, H, W, stride,
-                                       0, _ptr(dw), _stream(), *det_ws()), "gd_conv3x3_wgrad")
-    return dw, db
+    return conv3x3_wgrad16(gt.flatten(-2), x.view(B, H * W, Kc), H, W, stride, split,
+                           "wgrad_nhwc_x3" if split else "wgrad_nhwc"), db
 
 
 def nhwc_stem_fwd(img: Tensor, w: Tensor, bias: Optional[Tensor], relu: bool, split: bool = False) -> Tensor:

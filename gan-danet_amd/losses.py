@@ -106,7 +106,6 @@ class PerceptualLoss(nn.Module):
         cached = getattr(self, "_nhwc_cache", None)
         if cached is not None and cached[0] == version:
             return cached[1]
-        sw = (lambda w, axis: K.split3_weights(w.contiguous(), axis)) if split else (lambda w, axis: w)
         plan = None
         n = len(self.vgg)
         ok = n >= 2 and isinstance(self.vgg[0], Conv2d) and self.vgg[0].weight.shape[1] == 3 and n - 1 in self.feature_layers
@@ -119,13 +118,13 @@ class PerceptualLoss(nn.Module):
                     ok = False
                     break
                 k = len(pairs)
-                w = m.weight.detach()
+                w = m.weight.detach().contiguous()
                 if k == 0:
                     ops_.append(("stem", k, m.bias.detach()))
                     pairs.append([k, False, None, 3])
                 else:
-                    ops_.append(("conv", k, m.bias.detach(), K.conv3x3_nhwc_pack(sw(w, 1), False), w.shape[0]))
-                    pairs.append([k, False, K.conv3x3_nhwc_pack(sw(w, 0), True), w.shape[1]])
+                    ops_.append(("conv", k, m.bias.detach(), K.conv3x3_operator(w, "fwd", split), w.shape[0]))
+                    pairs.append([k, False, K.conv3x3_operator(w, "dgrad", split), w.shape[1]])
                 if i + 1 in self.feature_layers:
                     taps.add(k)
                 i += 2

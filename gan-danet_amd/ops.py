@@ -87,8 +87,8 @@ class Disc1TrunkFn(Function):
         ws, bs = (w1, w2, w3, w4), (b1, b2, b3, b4)
         acts = [K.disc_stem_fwd(x, _c(w1), b1, Disc1TrunkFn.SLOPE, split=sp)]
         for w, b in zip(ws[1:], bs[1:]):
-            wp = K.conv3x3_nhwc_pack(K.split3_weights(_c(w), 1) if sp else _c(w), 0)
-            acts.append(K.conv3x3_nhwc_s2(acts[-1], wp, b, w.shape[0], 2, Disc1TrunkFn.SLOPE, split=sp))
+            acts.append(K.conv3x3_nhwc_s2(acts[-1], K.conv3x3_operator(_c(w), "fwd", sp), b, w.shape[0], 2, Disc1TrunkFn.SLOPE,
+                                          split=sp))
         ctx.save_for_backward(x, *ws, *acts)       # autograd's version check guards x / the weights against in-place edits
         ctx.has_bias = tuple(b is not None for b in bs)
         ctx.split = sp
@@ -106,8 +106,8 @@ class Disc1TrunkFn(Function):
             if need[1 + 2 * l] or need[2 + 2 * l]:
                 dw, db = K.conv3x3_wgrad_nhwc(g, acts[l - 1], 2, ctx.has_bias[l] and need[2 + 2 * l], split=sp)
                 grads[1 + 2 * l], grads[2 + 2 * l] = (dw if need[1 + 2 * l] else None), db
-            wp = K.conv3x3_nhwc_pack(K.split3_weights(_c(ws[l]), 0) if sp else _c(ws[l]), 2)
-            g = K.conv3x3_nhwc_s2_dgrad(g, wp, acts[l - 1], Disc1TrunkFn.SLOPE, split=sp)
+            g = K.conv3x3_nhwc_s2_dgrad(g, K.conv3x3_operator(_c(ws[l]), "dgrad_s2", sp), acts[l - 1], Disc1TrunkFn.SLOPE,
+                                        split=sp)
         if need[1] or need[2]:
             dw, db = K.disc_stem_wgrad(g, x, ctx.has_bias[0] and need[2], split=sp)
             grads[1], grads[2] = (dw if need[1] else None), db
@@ -133,79 +133,87 @@ def _wide3x3(x, w, stride, pad, act, prec) -> bool:
             and w.shape[0] % 8 == 0 and (x.shape[2] * x.shape[3]) % 8 == 0)
 
 
+# The packed 3x3 / stride 1 / pad 1 route: the fp32 NCHW activation is packed ONCE into a pixel-major 16-bit copy that feeds
+# the forward (NHWC kernel, fp32 NCHW epilogue) and the weight gradient; the data gradient is the same kernel on a
+# pixel-major pack of dY against the transposed operator.  split: the same on [hi | lo | hi] packs (operand mode "x3").
+def _pack3x3_x(x, split, scale=None, shift=None, relu=False):
+    """x (B, C, H, W), possibly a slab slice -> its pixel-major 16-bit copy, of max(0, scale x + shift) when given"""
+    if split:
+        return K.pack_split(x, scale=scale, shift=shift, relu=relu)[1]
+    if scale is not None:
+        return K.pack_nhwc16_affine(x, scale, shift, relu)
+    B, Cin, H, W = x.shape
+    return K.pack_bf16(x, Cin, H * W, t_shape=(H * W, Cin))[1]
+
+
+def _packed3x3_fwd(x16, w, bias, H, W, split, relu=False, out=None):
+    return K.conv3x3_nhwc_f32out(x16, K.conv3x3_operator(_c(w), "fwd", split), bias, w.shape[0], H, W, relu=relu, out=out)
+
+
+def _packed3x3_bwd(dy, x16, w, H, W, split, need_dx, need_dw, mask=None, dw_first=False):
+    """(dx, dw) from dY (B, Cout, H, W), possibly a slab slice, packed once in exactly the layouts needed: channel-major
+    for the weight gradient, pixel-major for the data gradient.  mask (split only): a ReLU output whose backward rides in
+    the pack.  dw_first: launch order only -- the dense block takes dx last, straight into its BatchNorm backward"""
+    if not (need_dx or need_dw):
+        return None, None
+    Cout, N = dy.shape[1], H * W
+    if split:
+        dyp, dyt = K.pack_split(_as3(dy), want_plain=need_dw, want_tr=need_dx, mask=None if mask is None else _as3(mask))
+    else:
+        dyp, dyt = K.pack_bf16(_as3(dy), Cout, N, plain_shape=(Cout, N) if need_dw else None,
+                               t_shape=(N, Cout) if need_dx else None)
+
+    def wgrad():
+        return K.conv3x3_wgrad16(dyp, x16, H, W, split=split, tag="wgrad_x3" if split else "wgrad_packed")
+
+    dx = dw = None
+    if need_dw and dw_first:
+        dw = wgrad()
+    if need_dx:
+        dx = K.conv3x3_nhwc_f32out(dyt, K.conv3x3_operator(_c(w), "dgrad", split), None, w.shape[1], H, W)
+    if need_dw and not dw_first:
+        dw = wgrad()
+    return dx, dw
+
+
 class Conv2dFn(Function):
     @staticmethod
     def forward(ctx, x, w, bias, stride: int, pad: int, act: int, prec=None, layer: str = "other"):
-        x3 = prec is None and _x3(layer) and _x3_eligible(x, w, stride, pad, act)
+        split = prec is None and _x3(layer) and _x3_eligible(x, w, stride, pad, act)
         prec = _prec(layer) if prec is None else prec
-        if x3:
-            # split-bf16: x -> [hi | lo | hi] pixel-major (3 Cin channels) against the weights [hi ; hi ; lo]; the same
-            # pack serves the weight gradient
-            B, Cin, H, W = x.shape
-            _, x16 = K.pack_split(x)
-            y = K.conv3x3_nhwc_f32out(x16, K.conv3x3_nhwc_pack(K.split3_weights(_c(w), 1), 0), bias, w.shape[0], H, W,
-                                      relu=act == ACT_RELU)
-            ctx.save_for_backward(x16, w, y if act != ACT_NONE else None)
-            ctx.cfg = (stride, pad, act, prec, bias is not None)
-            ctx.wide = (H, W, True)
-            return y
-        if _wide3x3(x, w, stride, pad, act, prec):
-            # one pixel-major bf16 copy of x serves the forward (16-byte patch staging, no gather / convert in the
-            # kernel) and the weight gradient; only that copy is kept for the backward
-            B, Cin, H, W = x.shape
-            _, x16 = K.pack_bf16(x, Cin, H * W, t_shape=(H * W, Cin))
-            y = K.conv3x3_nhwc_f32out(x16, K.conv3x3_nhwc_pack(_c(w), 0), bias, w.shape[0], H, W, relu=act == ACT_RELU)
-            ctx.save_for_backward(x16, w, y if act != ACT_NONE else None)
-            ctx.cfg = (stride, pad, act, prec, bias is not None)
-            ctx.wide = (H, W, False)
-            return y
-        y = K.conv2d_fwd(x, w, bias, stride, pad, prec, act=act)
+        if split or _wide3x3(x, w, stride, pad, act, prec):
+            # only the 16-bit copy of x is kept for the backward
+            H, W = x.shape[2:]
+            x = _pack3x3_x(x, split)
+            y = _packed3x3_fwd(x, w, bias, H, W, split, relu=act == ACT_RELU)
+            ctx.packed = (H, W, split)
+        else:
+            y = K.conv2d_fwd(x, w, bias, stride, pad, prec, act=act)
+            ctx.packed = None
         ctx.save_for_backward(x, w, y if act != ACT_NONE else None)
         ctx.cfg = (stride, pad, act, prec, bias is not None)
-        ctx.wide = None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
         stride, pad, act, prec, has_bias = ctx.cfg
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        need_db = has_bias and ctx.needs_input_grad[2]
         dy = _c(dy)
         # split route with frozen weights (the VGG stack of PerceptualLoss): the ReLU backward rides in the pack of dY
-        fuse_mask = (ctx.wide is not None and ctx.wide[2] and act == ACT_RELU and not ctx.needs_input_grad[1]
-                     and not (has_bias and ctx.needs_input_grad[2]))
+        fuse_mask = ctx.packed is not None and ctx.packed[2] and act == ACT_RELU and not need_dw and not need_db
         if act != ACT_NONE and not fuse_mask:
             dy = K.act_bwd(y, dy, act)
-        dx = dw = db = None
-        if ctx.wide is not None and ctx.wide[2]:
-            H, W, _ = ctx.wide
-            B, Cout = dy.shape[0], dy.shape[1]
-            dy2, dyt = K.pack_split(dy.view(B, Cout, H * W), want_plain=ctx.needs_input_grad[1], want_tr=ctx.needs_input_grad[0],
-                                    mask=y.view(B, Cout, H * W) if fuse_mask else None)
-            if ctx.needs_input_grad[0]:
-                dx = K.conv3x3_nhwc_f32out(dyt, K.conv3x3_nhwc_pack(K.split3_weights(_c(w), 0), 1), None, w.shape[1], H, W)
-            if ctx.needs_input_grad[1]:
-                dw = K.conv3x3_wgrad_x3(dy2, x, H, W)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = K.channel_sum(dy)
-            return dx, dw, db, None, None, None, None, None
-        if ctx.wide is not None:
-            H, W, _ = ctx.wide
-            B, Cout = dy.shape[0], dy.shape[1]
-            # dY once in both 16-bit layouts: channel-major for the weight gradient, pixel-major for the data gradient
-            dy16, dyt16 = K.pack_bf16(dy.view(B, Cout, H * W), Cout, H * W, plain_shape=(Cout, H * W), t_shape=(H * W, Cout))
-            if ctx.needs_input_grad[0]:
-                dx = K.conv3x3_nhwc_f32out(dyt16, K.conv3x3_nhwc_pack(_c(w), 1), None, w.shape[1], H, W)
-            if ctx.needs_input_grad[1]:
-                dw = K.conv3x3_wgrad_packed(dy16, x, H, W)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = K.channel_sum(dy)
-            return dx, dw, db, None, None, None, None, None
-        if ctx.needs_input_grad[0]:
-            dx = K.conv2d_dgrad(dy, w, (x.shape[2], x.shape[3]), stride, pad, prec)
-        if ctx.needs_input_grad[1]:
-            dw = K.conv2d_wgrad(dy, x, w.shape[2], stride, pad, prec)
-        if has_bias and ctx.needs_input_grad[2]:
-            db = K.channel_sum(dy)
+        dx = dw = None
+        if ctx.packed is not None:
+            dx, dw = _packed3x3_bwd(dy, x, w, *ctx.packed, need_dx, need_dw, mask=y if fuse_mask else None)
+        else:
+            if need_dx:
+                dx = K.conv2d_dgrad(dy, w, (x.shape[2], x.shape[3]), stride, pad, prec)
+            if need_dw:
+                dw = K.conv2d_wgrad(dy, x, w.shape[2], stride, pad, prec)
+        db = K.channel_sum(dy) if need_db else None
         return dx, dw, db, None, None, None, None, None
 
 
@@ -360,36 +368,30 @@ class DenseBlockFn(Function):
         # instead of gathering / normalising the fp32 NCHW slab in their staging loops
         aligned = ((H * W) % 8 == 0 and g % 8 == 0 and all((C0 + l * g) % 8 == 0 for l in range(nl))
                    and tuple(params[4].shape[2:]) == (3, 3))
-        nhwc = DENSE_NHWC and prec == L.PREC_BF16 and aligned
         # "mixed": the same route on split-bf16 operands -- max(0, bn(x)) packed once as [hi | lo | hi] pixel-major
-        x3 = prec == L.PREC_X3 and aligned and C0 >= 32 and H * W * 3 * (C0 + nl * g) < (1 << 31)
+        split = prec == L.PREC_X3 and aligned and C0 >= 32 and H * W * 3 * (C0 + nl * g) < (1 << 31)
+        packed = split or (DENSE_NHWC and prec == L.PREC_BF16 and aligned)
         packs: List[torch.Tensor] = []
         for l in range(nl):
             bw, bb, rm, rv, cw, cb = params[6 * l: 6 * l + 6]
             cl = C0 + l * g
             xin = slab[:, :cl]
             scale, shift, mean, invstd = _bn_prepare(xin, bw, bb, rm, rv, training, momentum, eps)
-            if x3:
-                _, x16 = K.pack_split(xin, scale=scale, shift=shift, relu=True)
-                K.conv3x3_nhwc_f32out(x16, K.conv3x3_nhwc_pack(K.split3_weights(_c(cw), 1), 0), cb, g, H, W,
-                                      out=slab[:, cl:cl + g])
-                packs.append(x16)
-            elif nhwc:
-                x16 = K.pack_nhwc16_affine(xin, scale, shift, True)
-                K.conv3x3_nhwc_f32out(x16, K.conv3x3_nhwc_pack(_c(cw), 0), cb, g, H, W, out=slab[:, cl:cl + g])
-                packs.append(x16)
+            if packed:
+                packs.append(_pack3x3_x(xin, split, scale, shift, relu=True))
+                _packed3x3_fwd(packs[-1], cw, cb, H, W, split, out=slab[:, cl:cl + g])
             else:
                 K.conv2d_fwd(xin, cw, cb, 1, 1, prec, in_scale=scale, in_shift=shift, in_relu=True,
                              out=slab[:, cl:cl + g])
             saved += [scale, shift, mean, invstd, cw]
         ctx.save_for_backward(slab, *saved, *packs)
-        ctx.cfg = (nl, C0, g, training, prec, [p is not None for p in params[5::6]], nhwc, x3, training and _sync_bn_active())
+        ctx.cfg = (nl, C0, g, training, prec, [p is not None for p in params[5::6]], packed, split, training and _sync_bn_active())
         return slab
 
     @staticmethod
     def backward(ctx, dslab_in):
         slab, *saved = ctx.saved_tensors
-        nl, C0, g, training, prec, has_bias, nhwc, x3, sync = ctx.cfg
+        nl, C0, g, training, prec, has_bias, packed, split, sync = ctx.cfg
         packs = saved[5 * nl:]
         B, _, H, W = slab.shape
         dslab = torch.empty(slab.shape, device=slab.device, dtype=torch.float32)  # accumulated into below
@@ -400,14 +402,8 @@ class DenseBlockFn(Function):
             cl = C0 + l * g
             xin = slab[:, :cl]
             dy = dslab[:, cl:cl + g]
-            if x3:
-                dy2, dyt = K.pack_split(_as3(dy), want_plain=True)
-                grads[6 * l + 4] = K.conv3x3_wgrad_x3(dy2, packs[l], H, W)
-                dxt = K.conv3x3_nhwc_f32out(dyt, K.conv3x3_nhwc_pack(K.split3_weights(_c(cw), 0), 1), None, cl, H, W)
-            elif nhwc:
-                dy16, dyt16 = K.pack_bf16(_as3(dy), g, H * W, plain_shape=(g, H * W), t_shape=(H * W, g))
-                grads[6 * l + 4] = K.conv3x3_wgrad_packed(dy16, packs[l], H, W)
-                dxt = K.conv3x3_nhwc_f32out(dyt16, K.conv3x3_nhwc_pack(_c(cw), 1), None, cl, H, W)
+            if packed:
+                dxt, grads[6 * l + 4] = _packed3x3_bwd(dy, packs[l], cw, H, W, split, True, True, dw_first=True)
             else:
                 grads[6 * l + 4] = K.conv2d_wgrad(dy, xin, 3, 1, 1, prec, in_scale=scale, in_shift=shift, in_relu=True)
                 dxt = K.conv2d_dgrad(dy, cw, (H, W), 1, 1, prec)

@@ -122,7 +122,7 @@ def test_conv3x3_wgrad_packed_operands(gd, shape):
     x, dy = bf16_round(seeded((B, Cin, H, W), 303)), bf16_round(seeded((B, Cout, Ho, Wo), 304))
     dy16 = dy.view(B, Cout, Ho * Wo).to(torch.bfloat16).to(DEV)
     x16 = x.permute(0, 2, 3, 1).reshape(B, H * W, Cin).contiguous().to(torch.bfloat16).to(DEV)
-    _check(gd, lambda: K.conv3x3_wgrad_packed(dy16, x16, H, W, stride),
+    _check(gd, lambda: K.conv3x3_wgrad16(dy16, x16, H, W, stride),
            lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, stride)[0], [_wgrad_ref(x, dy, stride)], "packed")
 
 
@@ -134,7 +134,7 @@ def test_conv3x3_wgrad_x3_three_accumulating_launches(gd):
     ref = _wgrad_ref(xh, dh, 1) + _wgrad_ref(xh, dl, 1) + _wgrad_ref(xl, dh, 1)
     dy2 = torch.stack([dh, dl]).view(2, B, Cout, H * W).to(torch.bfloat16).to(DEV)
     x3 = _nhwc_split(x).view(B, H * W, 3 * Cin)
-    _check(gd, lambda: K.conv3x3_wgrad_x3(dy2, x3, H, W), lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, 1)[0], [ref], "x3")
+    _check(gd, lambda: K.conv3x3_wgrad16(dy2, x3, H, W, split=True, tag="wgrad_x3"), lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, H, W, 1)[0], [ref], "x3")
 
 
 @pytest.mark.parametrize("split", [False, True], ids=["plain", "split"])
@@ -414,7 +414,7 @@ def test_ordered_mode_is_actually_parallel(gd):
     def timed():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        K.conv3x3_wgrad_packed(dy16, x16, H, W, 1)
+        K.conv3x3_wgrad16(dy16, x16, H, W, 1)
         e1.record()
         e1.synchronize()
         return e0.elapsed_time(e1)

@@ -114,6 +114,47 @@ def test_wide_conv3x3_through_the_pixel_major_kernel(gd, shape):
         assert_close(a, bb, 2e-3, f"pixel-major vs patch kernel: {nm}", rell2)
 
 
+# route -> (B, Cin, H, W, Cout) at the smallest shape its predicate admits, precision, layer override, db tolerance,
+# forward error of the route
+PACKED_BIAS_ONLY = {"split": ((2, 32, 8, 8, 8), "fp32", {"other": "x3"}, 1e-5, 1e-5),
+                    "bf16": ((2, 128, 8, 8, 40), "bf16", {}, 1e-4, 1e-3)}
+
+
+@pytest.mark.parametrize("relu", [False, True], ids=["linear", "relu"])
+@pytest.mark.parametrize("route", sorted(PACKED_BIAS_ONLY))
+def test_packed_conv3x3_bias_only_backward(gd, route, relu):
+    """x and w frozen, only the bias asks for a gradient: the packed routes (ops._x3_eligible / ops._wide3x3) return db
+    without packing dY and without raising.  db against fp64 (go * [y_ref > 0]).sum at the db tolerance of
+    test_conv3x3_split_bf16_vs_fp64 (1e-5) / test_conv2d_fwd_bwd (1e-4).
+    The inputs keep every y_ref away from zero, so that the route's own ReLU mask is the reference's: input channel 0 is
+    a +-2 sign image that every output channel copies through its centre tap; the other channels add N(0, ~0.1^2)."""
+    ops, _ = _ops()
+    (B, Cin, H, W, Cout), prec, override, tol, fwd_err = PACKED_BIAS_ONLY[route]
+    x = seeded((B, Cin, H, W), 21)
+    x[:, 0] = torch.where(x[:, 0] > 0, 2.0, -2.0)
+    w = seeded((Cout, Cin, 3, 3), 22, 0.1 / math.sqrt(Cin * 9))
+    w[:, 0] = 0
+    w[:, 0, 1, 1] = 1
+    b = seeded((Cout,), 23, 0.1)
+    go = seeded((B, Cout, H, W), 24)
+    if route == "bf16":
+        x, w, go = bf16_round(x), bf16_round(w), bf16_round(go)
+    y_ref = F.conv2d(x.double(), w.double(), b.double(), padding=1)
+    assert y_ref.abs().min() > fwd_err * y_ref.abs().max()
+    assert 0.25 < (y_ref > 0).double().mean() < 0.75
+    db_ref = (go.double() * (y_ref > 0) if relu else go.double()).sum((0, 2, 3))
+    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV).requires_grad_(True)
+    act = ops.ACT_RELU if relu else ops.ACT_NONE
+    with gd.precision(prec), gd.layer_override(**override):
+        if route == "split":
+            assert ops._x3("other") and ops._x3_eligible(xd, wd, 1, 1, act)
+        else:
+            assert ops._wide3x3(xd, wd, 1, 1, act, ops._prec("other"))
+        ops.conv2d(xd, wd, bd, 1, 1, act).backward(go.to(DEV))
+    assert_close(bd.grad, db_ref.float(), tol, "db")
+    assert xd.grad is None and wd.grad is None
+
+
 def test_conv2d_slab_views_and_prologue(gd):
     """conv reading a channel slice of a slab with the fused BN-affine+ReLU prologue, writing another slice"""
     ops, K = _ops()

@@ -75,7 +75,7 @@ def main():
     for Cin, Cout in ((136, 24), (368, 184), (184, 64)):
         dy16, x16 = rnd16(B, Cout, T * T), rnd16(B, T * T, Cin)
         report(f"3x3 wgrad {Cin} -> {Cout}, {T}x{T}, B={B}",
-               three_modes(lambda: K.conv3x3_wgrad_packed(dy16, x16, T, T, 1),
+               three_modes(lambda: K.conv3x3_wgrad16(dy16, x16, T, T, 1),
                            lambda: K.conv3x3_wgrad_plan(B, Cout, Cin, T, T, 1)[0], a.reps))
         del dy16, x16
     Hd = 2 * T                                                        # conv2 of Discriminator1 on a 4T x 4T image
