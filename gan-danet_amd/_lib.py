@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libgandanet_hip.so")
 PREC_FP32, PREC_BF16, PREC_X3 = 0, 1, 2   # GD_PREC_*: exact f32 MFMA / bf16 operands / split-bf16 (hi + lo, three MFMAs per product)
 PAM_BWD_K64_ATOMIC, PAM_BWD_K64_PARTS, PAM_BWD_K32_PARTS, PAM_BWD_TWO_KERNEL = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_LEAKY02, ACT_SIGMOID = 0, 1, 2, 3
+EVAL_F64, EVAL_SKIP_NAN = 1, 2   # GD_EVAL_*
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -148,6 +149,12 @@ SIGNATURES = {
     "gd_combine_inputs": (_i, [_p, _i, _i, _i, _f, _p, _i, _i, _i, _f, _p, _i, _i, _i, _p]),
     "gd_hist_match_ws_bytes": (_sz, [_l, _l]),
     "gd_hist_match": (_i, [_p, _p, _i, _l, _l, C.c_double, _p, _p, _sz, _p]),
+    "gd_eval_stats_ws_bytes": (_sz, [_l]),
+    "gd_eval_stats": (_i, [_p, _p, _l, _l, _p, C.c_double, C.c_double, _i, _p, _p, _sz, _p]),
+    "gd_masked_plane_mean_ws_bytes": (_sz, [_l, _l]),
+    "gd_masked_plane_mean": (_i, [_p, _l, _l, _p, _p, _p, _p, _sz, _p]),
+    "gd_ensemble_stats": (_i, [_p, _i, _l, _l, _i, _p, _p, _p]),
+    "gd_eval_merge_host": (_i, [C.POINTER(C.c_double), _l, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gd_blend_region": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),

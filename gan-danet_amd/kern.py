@@ -1298,3 +1298,97 @@ def nhwc_l1_grad(a: Tensor, b: Tensor, upstream: Tensor, relu_mask: bool, split:
                                   _stream()),
             "gd_nhwc_l1_grad")
     return g
+
+
+# ---- evaluation (evalstats.hip) ----------------------------------------------------------------------------------------
+def _eval_dtype(t: Tensor, name: str) -> int:
+    if not t.is_cuda:
+        raise L.GandanetError(f"{name}: expected a GPU tensor (there is no CPU fallback in the product path)")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise L.GandanetError(f"{name}: expected float32 or float64, got {t.dtype}")
+    if not t.is_contiguous():
+        raise L.GandanetError(f"{name}: expected a contiguous tensor, got strides {t.stride()}")
+    return int(t.dtype == torch.float64)
+
+
+def _eval_mask(mask: Optional[Tensor], hw: int) -> Optional[Tensor]:
+    if mask is None:
+        return None
+    _chk(mask, "mask", torch.uint8)
+    if not mask.is_contiguous() or mask.numel() != hw:
+        raise L.GandanetError(f"mask: expected {hw} contiguous uint8 entries (one per pixel of a plane), got {tuple(mask.shape)}")
+    return mask
+
+
+def eval_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] = None, affine=None,
+               skip_nan: bool = False) -> Tensor:
+    """the 8-double record of ``pred`` against ``truth`` (include/gandanet.h, "evaluation") written into ``rec`` (a view
+    of 8 fp64 on the device); ``mask`` (uint8, one entry per element of the trailing dims it covers) is shared by all
+    leading planes; ``affine`` = (a, b) reads both inputs as v * a + b.  No host sync."""
+    f64 = _eval_dtype(pred, "pred")
+    if _eval_dtype(truth, "truth") != f64 or pred.shape != truth.shape:
+        raise L.GandanetError(f"eval_stats: pred {tuple(pred.shape)} {pred.dtype} vs truth {tuple(truth.shape)} {truth.dtype}")
+    _chk(rec, "record", torch.float64)
+    if rec.numel() != 8 or not rec.is_contiguous():
+        raise L.GandanetError("eval_stats: the record is 8 contiguous float64")
+    n = pred.numel()
+    hw = n if mask is None else mask.numel()
+    if hw <= 0 or n % hw:
+        raise L.GandanetError(f"eval_stats: a mask of {hw} entries does not tile {tuple(pred.shape)}")
+    mask = _eval_mask(mask, hw)
+    a, b = (1.0, 0.0) if affine is None else (float(affine[0]), float(affine[1]))
+    nbytes = int(lib().gd_eval_stats_ws_bytes(n))
+    ws = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
+    flags = (L.EVAL_F64 if f64 else 0) | (L.EVAL_SKIP_NAN if skip_nan else 0)
+    L.check(lib().gd_eval_stats(_ptr(pred), _ptr(truth), n // hw, hw, _ptr(mask), a, b, flags, _ptr(rec), _ptr(ws), nbytes,
+                                _stream()), "gd_eval_stats")
+    return rec
+
+
+def masked_plane_mean(x: Tensor, mask: Optional[Tensor] = None, plane_dims: int = 2) -> Tuple[Tensor, Tensor]:
+    """np.nanmean over the last ``plane_dims`` dims of ``x`` with the pixels where ``mask`` is 0 left out: (mean fp64,
+    valid count int64), both shaped like the leading dims; a plane without a valid pixel gives NaN"""
+    _dense(x, "planes")
+    lead = tuple(x.shape[:x.dim() - plane_dims])
+    hw = math.prod(x.shape[x.dim() - plane_dims:])
+    planes = math.prod(lead)
+    mask = _eval_mask(mask, hw)
+    mean = torch.empty(lead, device=x.device, dtype=torch.float64)
+    count = torch.empty(lead, device=x.device, dtype=torch.int64)
+    for lo in range(0, planes, 65535):                          # grid.y limit of one launch
+        k = min(65535, planes - lo)
+        nbytes = int(lib().gd_masked_plane_mean_ws_bytes(k, hw))
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+        L.check(lib().gd_masked_plane_mean(x.data_ptr() + 4 * lo * hw, k, hw, _ptr(mask), mean.data_ptr() + 8 * lo,
+                                           count.data_ptr() + 8 * lo, _ptr(ws), nbytes, _stream()), "gd_masked_plane_mean")
+    return mean, count
+
+
+def ensemble_stats(x: Tensor, mean: Optional[Tensor] = None, std: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """mean and population std over dim 0 of ``x`` (M, ...) with 1 <= M <= 32: every member dense, members a constant
+    stride apart (a slab with unused rows behind each member is fine); fp32 or fp64, outputs in the same dtype"""
+    if not x.is_cuda or x.dtype not in (torch.float32, torch.float64):
+        raise L.GandanetError(f"ensemble_stats: expected a float32 / float64 GPU tensor, got {x.dtype} on {x.device}")
+    M = x.shape[0]
+    if x.dim() < 2 or not x[0].is_contiguous():
+        raise L.GandanetError(f"ensemble_stats: every member must be dense, got strides {x.stride()}")
+    n = x[0].numel()
+    stride = x.stride(0) if M > 1 else n
+    mean = torch.empty(x.shape[1:], device=x.device, dtype=x.dtype) if mean is None else mean
+    std = torch.empty(x.shape[1:], device=x.device, dtype=x.dtype) if std is None else std
+    for o, nm in ((mean, "mean"), (std, "std")):
+        if not o.is_cuda or o.dtype != x.dtype or o.numel() != n or not o.is_contiguous():
+            raise L.GandanetError(f"ensemble_stats: {nm} must be a dense {x.dtype} GPU tensor of {n} elements")
+    L.check(lib().gd_ensemble_stats(_ptr(x), M, stride, n, int(x.dtype == torch.float64), _ptr(mean), _ptr(std), _stream()),
+            "gd_ensemble_stats")
+    return mean, std
+
+
+def eval_merge_host(records) -> Tuple[list, dict]:
+    """merge (k, 8) host records in the given order (plain C++ on the host, no GPU): (merged record, metrics dict)"""
+    import numpy as np
+    recs = np.ascontiguousarray(np.asarray(records, dtype=np.float64).reshape(-1, 8))
+    out, met = (C.c_double * 8)(), (C.c_double * 4)()
+    ptr = recs.ctypes.data_as(C.POINTER(C.c_double)) if len(recs) else None
+    L.check(lib().gd_eval_merge_host(ptr, len(recs), out, met), "gd_eval_merge_host")
+    return list(out), {"n": out[0], "mse": met[0], "mae": met[1], "r2": met[2], "cc": met[3]}

@@ -90,6 +90,12 @@ class GanTrainer:
         with ``lr_grace_025`` as the discriminator's real sample / the pixel target"""
         return self.step(K.combine_inputs(lr_grace_05, hr_aux, 0.5, 0.25), lr_grace_025, loss_weight)
 
+    def evaluate(self, dataset, batch_size: int) -> Dict[str, float]:
+        """``ModelTrainer.evaluate`` (deep_ensemble.ipynb:L249-293) of this trainer's generator and input gate over a
+        ``DeviceTileDataset``: evaluate.evaluate; the modules come back in the mode they were in"""
+        from .evaluate import evaluate
+        return evaluate(self.G, dataset, batch_size, input_attention=self.input_attention)
+
     def step(self, x: torch.Tensor, target: torch.Tensor, loss_weight: float) -> StepOutput:
         """one G+D update (L243-269) = d_backward -> reduce -> D.step -> g_backward -> reduce -> G.step.  The two
         backward phases are separate methods so that an EXTERNAL exchange of gradients (tests emulating N ranks in

@@ -560,6 +560,46 @@ int gd_reduce_scatter(const void* send, void* recv, size_t recv_n, int dtype, vo
 int gd_allgather(const void* send, void* recv, size_t send_n, int dtype, void* stream);
 int gd_comm_destroy(void);
 
+/* ------------------------------------------------------------------------------------------
+ * Evaluation (evalstats.hip): what the reference computes on the host after train().
+ *
+ * The RECORD is 8 doubles describing n pairs (p, t):
+ *   [0] n   [1] mean_p   [2] mean_t   [3] M2_p = sum (p - mean_p)^2   [4] M2_t   [5] C_pt = sum (p - mean_p)(t - mean_t)
+ *   [6] sum |p - t|   [7] sum (p - t)^2
+ * Two records merge with Chan's pairwise formulas (n = nA + nB, d = meanB - meanA, mean = meanA + d nB / n,
+ * M2 = M2A + M2B + d^2 nA nB / n, C likewise with d_p d_t; [6] and [7] add); a record with n == 0 is neutral.  Records are
+ * what travels between batches and between ranks, so unequal counts are exact.
+ * ---------------------------------------------------------------------------------------- */
+enum { GD_EVAL_F64 = 1, GD_EVAL_SKIP_NAN = 2 };
+/* ModelTrainer.evaluate (GAN_DANet_train.ipynb c0 "def evaluate"; deep_ensemble.ipynb:L249-293): the statistics behind
+ * mean_squared_error / mean_absolute_error / r2_score / np.corrcoef of pred against truth, both dense planes x hw
+ * elements (fp32; fp64 with GD_EVAL_F64), as ONE record written to rec (device, 8 doubles), without a host sync.
+ * mask: NULL or hw bytes shared by all planes, nonzero = valid.  Both inputs are read as v * a + b (the StandardScaler
+ * inverse of deep_ensemble.ipynb; a = 1, b = 0 for none).  GD_EVAL_SKIP_NAN drops pairs with a NaN on either side
+ * (valid_mask of compute_uncertainty, L470-472).  fp64 co-moment accumulation, fixed order, no atomics: bitwise
+ * reproducible.  ws: caller-owned, gd_eval_stats_ws_bytes(planes * hw) bytes (per-workgroup partial records). */
+size_t gd_eval_stats_ws_bytes(long n);
+int gd_eval_stats(const void* pred, const void* truth, long planes, long hw, const unsigned char* mask, double a, double b,
+                  int flags, double* rec, void* ws, size_t ws_bytes, void* stream);
+/* np.nanmean(masked, axis=(lat, lon)) of compute_uncertainty (deep_ensemble.ipynb:L451-463): mean[p] (fp64) over the valid
+ * pixels of plane p of x (planes x hw, fp32, planes <= 65535), count[p] = how many; no valid pixel -> NaN, count 0.
+ * mask as above (NULL: every pixel).  ws: gd_masked_plane_mean_ws_bytes(planes, hw) bytes. */
+size_t gd_masked_plane_mean_ws_bytes(long planes, long hw);
+int gd_masked_plane_mean(const float* x, long planes, long hw, const unsigned char* mask, double* mean, long long* count,
+                         void* ws, size_t ws_bytes, void* stream);
+/* np.mean / np.std (ddof 0) over the member axis (deep_ensemble.ipynb:L465-467 and the per-pixel maps of
+ * predict_ensemble): x holds M rows (1 <= M <= 32) of n elements, member_stride elements apart; mean and std_out (n) in
+ * the input dtype (fp32; fp64 when f64 != 0), two-pass in fp64 registers, rounded once.  16-byte loads and stores for
+ * every M when the rows (member_stride, unless M == 1) and both outputs share their offset from a 16-byte boundary;
+ * otherwise every element takes the scalar path. */
+int gd_ensemble_stats(const void* x, int M, long member_stride, long n, int f64, void* mean, void* std_out, void* stream);
+/* host only, no GPU call: merge k records (recs: k x 8 doubles, host memory) in the given order into rec_out (8 doubles,
+ * may be NULL) and derive metrics[4] = mse, mae, r2, cc.  r2 as sklearn.metrics.r2_score (1 - SS_res / SS_tot; SS_tot ==
+ * 0 -> 1.0 if SS_res == 0 else 0.0), cc as np.corrcoef(t, p)[0, 1] (NaN when a variance is 0); n == 0 (or k == 0): NaN
+ * for all four (L288-291).  n == 1 follows the same rules: SS_tot is 0, so r2 is 1.0 or 0.0 (sklearn warns and returns
+ * NaN below two samples) and cc is NaN. */
+int gd_eval_merge_host(const double* recs, long k, double* rec_out, double* metrics);
+
 #ifdef __cplusplus
 }
 #endif
