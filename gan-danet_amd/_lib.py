@@ -123,6 +123,10 @@ SIGNATURES = {
     "gd_pam_wide_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "gd_pam_f32_fwd": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p, _p, _l, _p, _l, _p, _p, _p]),
     "gd_pam_f32_bwd": (_i, [_p, _l, _p, _l, _p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "gd_pam_attn_stats": (_i, [_p, _l, _p, _l, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
+    "gd_pam_attn_received": (_i, [_p, _l, _p, _l, _p, _i, _i, _i, _i, _f, _p, _p]),
+    "gd_pam_attn_rows": (_i, [_p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
+    "gd_round_to_16": (_i, [_p, _p, _l, _f, _i, _p]),
     "gd_chan_dot": (_i, [_p, _l, _p, _l, _i, _i, _i, _p, _p, _p, _p]),
     "gd_pam_f16_scale": (_i, [_p, _l, _i, _i, _i, _p, _p, _p, _p, _p]),
     "gd_conv3x3_nhwc_pack": (_i, [_p, _i, _i, _i, _p, _sz, _p]),

@@ -91,6 +91,68 @@ __device__ __forceinline__ bf16x8_t read_tr_frag_sw(const unsigned short* X, int
 
 constexpr int B_QLD = 40;   // Q tile rows [i][32 d] (80 B): 16-B reads
 
+// ---- exact-fp32 operands (pam_f32.hip, pam_probe.hip): v_mfma_f32_32x32x2_f32 on channel-major (rows, Npad) planes ----
+namespace f32 {
+
+__device__ __forceinline__ f32x16_t mfma_f32(float a, float b, f32x16_t c) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+// one LDS-DMA wave-instruction: lane l's 16 bytes land at dst + 16 l (dst is wave-uniform)
+__device__ __forceinline__ void dma16(const float* src, float* dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+
+__device__ __forceinline__ void zero16(f32x16_t& a) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) a[e] = 0.f;
+}
+
+constexpr float MASKED = 1e30f;
+constexpr int MAXKS = 32;          // k-steps of the q.k product: r <= 63 -> (r + 1) / 2 <= 32
+
+// S tile: acc += A_tile^T-rows x own fragment, A read from an LDS region of rows [d][ld floats] at column ``col``; k-steps in
+// groups of four (reads first, then the MFMAs); rows past the last k-step are clamped (their B operand is zero or unused)
+template <int LD>
+__device__ __forceinline__ void s_tile(f32x16_t& acc, const float* rows, int col, int h, int nks, const float (&own)[MAXKS]) {
+    const int last = 2 * nks - 1;
+#pragma unroll
+    for (int g = 0; g < MAXKS / 4; ++g) {
+        if (4 * g < nks) {
+            float a[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = rows[min(2 * (4 * g + j) + h, last) * LD + col];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * g + j < nks) acc = mfma_f32(a[j], own[4 * g + j], acc);
+        }
+    }
+}
+
+// key tiles of the query-parallel sweeps: 64 keys per tile, rows [channel][F_LD floats]
+constexpr int F_KT = 64;            // keys per tile
+constexpr int F_LD = 68;            // LDS row: 64 keys + 4 pad floats (17 sixteen-byte chunks, the last a repeat)
+constexpr int F_RCH = 17;
+constexpr int F_KPIECE = 17;        // 1 KiB DMA pieces of the K region (64 rows x 17 chunks / 64)
+
+// streamed 32-column tiles of the owner-parallel sweeps: r region of 64 rows x 36 floats (8 data chunks + 1 pad chunk per row)
+constexpr int B_RLD = 36, B_RCH = 9;
+constexpr int B_RREG = 9 * 256;       // floats of the r region (64 rows x 9 chunks = 9 pieces)
+
+__device__ __forceinline__ void bwd_dma_r(const float* src, int R, int nks, int ld, int y0, float* slot, int wave, int lane) {
+    const int npiece = (2 * nks * B_RCH + 63) >> 6;
+    for (int p = wave; p < npiece; p += 4) {
+        const int c = p * 64 + lane;
+        const int row = c / B_RCH, part = c - row * B_RCH;
+        dma16(src + (long)min(row, R - 1) * ld + y0 + min(part, B_RCH - 2) * 4, slot + p * 256);
+    }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+}  // namespace f32
+
 // ---- host side ----
 // V channel chunks: `tiles` 32-channel tiles split into the fewest chunks of at most 6 tiles (the forward's register
 // ceiling), as even as possible

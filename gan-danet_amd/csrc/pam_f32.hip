@@ -32,51 +32,11 @@ namespace {
 
 using pam::LOG2E;
 using gd::acc_row;
-
-__device__ __forceinline__ f32x16_t mfma_f32(float a, float b, f32x16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// one LDS-DMA wave-instruction: lane l's 16 bytes land at dst + 16 l (dst is wave-uniform)
-__device__ __forceinline__ void dma16(const float* src, float* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
-__device__ __forceinline__ void zero16(f32x16_t& a) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) a[e] = 0.f;
-}
-
-constexpr float MASKED = 1e30f;
-constexpr int MAXKS = 32;          // k-steps of the q.k product: r <= 63 -> (r + 1) / 2 <= 32
-
-// S tile: acc += A_tile^T-rows x own fragment, A read from an LDS region of rows [d][ld floats] at column ``col``; k-steps in
-// groups of four (reads first, then the MFMAs); rows past the last k-step are clamped (their B operand is zero or unused)
-template <int LD>
-__device__ __forceinline__ void s_tile(f32x16_t& acc, const float* rows, int col, int h, int nks, const float (&own)[MAXKS]) {
-    const int last = 2 * nks - 1;
-#pragma unroll
-    for (int g = 0; g < MAXKS / 4; ++g) {
-        if (4 * g < nks) {
-            float a[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = rows[min(2 * (4 * g + j) + h, last) * LD + col];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * g + j < nks) acc = mfma_f32(a[j], own[4 * g + j], acc);
-        }
-    }
-}
+using namespace pam::f32;     // s_tile, the LDS-DMA helpers and the tile geometry shared with pam_probe.hip
 
 // =====================================================================================================
 // forward
 // =====================================================================================================
-constexpr int F_KT = 64;            // keys per tile
-constexpr int F_LD = 68;            // LDS row: 64 keys + 4 pad floats (17 sixteen-byte chunks, the last a repeat)
-constexpr int F_RCH = 17;
-constexpr int F_KPIECE = 17;        // 1 KiB DMA pieces of the K region (64 rows x 17 chunks / 64)
-
 template <int CT>
 __global__ __launch_bounds__(256) void pam_f32_fwd_kernel(const float* __restrict__ q, long q_bs, const float* __restrict__ k,
                                                           long k_bs, const float* __restrict__ v, long v_bs, int c0, int N,
@@ -216,18 +176,6 @@ __global__ __launch_bounds__(256) void pam_f32_fwd_kernel(const float* __restric
 // backward: streamed 32-column tiles.  Slot = [r region: 64 rows x 36 floats (8 data chunks + 1 pad chunk per row)]
 //                                             [C region: rows of CLD floats][lse 32][delta 32]
 // =====================================================================================================
-constexpr int B_RLD = 36, B_RCH = 9;
-constexpr int B_RREG = 9 * 256;       // floats of the r region (64 rows x 9 chunks = 9 pieces)
-
-__device__ __forceinline__ void bwd_dma_r(const float* src, int R, int nks, int ld, int y0, float* slot, int wave, int lane) {
-    const int npiece = (2 * nks * B_RCH + 63) >> 6;
-    for (int p = wave; p < npiece; p += 4) {
-        const int c = p * 64 + lane;
-        const int row = c / B_RCH, part = c - row * B_RCH;
-        dma16(src + (long)min(row, R - 1) * ld + y0 + min(part, B_RCH - 2) * 4, slot + p * 256);
-    }
-}
-
 // -----------------------------------------------------------------------------------------------------
 // dV^T of one channel chunk (CT x 32 channels from c0); owners = keys
 // -----------------------------------------------------------------------------------------------------
@@ -450,8 +398,6 @@ __global__ __launch_bounds__(256) void pam_f32_dkq_kernel(const float* __restric
             }
     }
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 

@@ -990,6 +990,42 @@ def pam_f32_bwd(q, k, v, gdo, lse, delta, B, N, Npad, Cn, r, dq, dk, dv):
                                      _ptr(_dense(dq)), _ptr(_dense(dk)), _ptr(_dense(dv)), _stream()), "gd_pam_f32_bwd")
 
 
+# ---- PAM attention probe (gd_pam_attn_*): the attention of q, k (B, r, Npad) fp32 planes without the N x N matrix ----------
+def pam_attn_stats(q, k, B, N, Npad, r, lse, entropy=None, peak=None, logit_scale: float = 1.0):
+    """(B, N) maps lse, entropy (nats), peak = max_j P_ij of softmax_j(logit_scale q_i . k_j); see gd_pam_attn_stats"""
+    with _Bracket("pam_attn_stats", 2.0 * N * N * r * B):
+        L.check(lib().gd_pam_attn_stats(_ptr(q), _plane_bs(q, "q"), _ptr(k), _plane_bs(k, "k"), B, N, Npad, r, float(logit_scale),
+                                        _ptr(_dense(lse)), _ptr(None if entropy is None else _dense(entropy)),
+                                        _ptr(None if peak is None else _dense(peak)), _stream()), "gd_pam_attn_stats")
+
+
+def pam_attn_received(q, k, lse, B, N, Npad, r, received, logit_scale: float = 1.0):
+    """received (B, N): sum over the queries of P_ij, from the lse of pam_attn_stats; see gd_pam_attn_received"""
+    with _Bracket("pam_attn_received", 2.0 * N * N * r * B):
+        L.check(lib().gd_pam_attn_received(_ptr(q), _plane_bs(q, "q"), _ptr(k), _plane_bs(k, "k"), _ptr(_dense(lse)), B, N, Npad,
+                                           r, float(logit_scale), _ptr(_dense(received)), _stream()), "gd_pam_attn_received")
+
+
+def pam_attn_rows(q, k, idx, B, N, Npad, r, rows, lse_rows=None, logit_scale: float = 1.0):
+    """rows (B, S, N): the attention rows of the queries ``idx`` (int32, S values in [0, N)); see gd_pam_attn_rows"""
+    _chk(idx, "idx", torch.int32)
+    S = idx.numel()
+    if idx.dim() != 1 or not idx.is_contiguous():
+        raise L.GandanetError("idx: expected a contiguous 1-D int32 tensor")
+    with _Bracket("pam_attn_rows", 4.0 * N * S * r * B):
+        L.check(lib().gd_pam_attn_rows(_ptr(q), _plane_bs(q, "q"), _ptr(k), _plane_bs(k, "k"), _ptr(idx), S, B, N, Npad, r,
+                                       float(logit_scale), _ptr(_dense(rows)),
+                                       _ptr(None if lse_rows is None else _dense(lse_rows)), _stream()), "gd_pam_attn_rows")
+
+
+def round_to_16(x: Tensor, scale: float = 1.0, f16: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """float(rne16(x * scale)) elementwise, bf16 or (``f16``) IEEE fp16: the rounding pack_bf16 applies; see gd_round_to_16"""
+    _dense(x, "round_to_16 input")
+    out = torch.empty_like(x) if out is None else _dense(out, "round_to_16 output")
+    L.check(lib().gd_round_to_16(_ptr(x), _ptr(out), x.numel(), float(scale), int(f16), _stream()), "gd_round_to_16")
+    return out
+
+
 # =====================================================================================================
 # NHWC bf16 kernels (frozen VGG19 feature stack of PerceptualLoss)
 # =====================================================================================================

@@ -96,6 +96,13 @@ class GanTrainer:
         from .evaluate import evaluate
         return evaluate(self.G, dataset, batch_size, input_attention=self.input_attention)
 
+    def attention_report(self, x: torch.Tensor, points=()) -> Dict[str, Dict[str, torch.Tensor]]:
+        """the attention every dual-attention block of this trainer's generator puts on the generator input ``x`` (passed
+        through the input gate first, as in ``step``): attention.attention_report; the modules come back in the mode they
+        were in"""
+        from .attention import attention_report
+        return attention_report(self.G, x, points, input_attention=self.input_attention)
+
     def step(self, x: torch.Tensor, target: torch.Tensor, loss_weight: float) -> StepOutput:
         """one G+D update (L243-269) = d_backward -> reduce -> D.step -> g_backward -> reduce -> G.step.  The two
         backward phases are separate methods so that an EXTERNAL exchange of gradients (tests emulating N ranks in

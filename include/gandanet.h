@@ -461,6 +461,37 @@ int gd_pam_f32_bwd(const float* q, long q_bs, const float* k, long k_bs, const f
                    long gdo_bs, const float* lse, const float* delta, int B, int N, int Npad, int C, int r, float* dq,
                    float* dk, float* dv, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PAM attention probe: the attention P = softmax_j(s_ij), s_ij = logit_scale * (q_i . k_j) in nats, of generator.py:115-118
+ * looked at without the N x N matrix.  Operand contract of gd_pam_f32_fwd: q, k (B, r, Npad) fp32 planes with batch strides
+ * q_bs / k_bs >= 0 (elements, multiples of 4), 16-byte aligned, Npad a multiple of 256 >= N, columns >= N zero, 1 <= r <= 63
+ * (padded to the MFMA k-step inside the kernels only).  Every product is a v_mfma_f32_32x32x2_f32.  logit_scale = 1 for the
+ * projections as they are; ln 2 for planes that hold what the 16-bit routes multiply (q log2 e and k rounded by
+ * gd_round_to_16).  No atomics, no scratch, no N x N or N x tile buffer; every output element is summed by one wave in a
+ * fixed order, so two runs agree bit for bit.  Nothing here is differentiable.
+ * Each returns 0, or -1 with gd_last_error naming the argument (checked on the host before any GPU call).
+ *
+ * gd_pam_attn_stats (query-parallel sweep, online in the running maximum m: l = sum_j e^(s - m), u = sum_j e^(s - m) (s - m);
+ * when m rises by d, u <- e^-d (u - d l) and l <- e^-d l); (B, N) fp32 maps, entropy / peak optional (NULL = skip):
+ *   lse     = m + ln l
+ *   entropy = ln l - u / l     = -sum_j P_ij ln P_ij, nats
+ *   peak    = 1 / l            = max_j P_ij */
+int gd_pam_attn_stats(const float* q, long q_bs, const float* k, long k_bs, int B, int N, int Npad, int r, float logit_scale,
+                      float* lse, float* entropy, float* peak, void* stream);
+/* key-parallel sweep with the lse of gd_pam_attn_stats: received[b][j] = sum_{i < N} exp(s_ij - lse[b][i]), (B, N) fp32: how
+ * much attention key j receives from all queries; its mean over j is 1. */
+int gd_pam_attn_received(const float* q, long q_bs, const float* k, long k_bs, const float* lse, int B, int N, int Npad, int r,
+                         float logit_scale, float* received, void* stream);
+/* attention rows of S selected queries, 1 <= S <= 256: idx holds S ints in [0, N) shared by the images of the batch (the
+ * kernel clamps, so a bad index never reads out of bounds; callers check the range); rows[b][s][j] = softmax_j(s_{idx[s], j}),
+ * (B, S, N) fp32 dense; lse_rows (B, S) optional (NULL = skip), bit for bit the lse of gd_pam_attn_stats at those queries.
+ * Self-contained: one sweep for the row statistics, a second that writes P. */
+int gd_pam_attn_rows(const float* q, long q_bs, const float* k, long k_bs, const int* idx, int S, int B, int N, int Npad, int r,
+                     float logit_scale, float* rows, float* lse_rows, void* stream);
+/* y[i] = float(rne16(x[i] * scale)), n elements: bf16 (f16 = 0) or IEEE fp16 (f16 = 1), the rounding gd_pack_16 applies to
+ * the operands of the 16-bit PAM routes (x and y may be the same buffer) */
+int gd_round_to_16(const float* x, float* y, long n, float scale, int f16, void* stream);
+
 /* test.ipynb c1:69-85 mild_histogram_matching, per sample of a batch: out[b] = (1 - weight) * src[b] + weight *
  * interp(cdf_src(src[b]), cdf_ref, sorted unique ref[b]) with numpy's np.unique / np.interp semantics (float64 result, as
  * the notebook produces).  src (B, ns), ref (B, nt) fp32; out (B, ns) fp64; ws: caller-owned scratch of
