@@ -15,6 +15,8 @@ PREC_FP32, PREC_BF16, PREC_X3 = 0, 1, 2   # GD_PREC_*: exact f32 MFMA / bf16 ope
 PAM_BWD_K64_ATOMIC, PAM_BWD_K64_PARTS, PAM_BWD_K32_PARTS, PAM_BWD_TWO_KERNEL = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_LEAKY02, ACT_SIGMOID = 0, 1, 2, 3
 EVAL_F64, EVAL_SKIP_NAN = 1, 2   # GD_EVAL_*
+GUARD_SQNORM, GUARD_NORM, GUARD_COEF, GUARD_OK, GUARD_APPLIED, GUARD_SKIPPED, GUARD_RECORD = range(7)   # GD_GUARD_*
+GUARD_CHUNK = 65536              # GD_GUARD_CHUNK
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -159,6 +161,10 @@ SIGNATURES = {
     "gd_masked_plane_mean": (_i, [_p, _l, _l, _p, _p, _p, _p, _sz, _p]),
     "gd_ensemble_stats": (_i, [_p, _i, _l, _l, _i, _p, _p, _p]),
     "gd_eval_merge_host": (_i, [C.POINTER(C.c_double), _l, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gd_grad_sqnorm_ws_bytes": (_sz, [_l]),
+    "gd_grad_sqnorm": (_i, [C.POINTER(_p), C.POINTER(_l), _i, _f, _i, _p, _p, _sz, _p]),
+    "gd_guard_finalize": (_i, [_p, C.c_double, _i, _p]),
+    "gd_adamw_guarded": (_i, [_p, _p, _p, _p, _p, _l, _p, _f, _f, _f, _f, _f, _f, _f, _p]),
     "gd_blend_region": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),

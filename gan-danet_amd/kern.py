@@ -1428,3 +1428,56 @@ def eval_merge_host(records) -> Tuple[list, dict]:
     ptr = recs.ctypes.data_as(C.POINTER(C.c_double)) if len(recs) else None
     L.check(lib().gd_eval_merge_host(ptr, len(recs), out, met), "gd_eval_merge_host")
     return list(out), {"n": out[0], "mse": met[0], "mae": met[1], "r2": met[2], "cc": met[3]}
+
+
+# ---- guarded step (include/gandanet.h, "guarded step") --------------------------------------------------------------
+def guard_record(device) -> Tensor:
+    """a zeroed guard record: 6 fp64 on ``device`` (sqnorm, norm, coef, ok, applied_steps, skipped_steps)"""
+    return torch.zeros(L.GUARD_RECORD, device=device, dtype=torch.float64)
+
+
+def _guard_rec(rec: Tensor) -> Tensor:
+    _chk(rec, "guard record", torch.float64)
+    if rec.numel() != L.GUARD_RECORD or not rec.is_contiguous():
+        raise L.GandanetError(f"guard record: expected {L.GUARD_RECORD} contiguous float64")
+    return rec
+
+
+def grad_sqnorm(grads, rec: Tensor, grad_scale: float = 1.0, accumulate: bool = False) -> Tensor:
+    """rec[0] (+)= sum over the dense fp32 tensors ``grads`` of (g * grad_scale)^2, in fp64 and in a fixed order; the
+    pointers travel in the kernel arguments, so nothing is copied to the device and nothing waits.  No host sync."""
+    _guard_rec(rec)
+    grads = list(grads)
+    if not grads:
+        raise L.GandanetError("grad_sqnorm: empty tensor list")
+    for g in grads:
+        _dense(g, "grad_sqnorm tensor")
+    k = len(grads)
+    ptrs = (L.c_fp * k)(*[g.data_ptr() for g in grads])
+    ns = (C.c_long * k)(*[g.numel() for g in grads])
+    nbytes = int(lib().gd_grad_sqnorm_ws_bytes(sum(-(-g.numel() // L.GUARD_CHUNK) for g in grads)))
+    ws = torch.empty(max(nbytes, 8), device=rec.device, dtype=torch.uint8)
+    L.check(lib().gd_grad_sqnorm(ptrs, ns, k, grad_scale, int(accumulate), _ptr(rec), _ptr(ws), nbytes, _stream()),
+            "gd_grad_sqnorm")
+    return rec
+
+
+def guard_finalize(rec: Tensor, max_norm: Optional[float] = None, skip_nonfinite: bool = False) -> Tensor:
+    """norm, clip factor and the apply / skip decision from rec[0]; advances applied_steps or skipped_steps"""
+    _guard_rec(rec)
+    L.check(lib().gd_guard_finalize(_ptr(rec), 0.0 if max_norm is None else float(max_norm), int(skip_nonfinite), _stream()),
+            "gd_guard_finalize")
+    return rec
+
+
+def adamw_guarded(p: Tensor, g: Tensor, m: Tensor, v: Tensor, rec: Tensor, lr: float, beta1: float, beta2: float, eps: float,
+                  weight_decay: float, grad_scale: float = 1.0, ema: Optional[Tensor] = None, ema_decay: float = 0.0) -> None:
+    """``adamw`` under the decision in ``rec``: clipped by rec's coef, skipped when rec's ok is 0, bias-corrected by rec's
+    applied_steps; ``ema`` (optional) is updated in the same launch"""
+    _guard_rec(rec)
+    for t in (p, g, m, v) + (() if ema is None else (ema,)):
+        _dense(t, "adamw_guarded tensor")
+        if t.numel() != p.numel():
+            raise L.GandanetError("adamw_guarded: tensors of different sizes")
+    L.check(lib().gd_adamw_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), _ptr(rec), lr, beta1, beta2, eps,
+                                   weight_decay, grad_scale, ema_decay, _stream()), "gd_adamw_guarded")

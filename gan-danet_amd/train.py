@@ -13,12 +13,14 @@ the generator loss is evaluated; ``loss_G = (1-w) MSE + w BCE(D(hr), 1) + TV + P
 """
 from __future__ import annotations
 
+import copy
 from dataclasses import dataclass
 from typing import Dict, Optional
 
 import torch
 from torch import nn
 
+from . import _lib as L
 from . import kern as K
 from . import ops
 from .optim import AdamW
@@ -44,7 +46,9 @@ class GanTrainer:
                  compute_ssim: bool = True, tv_global_batch_semantics: bool = False,
                  batch_real_fake: bool = True, input_attention: Optional[nn.Module] = None,
                  reduce_gradients: bool = True, external_world: Optional[int] = None,
-                 shard_bytes: int = 256 << 20, sync_bn: Optional[bool] = None) -> None:
+                 shard_bytes: int = 256 << 20, sync_bn: Optional[bool] = None,
+                 max_grad_norm_g: Optional[float] = None, max_grad_norm_d: Optional[float] = None,
+                 skip_nonfinite: bool = False, ema_decay: Optional[float] = None) -> None:
         self.G, self.D, self.perceptual = G, D, perceptual
         # sync_bn: BatchNorm statistics reduced over all ranks (config.sync_bn; process-wide).  With
         # tv_global_batch_semantics=True a world of W ranks on B/W samples each then takes the step one device takes on B
@@ -66,9 +70,18 @@ class GanTrainer:
         # discriminator tensors of >= shard_bytes (Discriminator1.fc1: 8.6 GB at 256x256 tiles) take the
         # reduce-scatter -> 1/world AdamW -> all-gather route under data parallelism (parallel.ShardedParam)
         self.sharded = shard_big_params(D, shard_bytes) if (reduce_gradients and shard_bytes > 0) else []
+        # the guarded step (optim.AdamW): clip each network's global gradient norm, skip a step whose norm is not finite,
+        # keep an averaged generator (EMA of G and of the input gate, not of D).  All decided on the device; off by default.
+        # With any of them on, BOTH optimisers run guarded (a norm limit of 0 = report the norm, clip nothing), so the step
+        # output carries both networks' gradient norms
+        if any(o is not None for o in (max_grad_norm_g, max_grad_norm_d, ema_decay)) or skip_nonfinite:
+            max_grad_norm_g = 0.0 if max_grad_norm_g is None else max_grad_norm_g
+            max_grad_norm_d = 0.0 if max_grad_norm_d is None else max_grad_norm_d
         self.opt_d = AdamW(D.parameters(), lr=lr_d, betas=betas, weight_decay=weight_decay, grad_scale=1.0 / ws,
-                           sharded=self.sharded)
-        self.opt_g = AdamW(g_params, lr=lr_g, betas=betas, weight_decay=weight_decay, grad_scale=1.0 / ws)
+                           sharded=self.sharded, max_grad_norm=max_grad_norm_d, skip_nonfinite=skip_nonfinite)
+        self.opt_g = AdamW(g_params, lr=lr_g, betas=betas, weight_decay=weight_decay, grad_scale=1.0 / ws,
+                           max_grad_norm=max_grad_norm_g, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay)
+        self.ema_decay = ema_decay
         self.red_d = GradReducer(D.parameters(), sharded=self.sharded) if reduce_gradients else _NoReduce()
         self.red_g = GradReducer(g_params) if reduce_gradients else _NoReduce()
         # TVLoss divides by the batch size twice (losses.py:82-87): per-shard TV averaged over ranks is `world`
@@ -90,11 +103,41 @@ class GanTrainer:
         with ``lr_grace_025`` as the discriminator's real sample / the pixel target"""
         return self.step(K.combine_inputs(lr_grace_05, hr_aux, 0.5, 0.25), lr_grace_025, loss_weight)
 
-    def evaluate(self, dataset, batch_size: int) -> Dict[str, float]:
+    def evaluate(self, dataset, batch_size: int, use_ema: bool = False) -> Dict[str, float]:
         """``ModelTrainer.evaluate`` (deep_ensemble.ipynb:L249-293) of this trainer's generator and input gate over a
-        ``DeviceTileDataset``: evaluate.evaluate; the modules come back in the mode they were in"""
+        ``DeviceTileDataset``: evaluate.evaluate; the modules come back in the mode they were in.  ``use_ema``: the
+        averaged generator and gate (``ema_generator``) instead of the live ones"""
         from .evaluate import evaluate
+        if use_ema:
+            return evaluate(self.ema_generator(), dataset, batch_size, input_attention=self.ema_input_attention())
         return evaluate(self.G, dataset, batch_size, input_attention=self.input_attention)
+
+    @torch.no_grad()
+    def _ema_copy(self, module: nn.Module, shadows) -> nn.Module:
+        """a copy of ``module`` (same class, same constructor arguments, same mode) whose parameters ARE the shadow tensors
+        (no copy: it follows later steps) and whose buffers -- BN running statistics, num_batches_tracked -- are copied
+        from the live module now"""
+        live = list(module.parameters())
+        for p in live:                                  # the copy gets the shadows: do not clone 2x the weights first
+            if isinstance(p, nn.parameter.UninitializedParameter):
+                raise RuntimeError("materialise lazy parameters (one forward) before asking for the averaged module")
+        memo = {id(p): nn.Parameter(e, requires_grad=False) for p, e in zip(live, shadows)}
+        return copy.deepcopy(module, memo)
+
+    def ema_generator(self) -> nn.Module:
+        """the averaged generator: ``G``'s class and constructor arguments, parameters = the optimiser's EMA shadows,
+        buffers copied from ``G`` at call time"""
+        if self.ema_decay is None:
+            raise RuntimeError("GanTrainer.ema_generator: built without ema_decay")
+        return self._ema_copy(self.G, self.opt_g.ema_params()[:len(list(self.G.parameters()))])
+
+    def ema_input_attention(self) -> Optional[nn.Module]:
+        """the averaged input gate (None without one)"""
+        if self.input_attention is None:
+            return None
+        if self.ema_decay is None:
+            raise RuntimeError("GanTrainer.ema_input_attention: built without ema_decay")
+        return self._ema_copy(self.input_attention, self.opt_g.ema_params()[len(list(self.G.parameters())):])
 
     def attention_report(self, x: torch.Tensor, points=()) -> Dict[str, Dict[str, torch.Tensor]]:
         """the attention every dual-attention block of this trainer's generator puts on the generator input ``x`` (passed
@@ -117,7 +160,21 @@ class GanTrainer:
         self.g_backward(st, target, loss_weight)
         self.red_g.reduce()
         self.opt_g.step()
-        return self.finish(st)
+        out = self.finish(st)
+        out.parts.update(self.guard_parts())
+        return out
+
+    def guard_parts(self) -> Dict[str, torch.Tensor]:
+        """``grad_norm_g / grad_norm_d / skipped_g / skipped_d`` of the step just taken, as device tensors (copies of the
+        optimisers' records: a later step does not change them); empty when no guard is on"""
+        if not (self.opt_g.guarded or self.opt_d.guarded):
+            return {}
+        parts = {}
+        for tag, opt in (("g", self.opt_g), ("d", self.opt_d)):
+            if opt.guarded:
+                rec = opt._record().clone()
+                parts["grad_norm_" + tag], parts["skipped_" + tag] = rec[L.GUARD_NORM], rec[L.GUARD_SKIPPED]
+        return parts
 
     def sync_params(self) -> None:
         """wait for the all-gathers of sharded weights still in flight (before reading D's parameters outside a

@@ -631,6 +631,38 @@ int gd_ensemble_stats(const void* x, int M, long member_stride, long n, int f64,
  * NaN below two samples) and cc is NaN. */
 int gd_eval_merge_host(const double* recs, long k, double* rec_out, double* metrics);
 
+/* ------------------------------------------------------------------------------------------
+ * Guarded step: gradient norm, clipping, skipping of non-finite steps and an averaged copy of the weights (EMA), decided
+ * and applied on the device.  One caller-owned RECORD of 6 doubles in device memory carries the decision from the norm
+ * to the update kernels; the host reads it only when it wants to know:
+ *   [0] sqnorm = sum (g * gscale)^2 over all gradients   [1] norm = sqrt(sqnorm)   [2] coef, the clip factor in (0, 1]
+ *   [3] ok: 1 = apply this step, 0 = skip it   [4] applied_steps   [5] skipped_steps
+ * A step is gd_grad_sqnorm (once, or twice with `accumulate`) -> gd_guard_finalize -> gd_adamw_guarded per tensor.
+ * ---------------------------------------------------------------------------------------- */
+enum { GD_GUARD_SQNORM = 0, GD_GUARD_NORM = 1, GD_GUARD_COEF = 2, GD_GUARD_OK = 3, GD_GUARD_APPLIED = 4, GD_GUARD_SKIPPED = 5,
+       GD_GUARD_RECORD = 6 };
+#define GD_GUARD_CHUNK 65536L /* elements of one tensor summed by one workgroup into one partial slot */
+/* rec[0] = (accumulate ? rec[0] : 0) + sum over the `count` fp32 tensors (grads[t], ns[t] elements; host arrays) of
+ * (g * gscale)^2.  The (pointer, n) pairs travel by value in the kernel arguments, 48 per launch: nothing is copied to
+ * or pinned for the device, so gradient buffers may move from step to step.  fp64 accumulation; one partial per
+ * (tensor, GD_GUARD_CHUNK elements of it) in ws, summed by a second stage in a fixed ascending order: no atomics, the
+ * same bits on every run, whatever the launch geometry.  Pointers need only element alignment (16-byte loads from the
+ * first 16-byte boundary of each chunk, scalar head and tail).  A non-finite gradient makes the sum non-finite.
+ * ws: gd_grad_sqnorm_ws_bytes(sum_t ceil(ns[t] / GD_GUARD_CHUNK)) bytes. */
+size_t gd_grad_sqnorm_ws_bytes(long total_chunks);
+int gd_grad_sqnorm(const float* const* grads, const long* ns, int count, float gscale, int accumulate, double* rec, void* ws,
+                   size_t ws_bytes, void* stream);
+/* norm = sqrt(sqnorm); ok = isfinite(norm), or 1 whatever the norm when skip_nonfinite == 0; coef = min(1, max_norm /
+ * (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), 1 when max_norm <= 0; applied_steps += ok; skipped_steps += !ok. */
+int gd_guard_finalize(double* rec, double max_norm, int skip_nonfinite, void* stream);
+/* gd_adamw with the gradient read as g * (grad_scale * coef), nothing written when ok == 0, and the bias corrections
+ * taken from applied_steps (which gd_guard_finalize has already advanced for this step): a skipped step does not
+ * advance Adam's time.  ema: NULL, or the averaged weights, updated in the same pass as ema = ema_decay * ema +
+ * (1 - ema_decay) * p_new.  The scaled gradient is never written back.  16-byte accesses when all tensors share their
+ * offset from a 16-byte boundary, scalar otherwise. */
+int gd_adamw_guarded(float* p, const float* g, float* m, float* v, float* ema, long n, const double* rec, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, float grad_scale, float ema_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
