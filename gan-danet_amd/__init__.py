@@ -13,6 +13,7 @@ from .config import config, layer_override, precision, set_precision, set_sync_b
 from .kern import set_deterministic
 from .attention import attention_report, cam_attention, pam_attention_rows, pam_attention_stats
 from .discriminator import SRGAND, Discriminator1
+from . import filters
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)

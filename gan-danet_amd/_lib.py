@@ -17,6 +17,9 @@ ACT_NONE, ACT_RELU, ACT_LEAKY02, ACT_SIGMOID = 0, 1, 2, 3
 EVAL_F64, EVAL_SKIP_NAN = 1, 2   # GD_EVAL_*
 GUARD_SQNORM, GUARD_NORM, GUARD_COEF, GUARD_OK, GUARD_APPLIED, GUARD_SKIPPED, GUARD_RECORD = range(7)   # GD_GUARD_*
 GUARD_CHUNK = 65536              # GD_GUARD_CHUNK
+FILTER_F32, FILTER_F64 = 0, 1    # GD_FILTER_*
+EDGE_REFLECT, EDGE_INTERIOR = 0, 1   # GD_EDGE_*
+FILTER_MAX_RADIUS, SAVGOL_MAX_WINDOW = 64, 33   # GD_FILTER_MAX_RADIUS, GD_SAVGOL_MAX_WINDOW
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -165,6 +168,12 @@ SIGNATURES = {
     "gd_grad_sqnorm": (_i, [C.POINTER(_p), C.POINTER(_l), _i, _f, _i, _p, _p, _sz, _p]),
     "gd_guard_finalize": (_i, [_p, C.c_double, _i, _p]),
     "gd_adamw_guarded": (_i, [_p, _p, _p, _p, _p, _l, _p, _f, _f, _f, _f, _f, _f, _f, _p]),
+    "gd_gaussian_weights_host": (_i, [C.c_double, C.c_double, C.POINTER(C.c_double), _i]),
+    "gd_correlate1d_axis": (_i, [_p, _p, _i, _l, _l, _l, C.POINTER(C.c_double), _i, _i, _p]),
+    "gd_savgol_edges_axis": (_i, [_p, _p, _i, _l, _l, _l, _p, _i, _p]),
+    "gd_median_nd": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), _p]),
+    "gd_fill_prepare": (_i, [_p, C.c_double, _p, _p, _i, _l, _p]),
+    "gd_fill_ratio": (_i, [_p, _p, _p, C.c_double, _p, _i, _l, _p]),
     "gd_blend_region": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import kern as K
+from .filters import SMOOTHING_METHODS
 from .parallel import rank as _rank
 from .parallel import world_size as _world
 
@@ -39,12 +40,18 @@ class DeviceTileDataset:
     ``lr_grace_05`` (N, h, w), ``lr_grace_025`` (N, H, W), ``hr_aux`` (N, H, W, C) as in the reference (numpy or
     tensors); stored as (N, 1, h, w), (N, 1, H, W), (N, C, H, W) fp32 (datasets.py:158-160).
     ``noise``: "reference" draws the Gaussian noise with torch's CPU generator exactly where the reference does
-    (bit-identical stream, host-bound); "device" draws it on the GPU (same distribution, different stream)."""
+    (bit-identical stream, host-bound); "device" draws it on the GPU (same distribution, different stream).
+    ``smoothing``: the notebook trainer's ``smoothing_method``, applied once to ``hr_aux`` after the upload -- before
+    the split and before any batch is cut, as there: None, "gaussian" (sigma 2), "median" (size 3), "savgol" (5, 2) --
+    ``filters.smooth_data_*`` -- or a callable taking and returning the stored (N, C, H, W) tensor."""
 
-    def __init__(self, lr_grace_05, lr_grace_025, hr_aux, augment: bool = False, device=None, noise: str = "device"):
+    def __init__(self, lr_grace_05, lr_grace_025, hr_aux, augment: bool = False, device=None, noise: str = "device",
+                 smoothing=None):
         device = torch.device("cuda") if device is None else torch.device(device)
         if device.type != "cuda":
             raise K.L.GandanetError("DeviceTileDataset: tensors live on the GPU (there is no CPU path)")
+        if not (smoothing is None or callable(smoothing) or (isinstance(smoothing, str) and smoothing in SMOOTHING_METHODS)):
+            raise ValueError(f"smoothing must be None, a callable or one of {sorted(SMOOTHING_METHODS)}")
         as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
         self.lr_grace_05 = as_t(lr_grace_05).float().unsqueeze(1).contiguous().to(device)
         self.lr_grace_025 = as_t(lr_grace_025).float().unsqueeze(1).contiguous().to(device)
@@ -53,6 +60,12 @@ class DeviceTileDataset:
             raise ValueError("the three arrays must hold the same number of samples")
         if noise not in ("device", "reference"):
             raise ValueError("noise must be 'device' or 'reference'")
+        if smoothing is not None:
+            smooth = smoothing if callable(smoothing) else SMOOTHING_METHODS[smoothing]
+            shape = self.hr_aux.shape
+            self.hr_aux = smooth(self.hr_aux)
+            if not isinstance(self.hr_aux, torch.Tensor) or self.hr_aux.shape != shape:
+                raise ValueError("smoothing must return a tensor shaped like the (N, C, H, W) tensor it was given")
         self.augment, self.noise, self.device = augment, noise, device
 
     def __len__(self) -> int:

@@ -1481,3 +1481,84 @@ def adamw_guarded(p: Tensor, g: Tensor, m: Tensor, v: Tensor, rec: Tensor, lr: f
             raise L.GandanetError("adamw_guarded: tensors of different sizes")
     L.check(lib().gd_adamw_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), _ptr(rec), lr, beta1, beta2, eps,
                                    weight_decay, grad_scale, ema_decay, _stream()), "gd_adamw_guarded")
+
+
+# ---- filters (include/gandanet.h, "filters"; filters.hip) ------------------------------------------------------------
+def _filter_dtype(t: Tensor, name: str) -> int:
+    return _eval_dtype(t, name)                                  # fp32 -> GD_FILTER_F32, fp64 -> GD_FILTER_F64
+
+
+def _axis_view(t: Tensor, axis: int) -> Tuple[int, int, int]:
+    """(outer, L, inner) of a dense tensor around ``axis``"""
+    return math.prod(t.shape[:axis]), t.shape[axis], math.prod(t.shape[axis + 1:])
+
+
+def gaussian_weights_host(sigma: float, truncate: float = 4.0):
+    """scipy's Gaussian taps as a ctypes array of 2 * radius + 1 doubles, and the radius (plain C++ on the host, no GPU)"""
+    cap = 2 * L.FILTER_MAX_RADIUS + 1
+    w = (C.c_double * cap)()
+    radius = lib().gd_gaussian_weights_host(float(sigma), float(truncate), w, cap)
+    if radius < 0:
+        raise L.GandanetError(f"gd_gaussian_weights_host failed (rc={radius}): {L.last_error()}")
+    return w, radius
+
+
+def correlate1d_axis(src: Tensor, dst: Tensor, axis: int, weights, radius: int, edge_mode: int = L.EDGE_REFLECT) -> Tensor:
+    """``dst`` = ``src`` correlated with ``weights`` (2 * radius + 1 host doubles) along ``axis``; no host sync"""
+    dt = _filter_dtype(src, "correlate1d src")
+    if _filter_dtype(dst, "correlate1d dst") != dt or dst.shape != src.shape:
+        raise L.GandanetError(f"correlate1d_axis: src {tuple(src.shape)} {src.dtype} vs dst {tuple(dst.shape)} {dst.dtype}")
+    if not isinstance(weights, C.Array):
+        weights = (C.c_double * len(weights))(*[float(v) for v in weights])
+    if len(weights) < 2 * radius + 1:
+        raise L.GandanetError(f"correlate1d_axis: {len(weights)} weights for radius {radius}")
+    outer, n, inner = _axis_view(src, axis)
+    L.check(lib().gd_correlate1d_axis(_ptr(src), _ptr(dst), dt, outer, n, inner, weights, radius, edge_mode, _stream()),
+            "gd_correlate1d_axis")
+    return dst
+
+
+def savgol_edges_axis(src: Tensor, dst: Tensor, axis: int, edge: Tensor, window: int) -> Tensor:
+    """the first and last ``window // 2`` positions of ``dst`` along ``axis`` from ``edge`` (2, window // 2, window) fp64"""
+    dt = _filter_dtype(src, "savgol src")
+    if _filter_dtype(dst, "savgol dst") != dt or dst.shape != src.shape:
+        raise L.GandanetError(f"savgol_edges_axis: src {tuple(src.shape)} {src.dtype} vs dst {tuple(dst.shape)} {dst.dtype}")
+    _chk(edge, "savgol edge matrices", torch.float64)
+    if not edge.is_contiguous() or tuple(edge.shape) != (2, window // 2, window):
+        raise L.GandanetError(f"savgol_edges_axis: edge matrices {tuple(edge.shape)}, expected {(2, window // 2, window)}")
+    outer, n, inner = _axis_view(src, axis)
+    L.check(lib().gd_savgol_edges_axis(_ptr(src), _ptr(dst), dt, outer, n, inner, _ptr(edge), window, _stream()),
+            "gd_savgol_edges_axis")
+    return dst
+
+
+def median_nd(src: Tensor, shape4, size4) -> Tensor:
+    """median over a ``size4`` box of ``src`` seen as the 4-D ``shape4`` ('reflect' edges); a new tensor shaped like src"""
+    dt = _filter_dtype(src, "median src")
+    if len(shape4) != 4 or len(size4) != 4 or math.prod(shape4) != src.numel():
+        raise L.GandanetError(f"median_nd: {tuple(shape4)} / {tuple(size4)} is not a 4-D view of {tuple(src.shape)}")
+    dst = torch.empty_like(src)
+    L.check(lib().gd_median_nd(_ptr(src), _ptr(dst), dt, (C.c_int64 * 4)(*shape4), (C.c_int * 4)(*size4), _stream()),
+            "gd_median_nd")
+    return dst
+
+
+def fill_prepare(x: Tensor, placeholder: float) -> Tuple[Tensor, Tensor]:
+    """(x with the gaps ``x <= placeholder`` zeroed, the valid mask as 0 / 1 in x's dtype) in one pass"""
+    dt = _filter_dtype(x, "fill input")
+    vals, mask = torch.empty_like(x), torch.empty_like(x)
+    L.check(lib().gd_fill_prepare(_ptr(x), float(placeholder), _ptr(vals), _ptr(mask), dt, x.numel(), _stream()),
+            "gd_fill_prepare")
+    return vals, mask
+
+
+def fill_ratio(x: Tensor, num: Tensor, den: Tensor, placeholder: float) -> Tensor:
+    """num / (den == 0 ? 1 : den) at the gaps of ``x``, ``x`` itself elsewhere; a new tensor"""
+    dt = _filter_dtype(x, "fill input")
+    for t, nm in ((num, "numerator"), (den, "denominator")):
+        if _filter_dtype(t, nm) != dt or t.shape != x.shape:
+            raise L.GandanetError(f"fill_ratio: {nm} {tuple(t.shape)} {t.dtype} vs x {tuple(x.shape)} {x.dtype}")
+    dst = torch.empty_like(x)
+    L.check(lib().gd_fill_ratio(_ptr(x), _ptr(num), _ptr(den), float(placeholder), _ptr(dst), dt, x.numel(), _stream()),
+            "gd_fill_ratio")
+    return dst

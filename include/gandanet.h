@@ -663,6 +663,53 @@ int gd_guard_finalize(double* rec, double max_norm, int skip_nonfinite, void* st
 int gd_adamw_guarded(float* p, const float* g, float* m, float* v, float* ema, long n, const double* rec, float lr, float beta1,
                      float beta2, float eps, float weight_decay, float grad_scale, float ema_decay, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Filters: the trainer's smoothing_method hook (GAN_DANet_train.ipynb: smooth_data_gaussian / _median /
+ * _savitzky_golay) and the Gaussian smoothing and gap fill of datasets.py (gaussian_filter per plane,
+ * fill_placeholder_with_nearest), with scipy's semantics.  A dense tensor is seen as (outer, L, inner) around the
+ * filtered axis; storage fp32 (dtype 0) or fp64 (dtype 1); every sum is fp64, rounded to the storage type once per pass
+ * (scipy's correlate1d).  The caller owns all memory, nothing is allocated or copied, nothing waits for the device; no
+ * atomics: the same bits on every run.  Pointers need element alignment only.  Index arithmetic is 64-bit and launches
+ * are cut where a grid dimension would pass its limit.  NaN inputs: the correlations propagate them like any sum; the
+ * median of a window that holds a NaN is unspecified.
+ * ---------------------------------------------------------------------------------------- */
+enum { GD_FILTER_F32 = 0, GD_FILTER_F64 = 1 };
+enum { GD_EDGE_REFLECT = 0, GD_EDGE_INTERIOR = 1 };
+#define GD_FILTER_MAX_RADIUS 64 /* taps = 2 * radius + 1 <= 129: sigma <= 16 at truncate 4 */
+#define GD_SAVGOL_MAX_WINDOW 33
+/* host only, no GPU call: scipy's Gaussian taps.  radius = int(truncate * sigma + 0.5); w[k + radius] = exp(-0.5 / sigma^2 *
+ * k^2) / sum, k = -radius .. radius, in fp64 (the sum in np.sum's order).  Returns the radius; negative when sigma <= 0 or
+ * 2 * radius + 1 > cap (the capacity of w in doubles). */
+int gd_gaussian_weights_host(double sigma, double truncate, double* w, int cap);
+/* dst[o, l, i] = sum_{k = -radius .. radius} w_host[k + radius] * src[o, idx(l + k), i], taps added in ascending k.
+ * w_host: 2 * radius + 1 doubles in HOST memory; they travel in the kernel arguments.  radius <= GD_FILTER_MAX_RADIUS.
+ * src != dst.  edge_mode GD_EDGE_REFLECT = scipy's 'reflect' (half-sample symmetric): with p = 2L and j = (l + k) mod p
+ * (0 <= j < p), idx = j < L ? j : p - 1 - j -- any radius against any L, L == 1 included.  GD_EDGE_INTERIOR: only
+ * l in [radius, L - radius) is written, the rest of dst is left as it was (savgol_filter's interior).
+ * inner > 1: lanes along inner (16 bytes per lane where inner is a whole number of 16-byte vectors and src and dst share
+ * their offset from a 16-byte boundary; a scalar head and tail, or all columns scalar, otherwise); inner == 1: lanes
+ * along L, a segment plus halo staged in LDS (16-byte loads for the rows that start on a 16-byte boundary). */
+int gd_correlate1d_axis(const void* src, void* dst, int dtype, long outer, long L, long inner, const double* w_host, int radius,
+                        int edge_mode, void* stream);
+/* scipy.signal.savgol_filter's mode='interp' edges: with h = window / 2, for p < h
+ *   dst[o, p, i]         = sum_j edge_dev[0][p][j] * src[o, j, i]
+ *   dst[o, L - h + p, i] = sum_j edge_dev[1][p][j] * src[o, L - window + j, i]      (j < window)
+ * edge_dev: (2, h, window) doubles in DEVICE memory (rows of the least-squares hat matrix).  window odd, <=
+ * GD_SAVGOL_MAX_WINDOW and <= L; src != dst; nothing else of dst is written. */
+int gd_savgol_edges_axis(const void* src, void* dst, int dtype, long outer, long L, long inner, const double* edge_dev,
+                         int window, void* stream);
+/* scipy.ndimage.median_filter(mode='reflect') over a box on a dense tensor seen as 4-D: shape4 and size4 are HOST arrays
+ * (pad leading dimensions with shape 1, size 1).  Each size is 1, 3 or 5 and their product is 3, 5, 9, 25, 27 or 81.  The
+ * median of an odd count is one of the inputs: the result is exact.  src != dst. */
+int gd_median_nd(const void* src, void* dst, int dtype, const int64_t* shape4, const int* size4, void* stream);
+/* fill_placeholder_with_nearest (datasets.py:222-250) around its two gaussian_filter calls: gd_fill_prepare writes
+ * vals = x <= placeholder ? 0 : x and mask = x <= placeholder ? 0 : 1; gd_fill_ratio writes dst = num / (den == 0 ? 1 : den)
+ * where x <= placeholder (the quotient in fp64, rounded once) and dst = x bit for bit elsewhere.  Every buffer is a
+ * buffer of its own. */
+int gd_fill_prepare(const void* x, double placeholder, void* vals, void* mask, int dtype, long n, void* stream);
+int gd_fill_ratio(const void* x, const void* num, const void* den, double placeholder, void* dst, int dtype, long n,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
