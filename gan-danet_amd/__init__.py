@@ -14,6 +14,7 @@ from .kern import set_deterministic
 from .attention import attention_report, cam_attention, pam_attention_rows, pam_attention_stats
 from .discriminator import SRGAND, Discriminator1
 from . import filters
+from . import spline
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)

@@ -20,6 +20,7 @@ GUARD_CHUNK = 65536              # GD_GUARD_CHUNK
 FILTER_F32, FILTER_F64 = 0, 1    # GD_FILTER_*
 EDGE_REFLECT, EDGE_INTERIOR = 0, 1   # GD_EDGE_*
 FILTER_MAX_RADIUS, SAVGOL_MAX_WINDOW = 64, 33   # GD_FILTER_MAX_RADIUS, GD_SAVGOL_MAX_WINDOW
+ZOOM_MIRROR, ZOOM_NEAREST = 0, 1   # GD_ZOOM_*
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -174,6 +175,12 @@ SIGNATURES = {
     "gd_median_nd": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), _p]),
     "gd_fill_prepare": (_i, [_p, C.c_double, _p, _p, _i, _l, _p]),
     "gd_fill_ratio": (_i, [_p, _p, _p, C.c_double, _p, _i, _l, _p]),
+    "gd_zoom_axis_ws_bytes": (_sz, [_l, _l, _l, _i, _i]),
+    "gd_zoom_axis": (_i, [_p, _p, _i, _i, _l, _l, _l, _l, _i, _i, _p, _sz, _p]),
+    "gd_spline_prefilter_axis": (_i, [_p, _p, _i, _l, _l, _l, _p]),
+    "gd_restore_units": (_i, [_p, _i, _p, _i, _p, _l, _l, C.c_double, C.c_double, C.c_double, _p, _i, _p]),
+    "gd_masked_plane_mean_f64_ws_bytes": (_sz, [_l, _l]),
+    "gd_masked_plane_mean_f64": (_i, [_p, _l, _l, _p, _p, _p, _p, _sz, _p]),
     "gd_blend_region": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),

@@ -257,6 +257,56 @@ __global__ __launch_bounds__(EV_THREADS) void plane_sum_kernel(const float* __re
         o[1] = c;
     }
 }
+// the same partials of an fp64 plane (gd_masked_plane_mean_f64), a NaN pixel counting as invalid: 16-byte loads of two
+// doubles from the first 16-byte boundary
+__global__ __launch_bounds__(EV_THREADS) void plane_sum_f64_kernel(const double* __restrict__ x, long hw,
+                                                                   const unsigned char* __restrict__ mask,
+                                                                   double* __restrict__ ws) {
+    __shared__ double red[EV_THREADS / 64][2];
+    const int tid = threadIdx.x;
+    const double* p = x + (long)blockIdx.y * hw;
+    long head = head_of(p);
+    if (head > hw) head = hw;
+    const long nv = (hw - head) / 2;
+    const double2* p2 = reinterpret_cast<const double2*>(p + head);
+    double s = 0.0;
+    unsigned int cnt = 0;
+    for (long v = (long)blockIdx.x * EV_THREADS + tid; v < nv; v += (long)gridDim.x * EV_THREADS) {
+        const double2 q = p2[v];
+        const double e[2] = {q.x, q.y};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const bool valid = (mask ? mask[head + v * 2 + j] != 0 : true) && e[j] == e[j];
+            s += valid ? e[j] : 0.0;
+            cnt += valid ? 1u : 0u;
+        }
+    }
+    if (blockIdx.x == 0) {
+        const long body_end = head + nv * 2, rest = hw - nv * 2;
+        for (long r = tid; r < rest; r += EV_THREADS) {
+            const long i = r < head ? r : body_end + (r - head);
+            const bool valid = (mask ? mask[i] != 0 : true) && p[i] == p[i];
+            s += valid ? p[i] : 0.0;
+            cnt += valid ? 1u : 0u;
+        }
+    }
+    s = gd_wave_sum_d(s);
+    double c = gd_wave_sum_d((double)cnt);
+    if ((tid & 63) == 0) {
+        red[tid >> 6][0] = s;
+        red[tid >> 6][1] = c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < EV_THREADS / 64; ++w) {
+            s += red[w][0];
+            c += red[w][1];
+        }
+        double* o = ws + 2 * ((long)blockIdx.y * gridDim.x + blockIdx.x);
+        o[0] = s;
+        o[1] = c;
+    }
+}
 // one thread per plane adds the plane's gx partials in ascending order; no valid pixel -> NaN (np.nanmean)
 __global__ void plane_mean_final_kernel(const double* __restrict__ ws, int gx, long planes, double* __restrict__ mean,
                                         long long* __restrict__ count) {
@@ -430,6 +480,24 @@ extern "C" int gd_masked_plane_mean(const float* x, long planes, long hw, const 
                  "gd_masked_plane_mean: pointer not element aligned");
     const int gx = plane_gx(planes, hw);
     hipLaunchKernelGGL(plane_sum_kernel, dim3(gx, (unsigned)planes), dim3(EV_THREADS), 0, GD_S, x, hw, mask, (double*)ws);
+    hipLaunchKernelGGL(plane_mean_final_kernel, dim3(gd_cdiv(planes, 256)), dim3(256), 0, GD_S, (const double*)ws, gx, planes,
+                       mean, count);
+    GD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t gd_masked_plane_mean_f64_ws_bytes(long planes, long hw) { return gd_masked_plane_mean_ws_bytes(planes, hw); }
+
+extern "C" int gd_masked_plane_mean_f64(const double* x, long planes, long hw, const unsigned char* mask, double* mean,
+                                        long long* count, void* ws, size_t ws_bytes, void* stream) {
+    GD_CHECK_ARG(x && mean && count && ws, "gd_masked_plane_mean_f64: null pointer");
+    GD_CHECK_ARG(planes > 0 && hw > 0, "gd_masked_plane_mean_f64: n <= 0");
+    GD_CHECK_ARG(planes <= 65535, "gd_masked_plane_mean_f64: more than 65535 planes in one call");
+    GD_CHECK_ARG(ws_bytes >= gd_masked_plane_mean_f64_ws_bytes(planes, hw), "gd_masked_plane_mean_f64: workspace smaller than gd_masked_plane_mean_f64_ws_bytes");
+    GD_CHECK_ARG(((uintptr_t)x % 8) == 0 && ((uintptr_t)mean % 8) == 0 && ((uintptr_t)count % 8) == 0 && ((uintptr_t)ws % 8) == 0,
+                 "gd_masked_plane_mean_f64: pointer not element aligned");
+    const int gx = plane_gx(planes, hw);
+    hipLaunchKernelGGL(plane_sum_f64_kernel, dim3(gx, (unsigned)planes), dim3(EV_THREADS), 0, GD_S, x, hw, mask, (double*)ws);
     hipLaunchKernelGGL(plane_mean_final_kernel, dim3(gd_cdiv(planes, 256)), dim3(256), 0, GD_S, (const double*)ws, gx, planes,
                        mean, count);
     GD_LAUNCH_CHECK();

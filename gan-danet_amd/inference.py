@@ -83,3 +83,75 @@ def predict_batch(model: torch.nn.Module, lr_grace_025: torch.Tensor, aux: torch
     K.blend_region(canvas, patch, mask, (0, er - sr, 0, ec - sc))
     yhat[:, :, sr:er, sc:ec] = canvas                                     # slice copy (plumbing)
     return yhat
+
+
+# ---- behind the loader loop: test.ipynb cell 3, after the `with torch.no_grad()` loop -----------------------------------
+def _mask_u8(mask, shape) -> torch.Tensor:
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise K.L.GandanetError("mask: expected a GPU tensor (there is no CPU path)")
+    if tuple(mask.shape) != tuple(shape):
+        raise K.L.GandanetError(f"mask: expected the product's plane {tuple(shape)}, got {tuple(mask.shape)}")
+    return (mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)).contiguous()
+
+
+@torch.no_grad()
+def restore_units(res: torch.Tensor, trend=None, scale: float = 1.0, mean: float = 0.0, unit: float = 1.0, mask=None,
+                  out_dtype=torch.float64, out=None) -> torch.Tensor:
+    """``((res + trend) * scale + mean) * unit`` in one launch (``gd_restore_units``): the notebook's ``res + trend_ups``,
+    ``scaler025.inverse_transform`` (a StandardScaler with one feature: ``* scale_ + mean_``) and ``* 10.0``.  Evaluated
+    in fp64 in that order, every operation rounded, so an fp64 result equals numpy's bit for bit.  ``mask`` (the shape of
+    res's trailing dims; 0 = outside) gives NaN there.  ``out=res`` works in place when ``res`` already has
+    ``out_dtype``."""
+    for t, name in ((res, "res"), (trend, "trend")):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda):
+            raise K.L.GandanetError(f"restore_units: {name} must be a GPU tensor (there is no CPU path)")
+    res = res if res.is_contiguous() else res.contiguous()
+    if trend is not None and not trend.is_contiguous():
+        trend = trend.contiguous()
+    if mask is not None:
+        mask = _mask_u8(mask, res.shape[res.dim() - mask.dim():])
+    if out is None:
+        out = torch.empty(res.shape, device=res.device, dtype=out_dtype)
+    return K.restore_units(res, trend, mask, scale, mean, unit, out)
+
+
+@torch.no_grad()
+def zoom_mask(mask: torch.Tensor, factor) -> torch.Tensor:
+    """``zoom(mask, factor, order=1) != 0`` as uint8: the notebooks' ``tpbh_hi = zoom(tpbh, (5, 5), order=1)`` and ``tpbl =
+    zoom(tpbl, (2, 2), order=1)`` with the comparison they are used in"""
+    from . import spline
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise K.L.GandanetError("zoom_mask: expected a GPU tensor (there is no CPU path)")
+    m = mask if mask.dtype in (torch.float32, torch.float64) else mask.to(torch.float64)
+    return (spline.zoom(m, factor, order=1) != 0).to(torch.uint8)
+
+
+@torch.no_grad()
+def assemble_product(res: torch.Tensor, trend25: torch.Tensor, scale: float, mean: float, *, trend_zoom=(1, 5, 5),
+                     unit: float = 10.0, mask=None, bias=None, bias_zoom=(1, 1.25, 1.25), uncertainty=None,
+                     uncertainty_zoom=(1, 5, 5)) -> dict:
+    """the post-loop chain of test.ipynb cell 3 on the device, from the stacked tiles ``res`` (T, H, W) to the product:
+
+        trend_ups = zoom(trend25, trend_zoom, order=3)          res = res + trend_ups
+        res_cm = scaler.inverse_transform(res) * unit           (scale, mean: the scaler's scale_ and mean_)
+        res_cm[:, mask == 0] = nan                              (mask: (H, W), at product resolution)
+        series = np.nanmean(res_cm, axis=(1, 2))
+        product = res_cm + zoom(bias, bias_zoom, order=3)       (bias given)
+        unc = zoom(uncertainty, uncertainty_zoom, order=0, mode='nearest')
+
+    Returns ``{"product": (T, H, W) fp64, "series": (T,) fp64, "uncertainty": fp64-or-input-dtype tensor or None}``.  The
+    series is taken before the bias is added, as in the notebook; a time step without a valid pixel gives NaN."""
+    from . import spline
+    trend_ups = spline.zoom(trend25, trend_zoom, order=3)
+    if trend_ups.shape != res.shape:
+        raise K.L.GandanetError(f"assemble_product: zoomed trend {tuple(trend_ups.shape)} vs tiles {tuple(res.shape)}")
+    mask_u8 = None if mask is None else _mask_u8(mask, res.shape[-2:])
+    product = restore_units(res, trend_ups, scale, mean, unit, mask_u8)
+    series, _ = K.masked_plane_mean_f64(product, mask_u8)
+    if bias is not None:
+        bias_ups = spline.zoom(bias, bias_zoom, order=3)
+        if bias_ups.shape != product.shape:
+            raise K.L.GandanetError(f"assemble_product: zoomed bias {tuple(bias_ups.shape)} vs product {tuple(product.shape)}")
+        product += bias_ups.to(product.dtype)                        # plumbing: one ATen add
+    unc = None if uncertainty is None else spline.zoom(uncertainty, uncertainty_zoom, order=0, mode="nearest")
+    return {"product": product, "series": series, "uncertainty": unc}

@@ -1562,3 +1562,77 @@ def fill_ratio(x: Tensor, num: Tensor, den: Tensor, placeholder: float) -> Tenso
     L.check(lib().gd_fill_ratio(_ptr(x), _ptr(num), _ptr(den), float(placeholder), _ptr(dst), dt, x.numel(), _stream()),
             "gd_fill_ratio")
     return dst
+
+
+# ---- spline zoom (include/gandanet.h, "spline zoom"; spline.hip) -------------------------------------------------------
+def zoom_axis(src: Tensor, axis: int, n_out: int, order: int, mode: int, out_dtype=None) -> Tensor:
+    """``src`` zoomed to ``n_out`` samples along ``axis`` (scipy.ndimage.zoom's rule for one axis); a new tensor of
+    ``out_dtype`` (default: the dtype of ``src``).  The order-3 coefficients live in a temporary.  No host sync."""
+    sdt = _filter_dtype(src, "zoom src")
+    out_dtype = src.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise L.GandanetError(f"zoom_axis: expected float32 or float64 output, got {out_dtype}")
+    outer, n, inner = _axis_view(src, axis)
+    shape = list(src.shape)
+    shape[axis] = int(n_out)
+    dst = torch.empty(shape, device=src.device, dtype=out_dtype)
+    nbytes = int(lib().gd_zoom_axis_ws_bytes(outer, n, inner, order, mode))
+    ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8) if nbytes else None
+    L.check(lib().gd_zoom_axis(_ptr(src), _ptr(dst), sdt, int(out_dtype == torch.float64), outer, n, int(n_out), inner, order,
+                               mode, _ptr(ws), nbytes, _stream()), "gd_zoom_axis")
+    return dst
+
+
+def spline_prefilter_axis(src: Tensor, axis: int) -> Tensor:
+    """the cubic B-spline coefficients of ``src`` along ``axis`` (mirror boundary) as a new fp64 tensor"""
+    sdt = _filter_dtype(src, "spline_filter src")
+    outer, n, inner = _axis_view(src, axis)
+    dst = torch.empty(src.shape, device=src.device, dtype=torch.float64)
+    L.check(lib().gd_spline_prefilter_axis(_ptr(src), _ptr(dst), sdt, outer, n, inner, _stream()), "gd_spline_prefilter_axis")
+    return dst
+
+
+def restore_units(x: Tensor, trend: Optional[Tensor], mask: Optional[Tensor], scale: float, mean: float, unit: float,
+                  out: Tensor) -> Tensor:
+    """``out`` = ((x + trend) * scale + mean) * unit in fp64, NaN where ``mask`` (uint8, one entry per element of the
+    trailing dims it covers) is 0; ``out`` may be ``x`` itself when the dtypes match"""
+    xdt = _filter_dtype(x, "restore_units x")
+    odt = _filter_dtype(out, "restore_units out")
+    if out.shape != x.shape:
+        raise L.GandanetError(f"restore_units: out {tuple(out.shape)} vs x {tuple(x.shape)}")
+    tdt = 0
+    if trend is not None:
+        tdt = _filter_dtype(trend, "restore_units trend")
+        if trend.shape != x.shape:
+            raise L.GandanetError(f"restore_units: trend {tuple(trend.shape)} vs x {tuple(x.shape)}")
+    n = x.numel()
+    hw = n
+    if mask is not None:
+        hw = mask.numel()
+        _eval_mask(mask, hw)
+        if hw == 0 or n % hw or tuple(x.shape[x.dim() - mask.dim():]) != tuple(mask.shape):
+            raise L.GandanetError(f"restore_units: mask {tuple(mask.shape)} does not cover the trailing dims of {tuple(x.shape)}")
+    L.check(lib().gd_restore_units(_ptr(x), xdt, _ptr(trend), tdt, _ptr(mask), n // hw, hw, float(scale), float(mean),
+                                   float(unit), _ptr(out), odt, _stream()), "gd_restore_units")
+    return out
+
+
+def masked_plane_mean_f64(x: Tensor, mask: Optional[Tensor] = None, plane_dims: int = 2) -> Tuple[Tensor, Tensor]:
+    """``masked_plane_mean`` of an fp64 tensor; NaN pixels are left out as well, as np.nanmean leaves them out"""
+    _chk(x, "planes", torch.float64)
+    if not x.is_contiguous():
+        raise L.GandanetError(f"planes: expected a contiguous tensor, got strides {x.stride()}")
+    lead = tuple(x.shape[:x.dim() - plane_dims])
+    hw = math.prod(x.shape[x.dim() - plane_dims:])
+    planes = math.prod(lead)
+    mask = _eval_mask(mask, hw)
+    mean = torch.empty(lead, device=x.device, dtype=torch.float64)
+    count = torch.empty(lead, device=x.device, dtype=torch.int64)
+    for lo in range(0, planes, 65535):                          # grid.y limit of one launch
+        k = min(65535, planes - lo)
+        nbytes = int(lib().gd_masked_plane_mean_f64_ws_bytes(k, hw))
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+        L.check(lib().gd_masked_plane_mean_f64(x.data_ptr() + 8 * lo * hw, k, hw, _ptr(mask), mean.data_ptr() + 8 * lo,
+                                               count.data_ptr() + 8 * lo, _ptr(ws), nbytes, _stream()),
+                "gd_masked_plane_mean_f64")
+    return mean, count

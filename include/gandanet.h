@@ -710,6 +710,54 @@ int gd_fill_prepare(const void* x, double placeholder, void* vals, void* mask, i
 int gd_fill_ratio(const void* x, const void* num, const void* den, double placeholder, void* dst, int dtype, long n,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Spline zoom (spline.hip): scipy.ndimage.zoom at orders 0, 1 and 3, which the inference notebooks apply to everything
+ * behind the loader loop (test.ipynb cell 3, after the `with torch.no_grad()` loop), and the pointwise chain that turns
+ * the tiles into a product in physical units.  A dense tensor is seen as (outer, L, inner) around the zoomed axis;
+ * storage fp32 (dtype 0) or fp64 (dtype 1), all arithmetic fp64, one rounding to the destination type.  The caller owns
+ * all memory, nothing is allocated, nothing waits for the device, no atomics.  Pointers need element alignment only.
+ * The rules, per axis (grid_mode=False): output o samples the coordinate o * (Lin - 1) / (Lout - 1) (0 when Lout == 1);
+ * order 0 takes sample floor(c + 0.5); order 1 taps f = floor(c) and f + 1 with weights 1 - t, t (t = c - f); order 3 taps
+ * f - 1 .. f + 2 of the prefiltered coefficients with u = 1 - t, w0 = u^3 / 6, w1 = (t^2 (t - 2) 3 + 4) / 6,
+ * w2 = (u^2 (u - 2) 3 + 4) / 6, w3 = 1 - w0 - w1 - w2.  A tap outside [0, n - 1] folds whole-sample symmetric: p = 2 (n - 1),
+ * j = i mod p, index j < n ? j : p - j (0 when n == 1).
+ * ---------------------------------------------------------------------------------------- */
+enum { GD_ZOOM_MIRROR = 0, GD_ZOOM_NEAREST = 1 };
+/* zoom(..., order, mode) along one axis: `trend_ups = zoom(trend25, (1, 5, 5), order=3)`, `zoom(tpbh, (5, 5), order=1)`,
+ * `zoom(biash, (1, 1.25, 1.25), order=3)`, `zoom(uncr, (1, 5, 5), order=0, mode='nearest')` of test.ipynb cell 3, `tpbl =
+ * zoom(tpbl, (2, 2), order=1)` of the 0.25-degree script, and the `zoom(..., order=3, mode='nearest')` calls of
+ * datasets.py:294-303, one axis per call.  src (outer, Lin, inner) in src_dtype -> dst (outer, Lout, inner) in dst_dtype;
+ * src != dst.  order in {0, 1, 3}.  GD_ZOOM_MIRROR is scipy's mode 'constant' (its default; the coordinates never leave the
+ * array, so cval is never produced) and 'mirror'; GD_ZOOM_NEAREST is 'nearest', which at order 3 pads the line by 12 edge
+ * samples either way in front of the prefilter (half-sample symmetric boundary sums) and shifts the coordinates by 12; the
+ * two agree at orders 0 and 1.  ws: gd_zoom_axis_ws_bytes(outer, Lin, inner, order, mode) bytes -- the fp64 coefficients
+ * of order 3 ((outer, Lin or Lin + 24, inner)); 0 bytes (ws may be NULL) at orders 0 and 1.
+ * Order 3 is the prefilter into ws and the interpolation out of it.  The prefilter cuts every line into chunks that are
+ * warm-started from 40 samples of look-back / look-ahead (z^40 = 1.3e-23; the exact boundary sums where the horizon
+ * reaches an end of the line): inner > 1 runs lanes along inner, 64 samples per thread; inner == 1 stages row segments
+ * in LDS and runs lanes along the line, 9 samples per thread. */
+size_t gd_zoom_axis_ws_bytes(long outer, long Lin, long inner, int order, int mode);
+int gd_zoom_axis(const void* src, void* dst, int src_dtype, int dst_dtype, long outer, long Lin, long Lout, long inner,
+                 int order, int mode, void* ws, size_t ws_bytes, void* stream);
+/* scipy.ndimage.spline_filter1d(order=3, mode='mirror', output=float64) along one axis, the prefilter that
+ * `zoom(trend25, (1, 5, 5), order=3)` (test.ipynb cell 3) runs first: pole z = sqrt(3) - 2, the samples scaled by
+ * (1 - z)(1 - 1 / z) = 6, causal c[i] += z c[i-1] from c[0] = (c[0] + z^(n-1) c[n-1] + sum_{i=1}^{n-2} z^i (c[i] +
+ * z^(n-1) c[n-1-i])) / (1 - z^(2(n-1))), anticausal c[i] = z (c[i+1] - c[i]) from c[n-1] = (z c[n-2] + c[n-1]) z / (z^2 - 1);
+ * a line of one sample passes through.  src (outer, L, inner) in src_dtype -> dst, fp64, same shape; src != dst. */
+int gd_spline_prefilter_axis(const void* src, double* dst, int src_dtype, long outer, long L, long inner, void* stream);
+/* `res = res + trend_ups`, `scaler025.inverse_transform(...)`, `* 10.0` and `res_cm[:, tpbh_hi == 0] = np.nan` of test.ipynb
+ * cell 3 in one pass: dst = ((x + trend) * scale + mean) * unit in fp64, evaluated in exactly that order with every
+ * operation rounded (no FMA contraction), so an fp64 dst equals numpy's bit for bit; NaN where mask[p] == 0.  x, trend,
+ * dst: planes x hw elements; mask: hw bytes shared by all planes.  trend and mask may be NULL (no addition, no NaN).
+ * dst may alias x only when their dtypes match. */
+int gd_restore_units(const void* x, int x_dtype, const void* trend, int trend_dtype, const unsigned char* mask, long planes,
+                     long hw, double scale, double mean, double unit, void* dst, int dst_dtype, void* stream);
+/* `np.nanmean(res_cm, axis=(1, 2))` of test.ipynb cell 3: gd_masked_plane_mean on fp64 planes, with np.nanmean's rule that a
+ * NaN pixel is left out like a masked one (a plane of NaNs gives NaN, count 0). */
+size_t gd_masked_plane_mean_f64_ws_bytes(long planes, long hw);
+int gd_masked_plane_mean_f64(const double* x, long planes, long hw, const unsigned char* mask, double* mean, long long* count,
+                             void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
