@@ -15,6 +15,7 @@ from .attention import attention_report, cam_attention, pam_attention_rows, pam_
 from .discriminator import SRGAND, Discriminator1
 from . import filters
 from . import spline
+from . import prepare
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)

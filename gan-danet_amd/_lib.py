@@ -21,6 +21,7 @@ FILTER_F32, FILTER_F64 = 0, 1    # GD_FILTER_*
 EDGE_REFLECT, EDGE_INTERIOR = 0, 1   # GD_EDGE_*
 FILTER_MAX_RADIUS, SAVGOL_MAX_WINDOW = 64, 33   # GD_FILTER_MAX_RADIUS, GD_SAVGOL_MAX_WINDOW
 ZOOM_MIRROR, ZOOM_NEAREST = 0, 1   # GD_ZOOM_*
+FREQ_MAX_BINS, FREQ_MAX_TABLE_BYTES = 33, 16 << 20   # GD_FREQ_MAX_BINS, GD_FREQ_MAX_TABLE_BYTES
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -182,6 +183,13 @@ SIGNATURES = {
     "gd_masked_plane_mean_f64_ws_bytes": (_sz, [_l, _l]),
     "gd_masked_plane_mean_f64": (_i, [_p, _l, _l, _p, _p, _p, _p, _sz, _p]),
     "gd_blend_region": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "gd_channel_moments_ws_bytes": (_sz, [_l, _l]),
+    "gd_channel_moments": (_i, [_p, _i, _l, _l, _p, _p, _sz, _p]),
+    "gd_scale_from_moments_host": (_i, [C.POINTER(C.c_double), _l, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)]),
+    "gd_channel_affine": (_i, [_p, _i, _p, _i, _l, _l, _p, _p, _i, _l, _l, _p]),
+    "gd_freq_cos_table_host": (_i, [_l, _i, C.POINTER(C.c_double)]),
+    "gd_freq_augment_axis": (_i, [_p, _p, _i, _l, _l, _l, _p, _i, _p, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

@@ -1636,3 +1636,91 @@ def masked_plane_mean_f64(x: Tensor, mask: Optional[Tensor] = None, plane_dims: 
                                                count.data_ptr() + 8 * lo, _ptr(ws), nbytes, _stream()),
                 "gd_masked_plane_mean_f64")
     return mean, count
+
+
+# ---- dataset preparation (include/gandanet.h, "dataset preparation"; prepare.hip) ----------------------------------------
+def channel_moments(x: Tensor, channels: int) -> Tensor:
+    """(count, mean, M2) of every channel of the dense channel-last ``x`` seen as (numel / channels, channels): a new
+    (channels, 3) fp64 device tensor.  No host sync."""
+    dt = _filter_dtype(x, "channel_moments input")
+    c = int(channels)
+    if c <= 0 or x.numel() == 0 or x.numel() % c:
+        raise L.GandanetError(f"channel_moments: {tuple(x.shape)} is not a non-empty array of rows of {c} channels")
+    m = x.numel() // c
+    rec = torch.empty(c, 3, device=x.device, dtype=torch.float64)
+    nbytes = int(lib().gd_channel_moments_ws_bytes(m, c))
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    L.check(lib().gd_channel_moments(_ptr(x), dt, m, c, _ptr(rec), _ptr(ws), nbytes, _stream()), "gd_channel_moments")
+    return rec
+
+
+def scale_from_moments_host(rec):
+    """sklearn's (mean_, var_, scale_) as fp64 numpy arrays from a (C, 3) HOST array of records (plain C++, no GPU)"""
+    import numpy as np
+    rec = np.ascontiguousarray(rec, dtype=np.float64)
+    if rec.ndim != 2 or rec.shape[1] != 3:
+        raise L.GandanetError(f"scale_from_moments_host: expected (C, 3) records, got {rec.shape}")
+    c = rec.shape[0]
+    dp = C.POINTER(C.c_double)
+    mean, var, scale = np.empty(c), np.empty(c), np.empty(c)
+    L.check(lib().gd_scale_from_moments_host(rec.ctypes.data_as(dp), c, mean.ctypes.data_as(dp), var.ctypes.data_as(dp),
+                                             scale.ctypes.data_as(dp)), "gd_scale_from_moments_host")
+    return mean, var, scale
+
+
+def channel_affine(src: Tensor, mean: Tensor, scale: Tensor, inverse: bool = False, out_dtype=None, to_nchw: bool = False) -> Tensor:
+    """``(src - mean[c]) / scale[c]`` or, with ``inverse``, ``src * scale[c] + mean[c]`` over the last axis of the dense
+    ``src`` (``mean``, ``scale``: C fp64 device values); with ``to_nchw`` a 4-D (N, H, W, C) input comes out as a dense
+    (N, C, H, W) tensor.  A new tensor of ``out_dtype`` (default: the dtype of ``src``)."""
+    sdt = _filter_dtype(src, "channel_affine input")
+    out_dtype = src.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise L.GandanetError(f"channel_affine: expected float32 or float64 output, got {out_dtype}")
+    _chk(mean, "channel_affine mean", torch.float64)
+    _chk(scale, "channel_affine scale", torch.float64)
+    c = mean.numel()
+    if scale.numel() != c or not mean.is_contiguous() or not scale.is_contiguous():
+        raise L.GandanetError("channel_affine: mean and scale must be dense and of one length")
+    if c == 0 or src.numel() == 0 or src.numel() % c:
+        raise L.GandanetError(f"channel_affine: {tuple(src.shape)} is not a non-empty array of rows of {c} channels")
+    m = src.numel() // c
+    n = hw = 0
+    shape = src.shape
+    if to_nchw:
+        if src.dim() != 4 or src.shape[3] != c:
+            raise L.GandanetError(f"channel_affine: to_nchw needs an (N, H, W, {c}) tensor, got {tuple(src.shape)}")
+        n, hw = src.shape[0], src.shape[1] * src.shape[2]
+        shape = (src.shape[0], c, src.shape[1], src.shape[2])
+    dst = torch.empty(shape, device=src.device, dtype=out_dtype)
+    L.check(lib().gd_channel_affine(_ptr(src), sdt, _ptr(dst), int(out_dtype == torch.float64), m, c, _ptr(mean), _ptr(scale),
+                                    int(bool(inverse)), n, hw, _stream()), "gd_channel_affine")
+    return dst
+
+
+def freq_cos_table_host(n: int, k1: int):
+    """the (k1, n) fp64 numpy table cos(2 pi ((k t) mod n) / n) / n (plain C++ on the host, no GPU)"""
+    import numpy as np
+    if n <= 0 or k1 < 1:
+        raise L.GandanetError(f"freq_cos_table_host: L = {n}, K1 = {k1}")
+    coef = np.empty((k1, n))
+    L.check(lib().gd_freq_cos_table_host(int(n), int(k1), coef.ctypes.data_as(C.POINTER(C.c_double))), "gd_freq_cos_table_host")
+    return coef
+
+
+def freq_augment_axis(src: Tensor, dst: Tensor, axis: int, noise: Tensor, coef: Tensor) -> Tensor:
+    """``dst`` = ``src`` + the cosine sum of ``noise`` (the shape of src with K1 entries along ``axis``, fp64) weighted by
+    ``coef`` (K1, L) fp64 along ``axis``; ``dst`` may be a dense slab of a larger buffer.  No host sync."""
+    dt = _filter_dtype(src, "freq_augment src")
+    if _filter_dtype(dst, "freq_augment dst") != dt or dst.shape != src.shape:
+        raise L.GandanetError(f"freq_augment_axis: src {tuple(src.shape)} {src.dtype} vs dst {tuple(dst.shape)} {dst.dtype}")
+    _chk(noise, "freq_augment noise", torch.float64)
+    _chk(coef, "freq_augment table", torch.float64)
+    outer, n, inner = _axis_view(src, axis)
+    k1 = coef.shape[0] if coef.dim() == 2 else -1
+    want = tuple(src.shape[:axis]) + (k1,) + tuple(src.shape[axis + 1:])
+    if k1 < 1 or coef.shape[1] != n or not coef.is_contiguous() or tuple(noise.shape) != want or not noise.is_contiguous():
+        raise L.GandanetError(f"freq_augment_axis: table {tuple(coef.shape)} / noise {tuple(noise.shape)} for src "
+                              f"{tuple(src.shape)} along axis {axis}")
+    L.check(lib().gd_freq_augment_axis(_ptr(src), _ptr(dst), dt, outer, n, inner, _ptr(noise), k1, _ptr(coef), _stream()),
+            "gd_freq_augment_axis")
+    return dst

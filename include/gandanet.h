@@ -758,6 +758,48 @@ size_t gd_masked_plane_mean_f64_ws_bytes(long planes, long hw);
 int gd_masked_plane_mean_f64(const double* x, long planes, long hw, const unsigned char* mask, double* mean, long long* count,
                              void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dataset preparation (prepare.hip): the per-channel StandardScaler of datasets.py's load_data() (the
+ * `scaler.fit_transform(hr_aux[..., i].reshape(-1, 1))` loop over the last axis and the two single-feature GRACE scalers)
+ * and frequency_domain_augmentation() (datasets.py:318-347).  Storage fp32 (dtype 0) or fp64 (dtype 1), all arithmetic
+ * fp64, one rounding to the output type.  The caller owns all memory, nothing is allocated, nothing waits for the device;
+ * no atomics, every reduction in an order fixed by the shape: the same bits on every run.  Pointers need element
+ * alignment only.  STL (detrend_and_compare) is not here: the caller supplies trend and detrended arrays.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_FREQ_MAX_BINS 33                  /* K1 <= 33: seasonal_freq <= 32 */
+#define GD_FREQ_LDS_BYTES 32768              /* table columns one workgroup holds; a longer axis is cut into chunks */
+#define GD_FREQ_MAX_TABLE_BYTES (16L << 20)  /* the whole K1 x L table of doubles */
+/* x: a channel-last array seen as (M rows, C channels).  rec (device, C x 3 doubles): count, mean, M2 = sum (x - mean)^2 of
+ * every channel.  Pass one: workgroup b reduces the rows [b * R, (b + 1) * R) -- R a function of (M, C) alone -- reading
+ * them as one contiguous run of R * C elements (C <= 256; 256-channel column blocks beyond), each thread a compensated
+ * sum shifted by its first sample, the threads of a channel merged with Chan's formulas; pass two merges the workgroups'
+ * records in ascending order.  ws: gd_channel_moments_ws_bytes(M, C) bytes. */
+size_t gd_channel_moments_ws_bytes(long M, long C);
+int gd_channel_moments(const void* x, int dtype, long M, long C, double* rec, void* ws, size_t ws_bytes, void* stream);
+/* host only, no GPU call: sklearn's StandardScaler attributes from C records in HOST memory: mean_, var_ = M2 / count
+ * (ddof 0), scale_ = sqrt(var_), and scale_ = 1 where sklearn calls the feature constant (_is_constant_feature:
+ * var_ <= count * eps * var_ + (count * mean_ * eps)^2, eps = 2^-52). */
+int gd_scale_from_moments_host(const double* rec, long C, double* mean, double* var, double* scale);
+/* dst = (src - mean[c]) / scale[c] (inverse 0) or src * scale[c] + mean[c] (inverse 1), c the channel of the element: the
+ * two operations of sklearn in their order, each rounded in fp64 (no reciprocal, no FMA), then one rounding to dst_dtype.
+ * src (M, C) channel-last; mean_dev, scale_dev: C doubles in DEVICE memory.  N == 0: dst has the layout of src (16-byte
+ * accesses when src and dst both start on a 16-byte boundary, scalar otherwise).  N > 0: src is (N, HW, C) with
+ * N * HW == M and dst is (N, C, HW), `.permute(0, 3, 1, 2)` of CustomDataset in the same pass, as a tiled transpose
+ * through LDS.  src != dst. */
+int gd_channel_affine(const void* src, int src_dtype, void* dst, int dst_dtype, long M, long C, const double* mean_dev,
+                      const double* scale_dev, int inverse, long N, long HW, void* stream);
+/* host only, no GPU call: coef[k * L + t] = cos(2 pi ((k t) mod L) / L) / L for k < K1, t < L (K1 <= min(L, 33)). */
+int gd_freq_cos_table_host(long L, int K1, double* coef);
+/* frequency_domain_augmentation along one axis of a dense (outer, L, inner) tensor.  The reference adds REAL noise to the
+ * FFT bins 0 .. K1 - 1, K1 = min(seasonal_freq, L - 1) + 1, and keeps the real part of the inverse FFT; by linearity
+ *   dst[o, t, p] = src[o, t, p] + sum_{k < K1} noise[o, k, p] * coef[k, t]         (terms in ascending k, src added last).
+ * noise: (outer, K1, inner) doubles and coef: the table of gd_freq_cos_table_host, both in DEVICE memory.  dst may be a
+ * slab of a larger buffer; src != dst.  1 <= K1 <= min(L, GD_FREQ_MAX_BINS) and K1 * L * 8 <= GD_FREQ_MAX_TABLE_BYTES.
+ * Lanes along inner, a thread keeps its K1 noise values in registers and walks the axis; two series per lane when inner
+ * is even and src and dst start on 16-byte boundaries, one otherwise. */
+int gd_freq_augment_axis(const void* src, void* dst, int dtype, long outer, long L, long inner, const double* noise, int K1,
+                         const double* coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
