@@ -990,7 +990,11 @@ class MseFn(Function):
 
     @staticmethod
     def backward(ctx, g):
-        return _ScalarLoss._bwd(ctx, g), None
+        da = _ScalarLoss._bwd(ctx, g)
+        db = None
+        if ctx.needs_input_grad[1]:     # was None (= zero to autograd): caught by the MSE second-argument gradient test
+            db = K.axpby(da, -1.0, torch.empty_like(da), 0.0)
+        return da, db
 
 
 class L1Fn(Function):
