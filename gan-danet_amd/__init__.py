@@ -16,6 +16,7 @@ from .discriminator import SRGAND, Discriminator1
 from . import filters
 from . import spline
 from . import prepare
+from . import basins
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)

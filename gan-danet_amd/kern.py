@@ -1724,3 +1724,84 @@ def freq_augment_axis(src: Tensor, dst: Tensor, axis: int, noise: Tensor, coef: 
     L.check(lib().gd_freq_augment_axis(_ptr(src), _ptr(dst), dt, outer, n, inner, _ptr(noise), k1, _ptr(coef), _stream()),
             "gd_freq_augment_axis")
     return dst
+
+
+# ---- basin analysis (include/gandanet.h, "Basin analysis"; basins.hip) -------------------------------------------------------
+def _zone_edges_host(edges, offsets):
+    import numpy as np
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if edges.ndim != 2 or edges.shape[1] != 4 or offsets.ndim != 1 or offsets.size < 2:
+        raise L.GandanetError(f"zone edges: expected (E, 4) edges and Z + 1 offsets, got {edges.shape} and {offsets.shape}")
+    return edges, offsets
+
+
+def zone_rasterize(edges: Tensor, offsets, xs: Tensor, ys: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """(H, W) uint32 words, bit z set where the grid point (xs[j], ys[i]) lies in zone z: ``edges`` (E, 4) fp64 on the
+    device, ``offsets`` Z + 1 host integers (1 <= Z <= 32), ``xs`` (W) and ``ys`` (H) fp64 on the device.  Every word of
+    ``out`` is written.  No host sync."""
+    import numpy as np
+    for t, nm in ((edges, "zone edges"), (xs, "zone grid xs"), (ys, "zone grid ys")):
+        _chk(t, nm, torch.float64)
+        if not t.is_contiguous():
+            raise L.GandanetError(f"{nm}: expected a contiguous tensor, got strides {t.stride()}")
+    if edges.dim() != 2 or edges.shape[1] != 4 or xs.dim() != 1 or ys.dim() != 1:
+        raise L.GandanetError(f"zone_rasterize: edges {tuple(edges.shape)}, xs {tuple(xs.shape)}, ys {tuple(ys.shape)}")
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    h, w = ys.numel(), xs.numel()
+    if out is None:
+        out = torch.empty(h, w, device=xs.device, dtype=torch.uint32)
+    _chk(out, "zone bits", torch.uint32)
+    if tuple(out.shape) != (h, w) or not out.is_contiguous():
+        raise L.GandanetError(f"zone bits: expected a dense ({h}, {w}) tensor, got {tuple(out.shape)}")
+    L.check(lib().gd_zone_rasterize(_ptr(edges), edges.shape[0], off.ctypes.data_as(C.POINTER(C.c_long)), off.size - 1, _ptr(xs), w,
+                                    _ptr(ys), h, _ptr(out), _stream()), "gd_zone_rasterize")
+    return out
+
+
+def zone_rasterize_host(edges, offsets, xs, ys):
+    """``zone_rasterize`` on HOST arrays (plain C++ loops over the same predicate, no GPU): an (H, W) uint32 numpy array"""
+    import numpy as np
+    edges, off = _zone_edges_host(edges, offsets)
+    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1)
+    ys = np.ascontiguousarray(ys, dtype=np.float64).reshape(-1)
+    out = np.empty((ys.size, xs.size), dtype=np.uint32)
+    dp = C.POINTER(C.c_double)
+    L.check(lib().gd_zone_rasterize_host(edges.ctypes.data_as(dp), edges.shape[0], off.ctypes.data_as(C.POINTER(C.c_long)),
+                                         off.size - 1, xs.ctypes.data_as(dp), xs.size, ys.ctypes.data_as(dp), ys.size,
+                                         out.ctypes.data_as(C.POINTER(C.c_uint32))), "gd_zone_rasterize_host")
+    return out
+
+
+def zone_mean(x: Tensor, bits: Tensor, zones: int, weights: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """means of ``x`` over ``zones`` (<= 32) zones at once: ``bits`` (uint32, bit z = zone z) covers the trailing dims of
+    the dense fp32 / fp64 ``x`` and is shared by all leading planes; a pixel counts for zone z iff its bit is set and its
+    value is not NaN; ``weights`` (fp64, the shape of ``bits``) or None = 1.  Returns (mean fp64, count int64), both shaped
+    like the leading dims of ``x`` followed by ``zones``; a zone without a contributing pixel gives NaN and 0."""
+    dt = _eval_dtype(x, "zone_mean input")
+    _chk(bits, "zone bits", torch.uint32)
+    hw = bits.numel()
+    nd = x.dim() - bits.dim()
+    if hw == 0 or nd < 0 or tuple(x.shape[nd:]) != tuple(bits.shape) or not bits.is_contiguous():
+        raise L.GandanetError(f"zone_mean: bits {tuple(bits.shape)} do not cover the trailing dims of {tuple(x.shape)}")
+    if weights is not None:
+        _chk(weights, "zone weights", torch.float64)
+        if weights.shape != bits.shape or not weights.is_contiguous():
+            raise L.GandanetError(f"zone_mean: weights {tuple(weights.shape)} vs bits {tuple(bits.shape)}")
+    z = int(zones)
+    if not 1 <= z <= L.ZONE_MAX:
+        raise L.GandanetError(f"zone_mean: {z} zones, expected 1..{L.ZONE_MAX}")
+    lead = tuple(x.shape[:nd])
+    planes = math.prod(lead)
+    if planes == 0:
+        raise L.GandanetError("zone_mean: empty tensor")
+    mean = torch.empty(lead + (z,), device=x.device, dtype=torch.float64)
+    count = torch.empty(lead + (z,), device=x.device, dtype=torch.int64)
+    esz = x.element_size()
+    for lo in range(0, planes, 65535):                          # grid.y limit of one launch
+        k = min(65535, planes - lo)
+        nbytes = int(lib().gd_zone_mean_ws_bytes(k, hw, z))
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+        L.check(lib().gd_zone_mean(x.data_ptr() + esz * lo * hw, dt, k, hw, _ptr(bits), z, _ptr(weights), mean.data_ptr() + 8 * lo * z,
+                                   count.data_ptr() + 8 * lo * z, _ptr(ws), nbytes, _stream()), "gd_zone_mean")
+    return mean, count

@@ -800,6 +800,48 @@ int gd_freq_cos_table_host(long L, int K1, double* coef);
 int gd_freq_augment_axis(const void* src, void* dst, int dtype, long outer, long L, long inner, const double* noise, int K1,
                          const double* coef, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Basin analysis (basins.hip): the loop over the basins of Basin_TWSA_Comparison_GRACE_Downscaled.ipynb (cell 5), which
+ * rasterises every basin polygon on the 0.25 and the 0.05 degree grid and averages both products over it.
+ * The containment rule (csrc/zones.h; the device kernel, the host entry and the tests use this one rule): a zone is a set
+ * of rings -- the outer rings and the holes of all its parts, in any order and orientation -- stored as edges
+ * (x0, y0, x1, y1).  The point (px, py) is inside the zone iff an odd number of its edges satisfy both
+ *   (y0 > py) != (y1 > py)                          half-open: a horizontal edge never counts, a ray through a vertex
+ *                                                   counts once
+ *   px < x0 + (py - y0) * (x1 - x0) / (y1 - y0)     in fp64, every operation rounded on its own
+ * For a valid (Multi)Polygon that is shapely's `contains` at every point that is not on a boundary.  Points exactly on a
+ * boundary are unspecified (shapely calls them outside).
+ * The caller owns all memory, nothing is allocated, nothing waits for the device; no global atomics, every reduction in
+ * an order fixed by the shape: the same bits on every run.  Pointers need element alignment only.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_ZONE_MAX 32           /* zones per call: one bit of a word each */
+#define GD_ZONE_EDGE_CHUNK 512   /* edges of a zone the rasteriser takes per pass (the capacity of a row's crossing list) */
+/* `mask = np.array([polygon.contains(pt) for pt in points]).reshape(lat_grid.shape)` of cell 5, for Z polygons at once.
+ * edges: (E, 4) doubles in DEVICE memory, the edges of zone z at rows edge_off[z] .. edge_off[z + 1] - 1; edge_off: Z + 1
+ * longs in HOST memory, read before the launch: edge_off[0] == 0, never decreasing, edge_off[Z] == E (a zone may be
+ * empty).  1 <= Z <= GD_ZONE_MAX, 1 <= E <= 2^30.  The grid is rectilinear: point (i, j) is (xs[j], ys[i]), xs (W) and
+ * ys (H) doubles in DEVICE memory, not necessarily uniform, ascending or descending.  bits: (H, W) words, bit z set iff
+ * the point is in zone z; every word is written (no need to clear it first).
+ * A workgroup owns 4 rows x 1024 columns: per zone and per chunk of GD_ZONE_EDGE_CHUNK edges its threads test the edges
+ * against the 4 rows and append the crossings of the straddling ones to per-row lists in LDS; one wave per row then
+ * flips the zone's bit of every column with an odd number of crossings to its right.  O(E + W k) per row, k the
+ * crossings of the row, against O(E W) point by point. */
+int gd_zone_rasterize(const double* edges, long E, const long* edge_off, int Z, const double* xs, long W, const double* ys,
+                      long H, unsigned int* bits, void* stream);
+/* host only, no GPU call: the same arguments, all in HOST memory; plain loops over the predicate of csrc/zones.h */
+int gd_zone_rasterize_host(const double* edges, long E, const long* edge_off, int Z, const double* xs, long W,
+                           const double* ys, long H, unsigned int* bits);
+/* `np.nanmean(data[:, mask], axis=1)` of cell 5 for all Z zones in ONE pass over the data.  x: planes x hw elements, fp32
+ * (dtype 0) or fp64 (dtype 1); bits: hw words of gd_zone_rasterize shared by all planes; weights: hw doubles (for
+ * instance cos(lat)) or NULL = 1 everywhere, as in the notebook.  A pixel contributes to zone z iff bit z is set and the
+ * value is not NaN.  mean (planes, Z) = sum w v / sum w, count (planes, Z) = the contributing pixels; without a
+ * contributing pixel, or with a weight sum of zero, the mean is NaN and the count 0.  planes <= 65535 per call.
+ * ws: gd_zone_mean_ws_bytes(planes, hw, Z) bytes.  Each thread keeps the Z (8, 16 or 32 with the padding) triples
+ * (sum w v, sum w, count) in registers; per-workgroup partials go to ws and a second kernel adds them in ascending order. */
+size_t gd_zone_mean_ws_bytes(long planes, long hw, int Z);
+int gd_zone_mean(const void* x, int dtype, long planes, long hw, const unsigned int* bits, int Z, const double* weights,
+                 double* mean, long long* count, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
