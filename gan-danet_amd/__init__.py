@@ -17,6 +17,8 @@ from . import filters
 from . import spline
 from . import prepare
 from . import basins
+from . import stl
+from .stl import detrend_and_compare, stl_decompose
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)

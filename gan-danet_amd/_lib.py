@@ -23,6 +23,7 @@ FILTER_MAX_RADIUS, SAVGOL_MAX_WINDOW = 64, 33   # GD_FILTER_MAX_RADIUS, GD_SAVGO
 ZOOM_MIRROR, ZOOM_NEAREST = 0, 1   # GD_ZOOM_*
 FREQ_MAX_BINS, FREQ_MAX_TABLE_BYTES = 33, 16 << 20   # GD_FREQ_MAX_BINS, GD_FREQ_MAX_TABLE_BYTES
 ZONE_MAX, ZONE_EDGE_CHUNK = 32, 512   # GD_ZONE_MAX, GD_ZONE_EDGE_CHUNK
+STL_MAX_T = 2048                 # GD_STL_MAX_T
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -196,6 +197,8 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint32)]),
     "gd_zone_mean_ws_bytes": (_sz, [_l, _l, _i]),
     "gd_zone_mean": (_i, [_p, _i, _l, _l, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    "gd_stl_decompose": (_i, [_p, _i, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "gd_stl_decompose_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

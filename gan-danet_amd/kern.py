@@ -1805,3 +1805,36 @@ def zone_mean(x: Tensor, bits: Tensor, zones: int, weights: Optional[Tensor] = N
         L.check(lib().gd_zone_mean(x.data_ptr() + esz * lo * hw, dt, k, hw, _ptr(bits), z, _ptr(weights), mean.data_ptr() + 8 * lo * z,
                                    count.data_ptr() + 8 * lo * z, _ptr(ws), nbytes, _stream()), "gd_zone_mean")
     return mean, count
+
+
+# ---- STL decomposition (include/gandanet.h, "STL decomposition"; stl.hip) ------------------------------------------------------
+def _stl_args(p: dict):
+    return [int(p[k]) for k in ("period", "seasonal", "trend", "low_pass", "seasonal_deg", "trend_deg", "low_pass_deg", "inner_iter",
+                                "outer_iter")]
+
+
+def stl_decompose(x: Tensor, p: dict, want_weights: bool = True):
+    """STL of the M series of a dense fp32 / fp64 ``x`` (T, M), series m at ``x[:, m]``; ``p`` holds period, seasonal, trend,
+    low_pass, the three degrees, inner_iter and outer_iter.  New tensors (trend, seasonal, resid, weights or None) shaped
+    like ``x``.  No host sync."""
+    dt = _filter_dtype(x, "stl_decompose input")
+    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise L.GandanetError(f"stl_decompose: expected a dense, non-empty (T, M) tensor, got {tuple(x.shape)} with strides {x.stride()}")
+    outs = [torch.empty_like(x) for _ in range(4 if want_weights else 3)]
+    L.check(lib().gd_stl_decompose(_ptr(x), dt, x.shape[0], x.shape[1], *_stl_args(p), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                   _ptr(outs[3]) if want_weights else None, _stream()), "gd_stl_decompose")
+    return outs[0], outs[1], outs[2], outs[3] if want_weights else None
+
+
+def stl_decompose_host(x, p: dict):
+    """``stl_decompose`` on a HOST array (T, M), fp32 or fp64 (plain C++ loops over the same arithmetic, no GPU): numpy
+    arrays (trend, seasonal, resid, weights)"""
+    import numpy as np
+    x = np.asarray(x)
+    if x.dtype not in (np.float32, np.float64) or x.ndim != 2 or x.size == 0:
+        raise L.GandanetError(f"stl_decompose_host: expected a non-empty float32 / float64 (T, M) array, got {x.dtype} {x.shape}")
+    x = np.ascontiguousarray(x)
+    outs = [np.empty_like(x) for _ in range(4)]
+    L.check(lib().gd_stl_decompose_host(x.ctypes.data, L.FILTER_F64 if x.dtype == np.float64 else L.FILTER_F32, x.shape[0], x.shape[1],
+                                        *_stl_args(p), *[o.ctypes.data for o in outs]), "gd_stl_decompose_host")
+    return tuple(outs)

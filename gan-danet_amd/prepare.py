@@ -12,9 +12,10 @@
 The kernels are ``csrc/prepare.hip``: fp32 or fp64 CUDA tensors, all arithmetic fp64, one rounding to the output type, no
 atomics (the same bits on every run).  There is no CPU path.
 
-Out of scope: the STL decomposition (``detrend_and_compare``).  It needs ``statsmodels``, and the reference's
-``cache/dataset_cache.npz`` holds no recorded trend a device version could be checked against, so none is written here:
-the caller supplies the trend and detrended arrays, as ``test.ipynb`` does from the cache.
+The STL decomposition that ends ``load_data()`` (``detrend_and_compare``) is ``gan_danet_amd.stl``: its trend and
+detrended arrays are what ``augment_dataset`` takes.  It follows the published algorithm and is held to closed-form cases
+and an independent fp64 oracle; agreement with statsmodels itself is unverified (statsmodels is not available, and the
+reference's ``cache/dataset_cache.npz`` holds no recorded trend).
 """
 from __future__ import annotations
 

@@ -764,7 +764,7 @@ int gd_masked_plane_mean_f64(const double* x, long planes, long hw, const unsign
  * and frequency_domain_augmentation() (datasets.py:318-347).  Storage fp32 (dtype 0) or fp64 (dtype 1), all arithmetic
  * fp64, one rounding to the output type.  The caller owns all memory, nothing is allocated, nothing waits for the device;
  * no atomics, every reduction in an order fixed by the shape: the same bits on every run.  Pointers need element
- * alignment only.  STL (detrend_and_compare) is not here: the caller supplies trend and detrended arrays.
+ * alignment only.  STL (detrend_and_compare) has its own section below.
  * ---------------------------------------------------------------------------------------- */
 #define GD_FREQ_MAX_BINS 33                  /* K1 <= 33: seasonal_freq <= 32 */
 #define GD_FREQ_LDS_BYTES 32768              /* table columns one workgroup holds; a longer axis is cut into chunks */
@@ -841,6 +841,51 @@ int gd_zone_rasterize_host(const double* edges, long E, const long* edge_off, in
 size_t gd_zone_mean_ws_bytes(long planes, long hw, int Z);
 int gd_zone_mean(const void* x, int dtype, long planes, long hw, const unsigned int* bits, int Z, const double* weights,
                  double* mean, long long* count, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * STL decomposition (stl.hip, csrc/stl_core.h): `detrend_and_compare` of datasets.py, which calls statsmodels'
+ * `STL(y, seasonal=13, period=12).fit()` once per grid point, for all M series of a (T, M) array in one launch.
+ * The algorithm is Cleveland et al. 1990 as netlib's stl.f computes it, with every jump 1.  Positions 1-based.
+ *   est(y, n, len, deg, xs, nleft, nright, userw, rw): h = max(xs - nleft, nright - xs), plus (len - n) / 2 (integer) when
+ *     len > n; for j = nleft .. nright, r = |j - xs|: w_j = 0 beyond 0.999 h, 1 up to 0.001 h, (1 - (r / h)^3)^3 between, times
+ *     rw_j under userw; a = sum w_j, not ok when a <= 0; w_j /= a; with h > 0 and deg > 0: a = sum w_j j, b = xs - a,
+ *     c = sum w_j (j - a)^2, and if sqrt(c) > 0.001 (n - 1): w_j *= (b / c) (j - a) + 1; ys = sum w_j y_j.
+ *   ess(y, n, len, deg): ys = y when n < 2; the window is [1, n] when len >= n, else it starts at [1, len] and moves right by
+ *     one for every position beyond (len + 1) / 2 until it touches n; ys_i = y_i where est is not ok.
+ *   One inner pass, from trend (0 at first): w = y - trend; every cycle-subseries j = 1 .. period of w (length
+ *     k = (n - j) / period + 1) is smoothed by ess(k, seasonal, seasonal_deg) and extended by est at positions 0 (window
+ *     [1, min(seasonal, k)]) and k + 1 (window [max(1, k - seasonal + 1), k]), each falling back on the neighbouring
+ *     smoothed value, giving C (n + 2 period); L = ess(n, low_pass, low_pass_deg) of the moving averages of lengths period,
+ *     period and 3 of C; seasonal_i = C_(period + i) - L_i; trend = ess(n, trend, trend_deg) of y - seasonal.
+ *   outer_iter + 1 outer passes of inner_iter inner passes each; after every outer pass but the last the robustness
+ *     weights are renewed: r_i = |y_i - trend_i - seasonal_i|, cmad = 3 (r_(m1) + r_(m2)) over the ascending order
+ *     statistics m1 = n / 2 + 1, m2 = n - m1 + 1; rw_i = 1 up to 0.001 cmad, (1 - (r_i / cmad)^2)^2 up to 0.999 cmad, 0 beyond;
+ *     every est from then on runs under userw (the low-pass one never does).  resid = y - seasonal - trend.
+ * Storage fp32 (dtype 0) or fp64 (dtype 1), all arithmetic fp64 with every operation rounded on its own, one rounding to
+ * the output type.  The moving averages are window sums per output (stl.f keeps a running sum): the one place where the
+ * order of additions differs.  The caller owns all memory, nothing is allocated on the device, nothing waits for it; no
+ * global atomics, no workspace; a series' result depends on the series and the parameters alone, not on M, its column or
+ * the launch.  Pointers need element alignment only.  A series that holds a non-finite value has unspecified outputs.
+ * Agreement with statsmodels itself has NOT been measured (it is not available here): it rests on this text, on closed-form
+ * cases and on an independent fp64 restatement in the tests.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_STL_MAX_T 2048 /* one series' working arrays, (6 T + 6 period + 2) doubles, must fit the 160 KiB LDS of a CU */
+/* x, trend_out, seasonal_out, resid_out, weights_out (NULL = not wanted; all ones when outer_iter == 0): (T, M) arrays in
+ * DEVICE memory, series m at x[t * M + m] (the reference's (time, x, y) layout flattened); no output may alias x or another
+ * output.  period >= 2; seasonal, trend, low_pass odd and >= 3; trend > period; low_pass > period; degrees 0 or 1;
+ * inner_iter >= 1; outer_iter >= 0; 2 * period <= T <= GD_STL_MAX_T.  statsmodels' defaults are trend = the smallest odd
+ * integer >= 1.5 period / (1 - 1.5 / seasonal), low_pass = the smallest odd integer > period, inner_iter 5 and outer_iter 0,
+ * or 2 and 15 with robust=True; they are the caller's to fill in.
+ * A workgroup of 256 threads owns S neighbouring series, S = 40960 / the bytes of one series' working arrays, within
+ * 1 .. 16 (4 at T = 181, period 12), held in LDS as [t][S] images; the threads share out the (series, output point) pairs
+ * of every smoothing pass, and the order statistics of cmad are found by counting ranks in LDS. */
+int gd_stl_decompose(const void* x, int dtype, long T, long M, int period, int seasonal, int trend, int low_pass, int seasonal_deg,
+                     int trend_deg, int low_pass_deg, int inner_iter, int outer_iter, void* trend_out, void* seasonal_out,
+                     void* resid_out, void* weights_out, void* stream);
+/* host only, no GPU call: the same arguments, all in HOST memory; the same fit (csrc/stl_core.h) in plain loops */
+int gd_stl_decompose_host(const void* x, int dtype, long T, long M, int period, int seasonal, int trend, int low_pass,
+                          int seasonal_deg, int trend_deg, int low_pass_deg, int inner_iter, int outer_iter, void* trend_out,
+                          void* seasonal_out, void* resid_out, void* weights_out);
 
 #ifdef __cplusplus
 }
