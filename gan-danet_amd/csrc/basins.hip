@@ -4,9 +4,9 @@
 // `np.nanmean(data[:, mask], axis=1)` per basin by one pass over the product for all zones.  The containment rule is
 // zones.h, shared with the host twin gd_zone_rasterize_host.  No global atomics; every reduction runs in an order fixed
 // by the shape, so the same input gives the same bits.  All index arithmetic on the grid is 64-bit.
-#include "common.h"
+// From elem_util.h: gd_head_of, gd_vec16, gd_plane_gx, gd_dtype_ok, gd_elem_aligned, gd_aligned, GD_S.
+#include "elem_util.h"
 #include "zones.h"
-#include "../../include/gandanet.h"
 
 #include <math.h>
 
@@ -89,27 +89,6 @@ __global__ __launch_bounds__(ZN_THREADS) void zone_rasterize_kernel(const double
 }
 
 // ---- zonal means -----------------------------------------------------------------------------------------------------------
-template <typename T> __host__ __device__ inline long head_of(const T* p) {
-    const unsigned long mis = (unsigned long)(uintptr_t)p & 15ul;
-    return mis ? (long)((16ul - mis) / sizeof(T)) : 0;
-}
-
-template <typename T> struct Vec16;   // the elements of one 16-byte load
-template <> struct Vec16<float> {
-    static constexpr int N = 4;
-    __device__ static void load(const float* p, double* o) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-    }
-};
-template <> struct Vec16<double> {
-    static constexpr int N = 2;
-    __device__ static void load(const double* p, double* o) {
-        const double2 v = *reinterpret_cast<const double2*>(p);
-        o[0] = v.x; o[1] = v.y;
-    }
-};
-
 // one pixel into the ZM accumulator triples of a thread: the zone loop is unrolled and every update is a select, so the
 // arrays are indexed by constants only and stay in registers
 template <int ZM, bool WT>
@@ -132,11 +111,11 @@ __device__ __forceinline__ void zone_acc(double (&s)[ZM], double (&sw)[WT ? ZM :
 template <typename T, int ZM, bool WT>
 __global__ __launch_bounds__(ZN_THREADS) void zone_sum_kernel(const T* __restrict__ x, long hw, const unsigned int* __restrict__ bits,
                                                               const double* __restrict__ wts, int Z, double* __restrict__ ws) {
-    constexpr int VW = Vec16<T>::N;
+    constexpr int VW = gd_vec16<T>::W;
     __shared__ double red[ZN_THREADS / GD_WAVE][ZM * 3];
     const int tid = threadIdx.x;
     const T* p = x + (long)blockIdx.y * hw;
-    long head = head_of(p);
+    long head = gd_head_of(p);
     if (head > hw) head = hw;             // a plane shorter than its head: all of it is 'rest'
     const long nv = (hw - head) / VW;
     double s[ZM], sw[WT ? ZM : 1];
@@ -151,7 +130,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zone_sum_kernel(const T* __restric
     for (long v = (long)blockIdx.x * ZN_THREADS + tid; v < nv; v += (long)gridDim.x * ZN_THREADS) {
         const long i = head + v * VW;
         double e[VW];
-        Vec16<T>::load(p + i, e);
+        gd_vec16<T>::load(p + i, e);
 #pragma unroll
         for (int j = 0; j < VW; ++j) zone_acc<ZM, WT>(s, sw, c, e[j], bits[i + j], WT ? wts[i + j] : 1.0);
     }
@@ -203,13 +182,7 @@ __global__ void zone_mean_final_kernel(const double* __restrict__ ws, int gx, lo
 }
 
 // workgroups per plane: a function of the shape alone (the partials' order is part of the result)
-static int zone_gx(long planes, long hw) {
-    long gx = (hw + ZN_THREADS * 8 - 1) / (ZN_THREADS * 8);
-    long cap = 2048 / planes;            // about 2048 workgroups over all planes fill the chip
-    cap = cap < 1 ? 1 : cap;
-    gx = gx > cap ? cap : gx;
-    return (int)(gx < 1 ? 1 : (gx > 64 ? 64 : gx));
-}
+static int zone_gx(long planes, long hw) { return gd_plane_gx(planes, hw, ZN_THREADS * 8); }
 
 template <typename T, int ZM>
 static void zone_sum_launch(const T* x, long planes, long hw, const unsigned int* bits, const double* wts, int Z, double* ws, int gx,
@@ -238,8 +211,6 @@ static bool offsets_ok(const long* off, int Z, long E) {
 
 }  // namespace
 
-#define GD_S ((hipStream_t)stream)
-#define ZN_ALIGNED(p, n) (((uintptr_t)(p) % (n)) == 0)
 // the checks gd_zone_rasterize and its host twin share
 #define ZN_RASTER_CHECKS(fn)                                                                                              \
     GD_CHECK_ARG(edges && edge_off && xs && ys && bits, fn ": null pointer");                                           \
@@ -247,7 +218,7 @@ static bool offsets_ok(const long* off, int Z, long E) {
     GD_CHECK_ARG(E > 0 && W > 0 && H > 0, fn ": E <= 0, W <= 0 or H <= 0");                                               \
     GD_CHECK_ARG(E <= (1L << 30), fn ": more than 2^30 edges");                                                          \
     GD_CHECK_ARG(offsets_ok(edge_off, Z, E), fn ": offsets must start at 0, never decrease and end at E");               \
-    GD_CHECK_ARG(ZN_ALIGNED(edges, 8) && ZN_ALIGNED(xs, 8) && ZN_ALIGNED(ys, 8) && ZN_ALIGNED(bits, 4),                   \
+    GD_CHECK_ARG(gd_aligned(edges, 8) && gd_aligned(xs, 8) && gd_aligned(ys, 8) && gd_aligned(bits, 4),                   \
                  fn ": pointer not element aligned")
 
 extern "C" int gd_zone_rasterize(const double* edges, long E, const long* edge_off, int Z, const double* xs, long W, const double* ys,
@@ -297,14 +268,14 @@ extern "C" size_t gd_zone_mean_ws_bytes(long planes, long hw, int Z) {
 extern "C" int gd_zone_mean(const void* x, int dtype, long planes, long hw, const unsigned int* bits, int Z, const double* weights,
                             double* mean, long long* count, void* ws, size_t ws_bytes, void* stream) {
     GD_CHECK_ARG(x && bits && mean && count && ws, "gd_zone_mean: null pointer");
-    GD_CHECK_ARG(dtype == GD_FILTER_F32 || dtype == GD_FILTER_F64, "gd_zone_mean: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_zone_mean: dtype outside {0, 1}");
     GD_CHECK_ARG(Z >= 1 && Z <= GD_ZONE_MAX, "gd_zone_mean: Z outside 1..32");
     GD_CHECK_ARG(planes > 0 && hw > 0, "gd_zone_mean: planes <= 0 or hw <= 0");
     GD_CHECK_ARG(planes <= 65535, "gd_zone_mean: more than 65535 planes in one call");
     GD_CHECK_ARG(hw < (1L << 53) / planes, "gd_zone_mean: tensor too large");
     GD_CHECK_ARG(ws_bytes >= gd_zone_mean_ws_bytes(planes, hw, Z), "gd_zone_mean: workspace smaller than gd_zone_mean_ws_bytes");
-    GD_CHECK_ARG(ZN_ALIGNED(x, dtype ? 8 : 4) && ZN_ALIGNED(bits, 4) && ZN_ALIGNED(weights, 8) && ZN_ALIGNED(mean, 8) &&
-                     ZN_ALIGNED(count, 8) && ZN_ALIGNED(ws, 8),
+    GD_CHECK_ARG(gd_elem_aligned(x, dtype) && gd_aligned(bits, 4) && gd_aligned(weights, 8) && gd_aligned(mean, 8) &&
+                     gd_aligned(count, 8) && gd_aligned(ws, 8),
                  "gd_zone_mean: pointer not element aligned");
     const int gx = zone_gx(planes, hw);
     if (dtype == GD_FILTER_F64) zone_sum_dispatch((const double*)x, planes, hw, bits, weights, Z, (double*)ws, gx, GD_S);

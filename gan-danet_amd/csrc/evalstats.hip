@@ -4,10 +4,13 @@
 // are only element aligned (channel and batch slices).  Reductions are two-stage in a fixed order (no atomics), in fp64,
 // as co-moments: a thread shifts its sums by the first valid pair it meets (norm.hip does the same for BatchNorm), and
 // everything above a thread is merged with Chan's pairwise formulas -- raw sums of squares are never formed.
-#include "common.h"
-#include "../../include/gandanet.h"
+// From elem_util.h: gd_head_of, gd_vec16, gd_plane_gx, gd_block_sum_d, gd_shfl_down_d, gd_aligned, gd_elem_aligned,
+// GD_S.
+#include "elem_util.h"
 
 #include <math.h>
+
+#include <string>
 
 namespace {
 
@@ -39,21 +42,19 @@ __host__ __device__ inline Rec rec_merge(const Rec& a, const Rec& b) {
 
 __host__ __device__ inline Rec rec_zero() { return Rec{0, 0, 0, 0, 0, 0, 0, 0}; }
 
-__device__ __forceinline__ double shfl_down_d(double v, int o) { return __shfl_down(v, o, 64); }
-
 // lane l ends with the merge of lanes l .. 63 in ascending order along a fixed tree; lane 0 holds the wave's record
 __device__ __forceinline__ Rec rec_wave_merge(Rec r) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         Rec b;
-        b.n = shfl_down_d(r.n, o);
-        b.mp = shfl_down_d(r.mp, o);
-        b.mt = shfl_down_d(r.mt, o);
-        b.m2p = shfl_down_d(r.m2p, o);
-        b.m2t = shfl_down_d(r.m2t, o);
-        b.c = shfl_down_d(r.c, o);
-        b.sae = shfl_down_d(r.sae, o);
-        b.sse = shfl_down_d(r.sse, o);
+        b.n = gd_shfl_down_d(r.n, o);
+        b.mp = gd_shfl_down_d(r.mp, o);
+        b.mt = gd_shfl_down_d(r.mt, o);
+        b.m2p = gd_shfl_down_d(r.m2p, o);
+        b.m2t = gd_shfl_down_d(r.m2t, o);
+        b.c = gd_shfl_down_d(r.c, o);
+        b.sae = gd_shfl_down_d(r.sae, o);
+        b.sse = gd_shfl_down_d(r.sse, o);
         if (((threadIdx.x & 63) & (2 * o - 1)) == 0) r = rec_merge(r, b);   // lanes that own a block of 2*o lanes
     }
     return r;
@@ -111,19 +112,6 @@ __device__ __forceinline__ Rec acc_finish(const Acc& A) {
     return r;
 }
 
-template <typename T> struct Vec;
-template <> struct Vec<float> { typedef float4 type; static constexpr int W = 4; };
-template <> struct Vec<double> { typedef double2 type; static constexpr int W = 2; };
-__device__ __forceinline__ void unpack(const float4& v, double* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-__device__ __forceinline__ void unpack(const double2& v, double* o) { o[0] = v.x; o[1] = v.y; }
-__device__ __forceinline__ void unpack(const float4& v, float* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-
-// elements of T from `p` up to the next 16-byte boundary (p is element aligned)
-template <typename T> __host__ __device__ inline long head_of(const T* p) {
-    const unsigned long mis = (unsigned long)(uintptr_t)p & 15ul;
-    return mis ? (long)((16ul - mis) / sizeof(T)) : 0;
-}
-
 // Stage 1.  grid (gx, gy): block (bx, by) takes the planes by, by + gy, ... and of each plane the 16-byte vectors
 // bx * 256 + tid, + gx * 256, ...; block bx == 0 also takes the plane's unaligned head and its tail.  Without a mask the
 // host passes the whole tensor as ONE plane.  One partial record per block at ws[by * gx + bx].
@@ -132,8 +120,8 @@ __global__ __launch_bounds__(EV_THREADS) void eval_stats_kernel(const T* __restr
                                                                 long planes, long hw,
                                                                 const unsigned char* __restrict__ mask, double a, double b,
                                                                 double* __restrict__ ws) {
-    typedef typename Vec<T>::type V;
-    constexpr int W = Vec<T>::W;
+    typedef typename gd_vec16<T>::type V;
+    constexpr int W = gd_vec16<T>::W;
     __shared__ double red[EV_THREADS / 64][8];
     Acc A;
     A.sp = A.st = A.s1p = A.s1t = A.s2p = A.s2t = A.spt = A.sae = A.sse = 0.0;
@@ -143,8 +131,8 @@ __global__ __launch_bounds__(EV_THREADS) void eval_stats_kernel(const T* __restr
     for (long pl = blockIdx.y; pl < planes; pl += gridDim.y) {
         const T* p = pred + pl * hw;
         const T* t = truth + pl * hw;
-        const long head = head_of(p);
-        if (head != head_of(t) || head > hw) {   // the two pointers never meet a 16-byte boundary together: scalar sweep
+        const long head = gd_head_of(p);
+        if (head != gd_head_of(t) || head > hw) {   // the two pointers never meet a 16-byte boundary together: scalar sweep
             for (long i = (long)blockIdx.x * EV_THREADS + tid; i < hw; i += (long)gridDim.x * EV_THREADS) {
                 const bool valid = MASK ? mask[i] != 0 : true;
                 acc_add<AFF, SKIPNAN>(A, (double)p[i], (double)t[i], valid, a, b);
@@ -157,8 +145,8 @@ __global__ __launch_bounds__(EV_THREADS) void eval_stats_kernel(const T* __restr
         for (long v = (long)blockIdx.x * EV_THREADS + tid; v < nv; v += (long)gridDim.x * EV_THREADS) {
             const V pv = p4[v], tv = t4[v];
             double pe[W], te[W];
-            unpack(pv, pe);
-            unpack(tv, te);
+            gd_vec16<T>::unpack(pv, pe);
+            gd_vec16<T>::unpack(tv, te);
 #pragma unroll
             for (int j = 0; j < W; ++j) {
                 const bool valid = MASK ? mask[head + v * W + j] != 0 : true;
@@ -208,103 +196,50 @@ static EvGrid eval_grid(long planes, long hw) {
 }
 
 // ---- masked plane means -------------------------------------------------------------------------------------------
-// grid (gx, planes): partial (sum, count) of the valid pixels of one plane per block, ws[(plane * gx + bx) * 2]
-__global__ __launch_bounds__(EV_THREADS) void plane_sum_kernel(const float* __restrict__ x, long hw,
+// grid (gx, planes): partial (sum, count) of the valid pixels of one plane per block, ws[(plane * gx + bx) * 2].  16-byte
+// loads from the plane's first 16-byte boundary; block 0 also takes the elements in front of it and behind the last whole
+// load.  SKIPNAN: a NaN pixel counts as invalid (gd_masked_plane_mean_f64); without it a NaN at a valid pixel makes the
+// plane's sum NaN (gd_masked_plane_mean).
+template <typename T, bool SKIPNAN>
+__global__ __launch_bounds__(EV_THREADS) void plane_sum_kernel(const T* __restrict__ x, long hw,
                                                                const unsigned char* __restrict__ mask,
                                                                double* __restrict__ ws) {
+    constexpr int W = gd_vec16<T>::W;
     __shared__ double red[EV_THREADS / 64][2];
     const int tid = threadIdx.x;
-    const float* p = x + (long)blockIdx.y * hw;
-    long head = head_of(p);
+    const T* p = x + (long)blockIdx.y * hw;
+    long head = gd_head_of(p);
     if (head > hw) head = hw;             // a plane shorter than its head: all of it is 'rest'
-    const long nv = (hw - head) / 4;
-    const float4* p4 = reinterpret_cast<const float4*>(p + head);
+    const long nv = (hw - head) / W;
     double s = 0.0;
     unsigned int cnt = 0;
     for (long v = (long)blockIdx.x * EV_THREADS + tid; v < nv; v += (long)gridDim.x * EV_THREADS) {
-        const float4 q = p4[v];
-        const float e[4] = {q.x, q.y, q.z, q.w};
+        T e[W];
+        gd_vec16<T>::load(p + head + v * W, e);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool valid = mask ? mask[head + v * 4 + j] != 0 : true;
+        for (int j = 0; j < W; ++j) {
+            bool valid = mask ? mask[head + v * W + j] != 0 : true;
+            if (SKIPNAN) valid = valid && e[j] == e[j];
             s += valid ? (double)e[j] : 0.0;
             cnt += valid ? 1u : 0u;
         }
     }
     if (blockIdx.x == 0) {
-        const long body_end = head + nv * 4, rest = hw - nv * 4;
+        const long body_end = head + nv * W, rest = hw - nv * W;
         for (long r = tid; r < rest; r += EV_THREADS) {
             const long i = r < head ? r : body_end + (r - head);
-            const bool valid = mask ? mask[i] != 0 : true;
+            bool valid = mask ? mask[i] != 0 : true;
+            if (SKIPNAN) valid = valid && p[i] == p[i];
             s += valid ? (double)p[i] : 0.0;
             cnt += valid ? 1u : 0u;
         }
     }
-    s = gd_wave_sum_d(s);
-    double c = gd_wave_sum_d((double)cnt);
-    if ((tid & 63) == 0) {
-        red[tid >> 6][0] = s;
-        red[tid >> 6][1] = c;
-    }
-    __syncthreads();
+    double sc[2] = {s, (double)cnt};
+    gd_block_sum_d<2, EV_THREADS / 64>(sc, red);
     if (tid == 0) {
-        for (int w = 1; w < EV_THREADS / 64; ++w) {
-            s += red[w][0];
-            c += red[w][1];
-        }
         double* o = ws + 2 * ((long)blockIdx.y * gridDim.x + blockIdx.x);
-        o[0] = s;
-        o[1] = c;
-    }
-}
-// the same partials of an fp64 plane (gd_masked_plane_mean_f64), a NaN pixel counting as invalid: 16-byte loads of two
-// doubles from the first 16-byte boundary
-__global__ __launch_bounds__(EV_THREADS) void plane_sum_f64_kernel(const double* __restrict__ x, long hw,
-                                                                   const unsigned char* __restrict__ mask,
-                                                                   double* __restrict__ ws) {
-    __shared__ double red[EV_THREADS / 64][2];
-    const int tid = threadIdx.x;
-    const double* p = x + (long)blockIdx.y * hw;
-    long head = head_of(p);
-    if (head > hw) head = hw;
-    const long nv = (hw - head) / 2;
-    const double2* p2 = reinterpret_cast<const double2*>(p + head);
-    double s = 0.0;
-    unsigned int cnt = 0;
-    for (long v = (long)blockIdx.x * EV_THREADS + tid; v < nv; v += (long)gridDim.x * EV_THREADS) {
-        const double2 q = p2[v];
-        const double e[2] = {q.x, q.y};
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const bool valid = (mask ? mask[head + v * 2 + j] != 0 : true) && e[j] == e[j];
-            s += valid ? e[j] : 0.0;
-            cnt += valid ? 1u : 0u;
-        }
-    }
-    if (blockIdx.x == 0) {
-        const long body_end = head + nv * 2, rest = hw - nv * 2;
-        for (long r = tid; r < rest; r += EV_THREADS) {
-            const long i = r < head ? r : body_end + (r - head);
-            const bool valid = (mask ? mask[i] != 0 : true) && p[i] == p[i];
-            s += valid ? p[i] : 0.0;
-            cnt += valid ? 1u : 0u;
-        }
-    }
-    s = gd_wave_sum_d(s);
-    double c = gd_wave_sum_d((double)cnt);
-    if ((tid & 63) == 0) {
-        red[tid >> 6][0] = s;
-        red[tid >> 6][1] = c;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < EV_THREADS / 64; ++w) {
-            s += red[w][0];
-            c += red[w][1];
-        }
-        double* o = ws + 2 * ((long)blockIdx.y * gridDim.x + blockIdx.x);
-        o[0] = s;
-        o[1] = c;
+        o[0] = sc[0];
+        o[1] = sc[1];
     }
 }
 // one thread per plane adds the plane's gx partials in ascending order; no valid pixel -> NaN (np.nanmean)
@@ -320,12 +255,29 @@ __global__ void plane_mean_final_kernel(const double* __restrict__ ws, int gx, l
     mean[pl] = c > 0 ? s / c : (double)NAN;
     count[pl] = (long long)c;
 }
-static int plane_gx(long planes, long hw) {
-    long gx = (hw + EV_THREADS * 4 - 1) / (EV_THREADS * 4);
-    long cap = 2048 / planes;            // about 2048 blocks over all planes fill the chip
-    cap = cap < 1 ? 1 : cap;
-    gx = gx > cap ? cap : gx;
-    return (int)(gx < 1 ? 1 : (gx > 64 ? 64 : gx));
+static int plane_gx(long planes, long hw) { return gd_plane_gx(planes, hw, EV_THREADS * 4); }
+
+// the two exported plane means: `fn` is the entry's name, for its messages
+template <typename T>
+static int plane_mean_launch(const char* fn, const T* x, long planes, long hw, const unsigned char* mask, double* mean,
+                             long long* count, void* ws, size_t ws_bytes, hipStream_t st) {
+    const std::string f(fn);
+#define PM_CHECK(cond, what) GD_CHECK_ARG(cond, (f + what).c_str())
+    PM_CHECK(x && mean && count && ws, ": null pointer");
+    PM_CHECK(planes > 0 && hw > 0, ": n <= 0");
+    PM_CHECK(planes <= 65535, ": more than 65535 planes in one call");
+    PM_CHECK(ws_bytes >= gd_masked_plane_mean_ws_bytes(planes, hw), ": workspace smaller than " + f + "_ws_bytes");
+    PM_CHECK(gd_aligned(x, sizeof(T)) && gd_aligned(mean, 8) && gd_aligned(count, 8) && gd_aligned(ws, 8),
+             ": pointer not element aligned");
+#undef PM_CHECK
+    const int gx = plane_gx(planes, hw);
+    // SKIPNAN with the dtype: the fp64 entry leaves NaN pixels out, the fp32 entry does not
+    hipLaunchKernelGGL((plane_sum_kernel<T, sizeof(T) == 8>), dim3(gx, (unsigned)planes), dim3(EV_THREADS), 0, st, x, hw, mask,
+                       (double*)ws);
+    hipLaunchKernelGGL(plane_mean_final_kernel, dim3(gd_cdiv(planes, 256)), dim3(256), 0, st, (const double*)ws, gx, planes,
+                       mean, count);
+    GD_LAUNCH_CHECK();
+    return 0;
 }
 
 // ---- statistics over the member axis ----------------------------------------------------------------------------------
@@ -339,7 +291,6 @@ template <typename T, int MMAX, int VW>
 __global__ __launch_bounds__(EV_THREADS) void ensemble_stats_kernel(const T* __restrict__ x, int M, long mstride, long items,
                                                                     long skip_from, long skip_len, T* __restrict__ mean,
                                                                     T* __restrict__ sd) {
-    typedef typename Vec<T>::type V;
     const double inv = 1.0 / (double)M;
     for (long it = (long)blockIdx.x * EV_THREADS + threadIdx.x; it < items; it += (long)gridDim.x * EV_THREADS) {
         const long e = (it < skip_from ? it : it + skip_len) * VW;
@@ -348,7 +299,7 @@ __global__ __launch_bounds__(EV_THREADS) void ensemble_stats_kernel(const T* __r
         for (int m = 0; m < MMAX; ++m) {
             if (m < M) {
                 if constexpr (VW > 1) {
-                    unpack(*reinterpret_cast<const V*>(x + (long)m * mstride + e), v[m]);
+                    gd_vec16<T>::load(x + (long)m * mstride + e, v[m]);
                 } else {
                     v[m][0] = x[(long)m * mstride + e];
                 }
@@ -371,12 +322,9 @@ __global__ __launch_bounds__(EV_THREADS) void ensemble_stats_kernel(const T* __r
                 }
             sq[j] = sqrt(q * inv);
         }
-        if constexpr (VW == 4) {
-            *reinterpret_cast<float4*>(mean + e) = make_float4((float)mu[0], (float)mu[1], (float)mu[2], (float)mu[3]);
-            *reinterpret_cast<float4*>(sd + e) = make_float4((float)sq[0], (float)sq[1], (float)sq[2], (float)sq[3]);
-        } else if constexpr (VW == 2) {
-            *reinterpret_cast<double2*>(mean + e) = make_double2(mu[0], mu[1]);
-            *reinterpret_cast<double2*>(sd + e) = make_double2(sq[0], sq[1]);
+        if constexpr (VW > 1) {
+            gd_vec16<T>::store(mean + e, mu);
+            gd_vec16<T>::store(sd + e, sq);
         } else {
             mean[e] = (T)mu[0];
             sd[e] = (T)sq[0];
@@ -391,7 +339,7 @@ static int ens_grid(long items) {
 
 template <typename T, int MMAX>
 static void ensemble_launch_m(const T* x, int M, long mstride, long n, long head, long nv, T* mean, T* sd, hipStream_t s) {
-    constexpr int VW = Vec<T>::W;
+    constexpr int VW = gd_vec16<T>::W;
     if (nv > 0)
         hipLaunchKernelGGL((ensemble_stats_kernel<T, MMAX, VW>), dim3(ens_grid(nv)), dim3(EV_THREADS), 0, s, x + head, M,
                            mstride, nv, nv, 0L, mean + head, sd + head);
@@ -405,9 +353,9 @@ template <typename T>
 static void ensemble_launch(const T* x, int M, long mstride, long n, T* mean, T* sd, hipStream_t s) {
     // 16-byte path: every member row, and both outputs, reach a 16-byte boundary after the same `head` elements (a
     // single member has no stride to satisfy); otherwise every element goes through the scalar instance
-    long head = head_of(x), nv = 0;
-    const bool same = head == head_of(mean) && head == head_of(sd) && (M == 1 || (mstride * (long)sizeof(T)) % 16 == 0);
-    if (same && head <= n) nv = (n - head) / Vec<T>::W;
+    long head = gd_head_of(x), nv = 0;
+    const bool same = head == gd_head_of(mean) && head == gd_head_of(sd) && (M == 1 || (mstride * (long)sizeof(T)) % 16 == 0);
+    if (same && head <= n) nv = (n - head) / gd_vec16<T>::W;
     else head = 0;
     if (M <= 8) ensemble_launch_m<T, 8>(x, M, mstride, n, head, nv, mean, sd, s);
     else ensemble_launch_m<T, 32>(x, M, mstride, n, head, nv, mean, sd, s);
@@ -429,8 +377,6 @@ static void eval_launch(const T* pred, const T* truth, long planes, long hw, con
 
 }  // namespace
 
-#define GD_S ((hipStream_t)stream)
-
 extern "C" size_t gd_eval_stats_ws_bytes(long n) {
     if (n <= 0) return 0;
     // the partial count depends on how the planes are cut; EV_BLOCKS records cover every cut
@@ -444,9 +390,9 @@ extern "C" int gd_eval_stats(const void* pred, const void* truth, long planes, l
     GD_CHECK_ARG((flags & ~(GD_EVAL_F64 | GD_EVAL_SKIP_NAN)) == 0, "gd_eval_stats: unknown flag");
     GD_CHECK_ARG(a == a && b == b, "gd_eval_stats: the affine is NaN");
     GD_CHECK_ARG(ws_bytes >= gd_eval_stats_ws_bytes(planes * hw), "gd_eval_stats: workspace smaller than gd_eval_stats_ws_bytes");
-    const size_t esz = (flags & GD_EVAL_F64) ? 8 : 4;
-    GD_CHECK_ARG(((uintptr_t)pred % esz) == 0 && ((uintptr_t)truth % esz) == 0 && ((uintptr_t)rec % 8) == 0 &&
-                     ((uintptr_t)ws % 8) == 0, "gd_eval_stats: pointer not element aligned");
+    const int f64 = flags & GD_EVAL_F64;
+    GD_CHECK_ARG(gd_elem_aligned(pred, f64) && gd_elem_aligned(truth, f64) && gd_aligned(rec, 8) && gd_aligned(ws, 8),
+                 "gd_eval_stats: pointer not element aligned");
     if (!mask) {   // nothing repeats per plane: one plane of n elements
         hw *= planes;
         planes = 1;
@@ -472,36 +418,14 @@ extern "C" size_t gd_masked_plane_mean_ws_bytes(long planes, long hw) {
 
 extern "C" int gd_masked_plane_mean(const float* x, long planes, long hw, const unsigned char* mask, double* mean,
                                     long long* count, void* ws, size_t ws_bytes, void* stream) {
-    GD_CHECK_ARG(x && mean && count && ws, "gd_masked_plane_mean: null pointer");
-    GD_CHECK_ARG(planes > 0 && hw > 0, "gd_masked_plane_mean: n <= 0");
-    GD_CHECK_ARG(planes <= 65535, "gd_masked_plane_mean: more than 65535 planes in one call");
-    GD_CHECK_ARG(ws_bytes >= gd_masked_plane_mean_ws_bytes(planes, hw), "gd_masked_plane_mean: workspace smaller than gd_masked_plane_mean_ws_bytes");
-    GD_CHECK_ARG(((uintptr_t)x % 4) == 0 && ((uintptr_t)mean % 8) == 0 && ((uintptr_t)count % 8) == 0 && ((uintptr_t)ws % 8) == 0,
-                 "gd_masked_plane_mean: pointer not element aligned");
-    const int gx = plane_gx(planes, hw);
-    hipLaunchKernelGGL(plane_sum_kernel, dim3(gx, (unsigned)planes), dim3(EV_THREADS), 0, GD_S, x, hw, mask, (double*)ws);
-    hipLaunchKernelGGL(plane_mean_final_kernel, dim3(gd_cdiv(planes, 256)), dim3(256), 0, GD_S, (const double*)ws, gx, planes,
-                       mean, count);
-    GD_LAUNCH_CHECK();
-    return 0;
+    return plane_mean_launch("gd_masked_plane_mean", x, planes, hw, mask, mean, count, ws, ws_bytes, GD_S);
 }
 
 extern "C" size_t gd_masked_plane_mean_f64_ws_bytes(long planes, long hw) { return gd_masked_plane_mean_ws_bytes(planes, hw); }
 
 extern "C" int gd_masked_plane_mean_f64(const double* x, long planes, long hw, const unsigned char* mask, double* mean,
                                         long long* count, void* ws, size_t ws_bytes, void* stream) {
-    GD_CHECK_ARG(x && mean && count && ws, "gd_masked_plane_mean_f64: null pointer");
-    GD_CHECK_ARG(planes > 0 && hw > 0, "gd_masked_plane_mean_f64: n <= 0");
-    GD_CHECK_ARG(planes <= 65535, "gd_masked_plane_mean_f64: more than 65535 planes in one call");
-    GD_CHECK_ARG(ws_bytes >= gd_masked_plane_mean_f64_ws_bytes(planes, hw), "gd_masked_plane_mean_f64: workspace smaller than gd_masked_plane_mean_f64_ws_bytes");
-    GD_CHECK_ARG(((uintptr_t)x % 8) == 0 && ((uintptr_t)mean % 8) == 0 && ((uintptr_t)count % 8) == 0 && ((uintptr_t)ws % 8) == 0,
-                 "gd_masked_plane_mean_f64: pointer not element aligned");
-    const int gx = plane_gx(planes, hw);
-    hipLaunchKernelGGL(plane_sum_f64_kernel, dim3(gx, (unsigned)planes), dim3(EV_THREADS), 0, GD_S, x, hw, mask, (double*)ws);
-    hipLaunchKernelGGL(plane_mean_final_kernel, dim3(gd_cdiv(planes, 256)), dim3(256), 0, GD_S, (const double*)ws, gx, planes,
-                       mean, count);
-    GD_LAUNCH_CHECK();
-    return 0;
+    return plane_mean_launch("gd_masked_plane_mean_f64", x, planes, hw, mask, mean, count, ws, ws_bytes, GD_S);
 }
 
 extern "C" int gd_ensemble_stats(const void* x, int M, long member_stride, long n, int f64, void* mean, void* std_out,
@@ -510,8 +434,7 @@ extern "C" int gd_ensemble_stats(const void* x, int M, long member_stride, long 
     GD_CHECK_ARG(n > 0, "gd_ensemble_stats: n <= 0");
     GD_CHECK_ARG(M >= 1 && M <= 32, "gd_ensemble_stats: M outside 1..32");
     GD_CHECK_ARG(M == 1 || member_stride >= n, "gd_ensemble_stats: member stride smaller than n");
-    const size_t esz = f64 ? 8 : 4;
-    GD_CHECK_ARG(((uintptr_t)x % esz) == 0 && ((uintptr_t)mean % esz) == 0 && ((uintptr_t)std_out % esz) == 0,
+    GD_CHECK_ARG(gd_elem_aligned(x, f64) && gd_elem_aligned(mean, f64) && gd_elem_aligned(std_out, f64),
                  "gd_ensemble_stats: pointer not element aligned");
     if (f64) ensemble_launch<double>((const double*)x, M, member_stride, n, (double*)mean, (double*)std_out, GD_S);
     else ensemble_launch<float>((const float*)x, M, member_stride, n, (float*)mean, (float*)std_out, GD_S);

@@ -3,8 +3,8 @@
 // rank filter of median_filter over a small box, and the pointwise head and tail of the normalised-convolution gap fill.
 // A dense tensor is seen as (outer, L, inner) around the filtered axis.  Storage fp32 or fp64; every sum is fp64 and is
 // rounded to the storage type once per pass, as scipy's correlate1d does.  No atomics; all index arithmetic is 64-bit.
-#include "common.h"
-#include "../../include/gandanet.h"
+// From elem_util.h: gd_vec16, gd_head_of, gd_stream_grid, gd_dtype_ok, gd_elem_aligned, gd_aligned, GD_S.
+#include "elem_util.h"
 
 #include <math.h>
 
@@ -18,18 +18,6 @@ constexpr int FT_MAXW = 2 * GD_FILTER_MAX_RADIUS + 1;
 struct CorrW {
     double w[FT_MAXW];
 };
-
-template <typename T> struct Vec;
-template <> struct Vec<float> { typedef float4 type; static constexpr int W = 4; };
-template <> struct Vec<double> { typedef double2 type; static constexpr int W = 2; };
-__device__ __forceinline__ void unpack(const float4& v, float* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-__device__ __forceinline__ void unpack(const double2& v, double* o) { o[0] = v.x; o[1] = v.y; }
-
-// elements of T from `p` up to the next 16-byte boundary (p is element aligned)
-template <typename T> static inline long head_of(const T* p) {
-    const unsigned long mis = (unsigned long)(uintptr_t)p & 15ul;
-    return mis ? (long)((16ul - mis) / sizeof(T)) : 0;
-}
 
 // scipy's 'reflect' (half-sample symmetric: d c b a | a b c d | d c b a) for ANY q: the extension has period 2L, so the
 // rule holds when the radius is several times L, and L == 1 maps everything to 0
@@ -59,7 +47,6 @@ __global__ __launch_bounds__(64 * CORR_TY) void corr_inner_kernel(const T* __res
                                                                   long inner, long c0, long nitems, long skip_from,
                                                                   long skip_len, long o0, long lb0, long cb0, CorrW W,
                                                                   int radius, int edge) {
-    typedef typename Vec<T>::type V;
     const long it = (cb0 + blockIdx.y) * 64 + threadIdx.x;
     const long l0 = ((lb0 + blockIdx.x) * CORR_TY + threadIdx.y) * CORR_LR;
     if (it >= nitems || l0 >= L) return;
@@ -81,7 +68,7 @@ __global__ __launch_bounds__(64 * CORR_TY) void corr_inner_kernel(const T* __res
         }
         T v[VW];
         if constexpr (VW > 1) {
-            unpack(*reinterpret_cast<const V*>(s + q * inner), v);
+            gd_vec16<T>::load(s + q * inner, v);
         } else {
             v[0] = s[q * inner];
         }
@@ -99,11 +86,8 @@ __global__ __launch_bounds__(64 * CORR_TY) void corr_inner_kernel(const T* __res
     for (int j = 0; j < CORR_LR; ++j) {
         const long l = l0 + j;
         if (l >= L || (edge == GD_EDGE_INTERIOR && (l < radius || l >= L - radius))) continue;
-        if constexpr (VW == 4) {
-            *reinterpret_cast<float4*>(d + l * inner) =
-                make_float4((float)acc[j][0], (float)acc[j][1], (float)acc[j][2], (float)acc[j][3]);
-        } else if constexpr (VW == 2) {
-            *reinterpret_cast<double2*>(d + l * inner) = make_double2(acc[j][0], acc[j][1]);
+        if constexpr (VW > 1) {
+            gd_vec16<T>::store(d + l * inner, acc[j]);
         } else {
             d[l * inner] = (T)acc[j][0];
         }
@@ -122,8 +106,8 @@ constexpr int ROW_PER = ROW_SEG / FT_THREADS;
 template <typename T>
 __global__ __launch_bounds__(FT_THREADS) void corr_row_kernel(const T* __restrict__ src, T* __restrict__ dst, long L, long o0,
                                                               long sb0, CorrW W, int radius, int edge) {
-    typedef typename Vec<T>::type V;
-    constexpr int VW = Vec<T>::W;
+    typedef typename gd_vec16<T>::type V;
+    constexpr int VW = gd_vec16<T>::W;
     __shared__ __attribute__((aligned(16))) T tile[ROW_SEG + 2 * GD_FILTER_MAX_RADIUS];
     const int tid = threadIdx.x;
     const long row = o0 + blockIdx.x, seg0 = (sb0 + blockIdx.y) * ROW_SEG;
@@ -176,11 +160,11 @@ static void corr_launch(const T* src, T* dst, long outer, long L, long inner, co
             }
         return;
     }
-    constexpr int VW = Vec<T>::W;
+    constexpr int VW = gd_vec16<T>::W;
     // 16-byte path: the row stride is a whole number of vectors and both tensors reach a 16-byte boundary after the same
     // `head` columns; the scalar instance takes the head and the tail, or everything
-    long head = head_of(src), nv = 0;
-    if (inner % VW == 0 && head == head_of(dst) && head <= inner) nv = (inner - head) / VW;
+    long head = gd_head_of(src), nv = 0;
+    if (inner % VW == 0 && head == gd_head_of(dst) && head <= inner) nv = (inner - head) / VW;
     else head = 0;
     const long rest = inner - nv * VW;
     const long lblocks = (L + CORR_TY * CORR_LR - 1) / (CORR_TY * CORR_LR);
@@ -300,10 +284,7 @@ __global__ __launch_bounds__(FT_THREADS) void median_kernel(const T* __restrict_
     }
 }
 
-static int stream_grid(long n) {
-    long g = (n + FT_THREADS - 1) / FT_THREADS;
-    return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
-}
+static int stream_grid(long n) { return gd_stream_grid(n, FT_THREADS, 65536); }
 
 template <typename T>
 static bool median_launch(const T* src, T* dst, const long* n, const int* s, int count, hipStream_t st) {
@@ -353,8 +334,6 @@ __global__ __launch_bounds__(FT_THREADS) void fill_ratio_kernel(const T* __restr
     }
 }
 
-static bool elem_aligned(const void* p, int dtype) { return ((uintptr_t)p % (dtype ? 8 : 4)) == 0; }
-
 // np.sum's pairwise order for n < 8, and for 8 <= n <= 128 its eight running sums: the normalisation of the Gaussian
 // taps then rounds as scipy's `phi_x / phi_x.sum()` does
 static double pairwise_sum(const double* a, int n) {
@@ -380,8 +359,6 @@ static double pairwise_sum(const double* a, int n) {
 
 }  // namespace
 
-#define GD_S ((hipStream_t)stream)
-
 // Host only.  scipy.ndimage._filters._gaussian_kernel1d at order 0.
 extern "C" int gd_gaussian_weights_host(double sigma, double truncate, double* w, int cap) {
     GD_CHECK_ARG(w, "gd_gaussian_weights_host: null pointer");
@@ -400,12 +377,12 @@ extern "C" int gd_correlate1d_axis(const void* src, void* dst, int dtype, long o
                                    int radius, int edge_mode, void* stream) {
     GD_CHECK_ARG(src && dst && w_host, "gd_correlate1d_axis: null pointer");
     GD_CHECK_ARG(src != dst, "gd_correlate1d_axis: src == dst (the filter is not in place)");
-    GD_CHECK_ARG(dtype == GD_FILTER_F32 || dtype == GD_FILTER_F64, "gd_correlate1d_axis: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_correlate1d_axis: dtype outside {0, 1}");
     GD_CHECK_ARG(L > 0 && outer > 0 && inner > 0, "gd_correlate1d_axis: L <= 0 (or outer, inner <= 0)");
     GD_CHECK_ARG(radius >= 0 && radius <= GD_FILTER_MAX_RADIUS, "gd_correlate1d_axis: radius outside 0..64");
     GD_CHECK_ARG(inner < (1L << 32), "gd_correlate1d_axis: inner >= 2^32 (split the trailing dimensions)");
     GD_CHECK_ARG(edge_mode == GD_EDGE_REFLECT || edge_mode == GD_EDGE_INTERIOR, "gd_correlate1d_axis: unknown edge mode");
-    GD_CHECK_ARG(elem_aligned(src, dtype) && elem_aligned(dst, dtype), "gd_correlate1d_axis: pointer not element aligned");
+    GD_CHECK_ARG(gd_elem_aligned(src, dtype) && gd_elem_aligned(dst, dtype), "gd_correlate1d_axis: pointer not element aligned");
     CorrW W;
     for (int k = 0; k < FT_MAXW; ++k) W.w[k] = k <= 2 * radius ? w_host[k] : 0.0;
     if (dtype == GD_FILTER_F64) corr_launch<double>((const double*)src, (double*)dst, outer, L, inner, W, radius, edge_mode, GD_S);
@@ -418,11 +395,11 @@ extern "C" int gd_savgol_edges_axis(const void* src, void* dst, int dtype, long 
                                     const double* edge_dev, int window, void* stream) {
     GD_CHECK_ARG(src && dst && edge_dev, "gd_savgol_edges_axis: null pointer");
     GD_CHECK_ARG(src != dst, "gd_savgol_edges_axis: src == dst");
-    GD_CHECK_ARG(dtype == GD_FILTER_F32 || dtype == GD_FILTER_F64, "gd_savgol_edges_axis: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_savgol_edges_axis: dtype outside {0, 1}");
     GD_CHECK_ARG(L > 0 && outer > 0 && inner > 0, "gd_savgol_edges_axis: L <= 0 (or outer, inner <= 0)");
     GD_CHECK_ARG(window >= 1 && (window & 1) && window <= GD_SAVGOL_MAX_WINDOW, "gd_savgol_edges_axis: window must be odd and <= 33");
     GD_CHECK_ARG(window <= L, "gd_savgol_edges_axis: window longer than the axis");
-    GD_CHECK_ARG(elem_aligned(src, dtype) && elem_aligned(dst, dtype) && ((uintptr_t)edge_dev % 8) == 0,
+    GD_CHECK_ARG(gd_elem_aligned(src, dtype) && gd_elem_aligned(dst, dtype) && gd_aligned(edge_dev, 8),
                  "gd_savgol_edges_axis: pointer not element aligned");
     if (window == 1) return 0;
     const int g = stream_grid(outer * 2 * (window / 2) * inner);
@@ -439,7 +416,7 @@ extern "C" int gd_savgol_edges_axis(const void* src, void* dst, int dtype, long 
 extern "C" int gd_median_nd(const void* src, void* dst, int dtype, const int64_t* shape4, const int* size4, void* stream) {
     GD_CHECK_ARG(src && dst && shape4 && size4, "gd_median_nd: null pointer");
     GD_CHECK_ARG(src != dst, "gd_median_nd: src == dst");
-    GD_CHECK_ARG(dtype == GD_FILTER_F32 || dtype == GD_FILTER_F64, "gd_median_nd: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_median_nd: dtype outside {0, 1}");
     long n[4];
     int count = 1;
     for (int a = 0; a < 4; ++a) {
@@ -450,7 +427,7 @@ extern "C" int gd_median_nd(const void* src, void* dst, int dtype, const int64_t
     }
     GD_CHECK_ARG(count == 3 || count == 5 || count == 9 || count == 25 || count == 27 || count == 81,
                  "gd_median_nd: window count outside {3, 5, 9, 25, 27, 81}");
-    GD_CHECK_ARG(elem_aligned(src, dtype) && elem_aligned(dst, dtype), "gd_median_nd: pointer not element aligned");
+    GD_CHECK_ARG(gd_elem_aligned(src, dtype) && gd_elem_aligned(dst, dtype), "gd_median_nd: pointer not element aligned");
     const bool ok = dtype == GD_FILTER_F64 ? median_launch<double>((const double*)src, (double*)dst, n, size4, count, GD_S)
                                            : median_launch<float>((const float*)src, (float*)dst, n, size4, count, GD_S);
     GD_CHECK_ARG(ok, "gd_median_nd: window count outside {3, 5, 9, 25, 27, 81}");
@@ -461,9 +438,9 @@ extern "C" int gd_median_nd(const void* src, void* dst, int dtype, const int64_t
 extern "C" int gd_fill_prepare(const void* x, double placeholder, void* vals, void* mask, int dtype, long n, void* stream) {
     GD_CHECK_ARG(x && vals && mask, "gd_fill_prepare: null pointer");
     GD_CHECK_ARG(x != vals && x != mask && vals != mask, "gd_fill_prepare: x, vals and mask must be three buffers");
-    GD_CHECK_ARG(dtype == GD_FILTER_F32 || dtype == GD_FILTER_F64, "gd_fill_prepare: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_fill_prepare: dtype outside {0, 1}");
     GD_CHECK_ARG(n > 0, "gd_fill_prepare: n <= 0");
-    GD_CHECK_ARG(elem_aligned(x, dtype) && elem_aligned(vals, dtype) && elem_aligned(mask, dtype),
+    GD_CHECK_ARG(gd_elem_aligned(x, dtype) && gd_elem_aligned(vals, dtype) && gd_elem_aligned(mask, dtype),
                  "gd_fill_prepare: pointer not element aligned");
     if (dtype == GD_FILTER_F64)
         hipLaunchKernelGGL((fill_prepare_kernel<double>), dim3(stream_grid(n)), dim3(FT_THREADS), 0, GD_S, (const double*)x,
@@ -479,9 +456,9 @@ extern "C" int gd_fill_ratio(const void* x, const void* num, const void* den, do
                              void* stream) {
     GD_CHECK_ARG(x && num && den && dst, "gd_fill_ratio: null pointer");
     GD_CHECK_ARG(dst != x && dst != num && dst != den, "gd_fill_ratio: dst must be a buffer of its own");
-    GD_CHECK_ARG(dtype == GD_FILTER_F32 || dtype == GD_FILTER_F64, "gd_fill_ratio: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_fill_ratio: dtype outside {0, 1}");
     GD_CHECK_ARG(n > 0, "gd_fill_ratio: n <= 0");
-    GD_CHECK_ARG(elem_aligned(x, dtype) && elem_aligned(num, dtype) && elem_aligned(den, dtype) && elem_aligned(dst, dtype),
+    GD_CHECK_ARG(gd_elem_aligned(x, dtype) && gd_elem_aligned(num, dtype) && gd_elem_aligned(den, dtype) && gd_elem_aligned(dst, dtype),
                  "gd_fill_ratio: pointer not element aligned");
     if (dtype == GD_FILTER_F64)
         hipLaunchKernelGGL((fill_ratio_kernel<double>), dim3(stream_grid(n)), dim3(FT_THREADS), 0, GD_S, (const double*)x,

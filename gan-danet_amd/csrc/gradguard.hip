@@ -3,9 +3,8 @@
 // whether a step was applied until it asks.  All HBM-bound: the norm reads every gradient once with 16-byte loads where
 // the pointer allows it (scalar head / tail otherwise, as in evalstats.hip), the update moves the 28 bytes per element of
 // adamw_kernel (pointwise.hip) plus 8 when an averaged copy of the weights (EMA) rides along.  Reductions are two-stage in
-// a fixed order, in fp64, without atomics.
-#include "common.h"
-#include "../../include/gandanet.h"
+// a fixed order, in fp64, without atomics.  From elem_util.h: gd_head_of, gd_block_sum_d, gd_aligned, GD_S.
+#include "elem_util.h"
 
 #include <math.h>
 
@@ -24,12 +23,6 @@ struct NormArgs {
     int count;
 };
 
-// elements from `p` up to the next 16-byte boundary (p is element aligned)
-__host__ __device__ inline long head_of(const float* p) {
-    const unsigned long mis = (unsigned long)(uintptr_t)p & 15ul;
-    return mis ? (long)((16ul - mis) / sizeof(float)) : 0;
-}
-
 __device__ __forceinline__ double sq4(const float4& q, double acc) {
     acc = fma((double)q.x, (double)q.x, acc);
     acc = fma((double)q.y, (double)q.y, acc);
@@ -40,7 +33,7 @@ __device__ __forceinline__ double sq4(const float4& q, double acc) {
 // Stage 1.  Block b of the launch owns chunk (b - first[t]) of tensor t: elements [c * GG_CHUNK, min(n, (c + 1) * GG_CHUNK)).
 // Its partial sum of squares, times gscale^2, goes to ws[slot0 + b]: the slot is fixed by (tensor, chunk of tensor) alone.
 __global__ __launch_bounds__(GG_THREADS) void grad_sqnorm_kernel(const NormArgs a, double gscale2, double* __restrict__ ws) {
-    __shared__ double red[GG_THREADS / 64];
+    __shared__ double red[GG_THREADS / 64][1];
     const int b = blockIdx.x, tid = threadIdx.x;
     int t = 0;
     while (t + 1 < a.count && b >= a.first[t + 1]) ++t;   // uniform over the block
@@ -48,7 +41,7 @@ __global__ __launch_bounds__(GG_THREADS) void grad_sqnorm_kernel(const NormArgs 
     long len = a.n[t] - lo;
     len = len > GG_CHUNK ? GG_CHUNK : len;
     const float* p = a.ptr[t] + lo;
-    long head = head_of(p);
+    long head = gd_head_of(p);
     head = head > len ? len : head;
     const long nv = (len - head) / 4;
     const float4* p4 = reinterpret_cast<const float4*>(p + head);
@@ -68,13 +61,9 @@ __global__ __launch_bounds__(GG_THREADS) void grad_sqnorm_kernel(const NormArgs 
         const double e = (double)p[tid < head ? tid : body_end + (tid - head)];
         s1 = fma(e, e, s1);
     }
-    double s = gd_wave_sum_d((s0 + s1) + (s2 + s3));
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < GG_THREADS / 64; ++w) s += red[w];
-        ws[b] = s * gscale2;
-    }
+    double s[1] = {(s0 + s1) + (s2 + s3)};
+    gd_block_sum_d<1, GG_THREADS / 64>(s, red);
+    if (tid == 0) ws[b] = s[0] * gscale2;
 }
 
 // Stage 2 (one block): thread i adds its contiguous run of slots in ascending order, then the threads are added in
@@ -184,8 +173,6 @@ static long chunks_of(long n) { return (n + GG_CHUNK - 1) / GG_CHUNK; }
 
 }  // namespace
 
-#define GD_S ((hipStream_t)stream)
-
 extern "C" size_t gd_grad_sqnorm_ws_bytes(long total_chunks) {
     return total_chunks > 0 ? (size_t)total_chunks * sizeof(double) : 0;
 }
@@ -194,12 +181,12 @@ extern "C" int gd_grad_sqnorm(const float* const* grads, const long* ns, int cou
                               void* ws, size_t ws_bytes, void* stream) {
     GD_CHECK_ARG(grads && ns && rec && ws, "gd_grad_sqnorm: null pointer");
     GD_CHECK_ARG(count > 0, "gd_grad_sqnorm: n <= 0 (empty tensor list)");
-    GD_CHECK_ARG(((uintptr_t)rec % 8) == 0 && ((uintptr_t)ws % 8) == 0, "gd_grad_sqnorm: record or workspace not 8-byte aligned");
+    GD_CHECK_ARG(gd_aligned(rec, 8) && gd_aligned(ws, 8), "gd_grad_sqnorm: record or workspace not 8-byte aligned");
     long total = 0;
     for (int t = 0; t < count; ++t) {
         GD_CHECK_ARG(grads[t], "gd_grad_sqnorm: null pointer in the tensor list");
         GD_CHECK_ARG(ns[t] > 0, "gd_grad_sqnorm: n <= 0 in the tensor list");
-        GD_CHECK_ARG(((uintptr_t)grads[t] % 4) == 0, "gd_grad_sqnorm: pointer not element aligned");
+        GD_CHECK_ARG(gd_aligned(grads[t], 4), "gd_grad_sqnorm: pointer not element aligned");
         // one launch's grid is an int: a tensor of more than 2^31 - 1 chunks (1.4e14 elements) does not fit one
         GD_CHECK_ARG(chunks_of(ns[t]) <= 0x7fffffffL, "gd_grad_sqnorm: tensor longer than 2^31 - 1 chunks");
         total += chunks_of(ns[t]);
@@ -237,7 +224,7 @@ extern "C" int gd_grad_sqnorm(const float* const* grads, const long* ns, int cou
 
 extern "C" int gd_guard_finalize(double* rec, double max_norm, int skip_nonfinite, void* stream) {
     GD_CHECK_ARG(rec, "gd_guard_finalize: null pointer");
-    GD_CHECK_ARG(((uintptr_t)rec % 8) == 0, "gd_guard_finalize: record not 8-byte aligned");
+    GD_CHECK_ARG(gd_aligned(rec, 8), "gd_guard_finalize: record not 8-byte aligned");
     GD_CHECK_ARG(max_norm == max_norm, "gd_guard_finalize: max_norm is NaN");
     hipLaunchKernelGGL(guard_finalize_kernel, dim3(1), dim3(64), 0, GD_S, rec, max_norm, skip_nonfinite);
     GD_LAUNCH_CHECK();
@@ -249,11 +236,11 @@ extern "C" int gd_adamw_guarded(float* p, const float* g, float* m, float* v, fl
                                 void* stream) {
     GD_CHECK_ARG(p && g && m && v && rec, "gd_adamw_guarded: null pointer");
     GD_CHECK_ARG(n > 0, "gd_adamw_guarded: n <= 0");
-    GD_CHECK_ARG(((uintptr_t)p % 4) == 0 && ((uintptr_t)g % 4) == 0 && ((uintptr_t)m % 4) == 0 && ((uintptr_t)v % 4) == 0 &&
-                     ((uintptr_t)ema % 4) == 0 && ((uintptr_t)rec % 8) == 0, "gd_adamw_guarded: pointer not element aligned");
+    GD_CHECK_ARG(gd_aligned(p, 4) && gd_aligned(g, 4) && gd_aligned(m, 4) && gd_aligned(v, 4) &&
+                     gd_aligned(ema, 4) && gd_aligned(rec, 8), "gd_adamw_guarded: pointer not element aligned");
     GD_CHECK_ARG(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), "gd_adamw_guarded: ema_decay outside [0, 1]");
-    long head = head_of(p), nv = 0;
-    const bool same = head == head_of(g) && head == head_of(m) && head == head_of(v) && (!ema || head == head_of(ema));
+    long head = gd_head_of(p), nv = 0;
+    const bool same = head == gd_head_of(g) && head == gd_head_of(m) && head == gd_head_of(v) && (!ema || head == gd_head_of(ema));
     if (same && head <= n) nv = (n - head) / 4;
     else head = 0;
     long grid = (nv + (n - nv * 4) + GG_THREADS - 1) / GG_THREADS;   // one vector or one scalar element per thread ...

@@ -3,8 +3,8 @@
 // (N, C, H, W) layout -- and frequency_domain_augmentation() restated as a cosine sum along one axis.  Storage fp32 or
 // fp64; all arithmetic fp64 with one rounding to the output type.  No atomics: every reduction runs in a fixed order that
 // depends on the shape alone, so the same input gives the same bits.  All index arithmetic is 64-bit.
-#include "common.h"
-#include "../../include/gandanet.h"
+// From elem_util.h: gd_vec16, gd_shfl_down_d, gd_stream_grid, gd_dtype_ok, gd_elem_aligned, gd_aligned, GD_S.
+#include "elem_util.h"
 
 #include <math.h>
 
@@ -114,8 +114,6 @@ __global__ __launch_bounds__(PR_THREADS) void moments_partial_kernel(const T* __
     }
 }
 
-__device__ __forceinline__ double shfl_down_d(double v, int o) { return __shfl_down(v, o, 64); }
-
 // Pass two: one wave per channel.  Lane l merges its contiguous run of partial records in block order, then the lanes are
 // merged in ascending order along a fixed tree (evalstats.hip, stage 2).
 __global__ __launch_bounds__(64) void moments_merge_kernel(const double* __restrict__ part, long nblocks, long C, long cb0,
@@ -132,9 +130,9 @@ __global__ __launch_bounds__(64) void moments_merge_kernel(const double* __restr
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         Mom b;
-        b.n = shfl_down_d(r.n, o);
-        b.mean = shfl_down_d(r.mean, o);
-        b.m2 = shfl_down_d(r.m2, o);
+        b.n = gd_shfl_down_d(r.n, o);
+        b.mean = gd_shfl_down_d(r.mean, o);
+        b.m2 = gd_shfl_down_d(r.m2, o);
         if ((lane & (2 * o - 1)) == 0) r = mom_merge(r, b);
     }
     if (lane == 0) {
@@ -156,26 +154,15 @@ __device__ __forceinline__ double affine(double x, double mean, double scale, in
     return d / scale;
 }
 
-template <typename T> struct Vec4;   // four consecutive elements
-template <> struct Vec4<float> {
-    __device__ static void load(const float* p, double* o) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-    }
-    __device__ static void store(float* p, const double* o) {
-        *reinterpret_cast<float4*>(p) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
-    }
-};
-template <> struct Vec4<double> {
-    __device__ static void load(const double* p, double* o) {
-        const double2 a = *reinterpret_cast<const double2*>(p), b = *reinterpret_cast<const double2*>(p + 2);
-        o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
-    }
-    __device__ static void store(double* p, const double* o) {
-        *reinterpret_cast<double2*>(p) = make_double2(o[0], o[1]);
-        *reinterpret_cast<double2*>(p + 2) = make_double2(o[2], o[3]);
-    }
-};
+// four consecutive elements: one 16-byte access of fp32, two of fp64
+template <typename T> __device__ __forceinline__ void load4(const T* p, double* o) {
+#pragma unroll
+    for (int k = 0; k < 4; k += gd_vec16<T>::W) gd_vec16<T>::load(p + k, o + k);
+}
+template <typename T> __device__ __forceinline__ void store4(T* p, const double* o) {
+#pragma unroll
+    for (int k = 0; k < 4; k += gd_vec16<T>::W) gd_vec16<T>::store(p + k, o + k);
+}
 
 // Same layout in and out: item i is the VW consecutive elements from e0 + i * VW on; the channel of an element is its
 // flat index mod C, found once per thread and advanced with the grid stride.
@@ -191,7 +178,7 @@ __global__ __launch_bounds__(PR_THREADS) void affine_flat_kernel(const TS* __res
     for (; it < nitems; it += stride) {
         const long e = e0 + it * VW;
         double v[VW];
-        if constexpr (VW == 4) Vec4<TS>::load(src + e, v);
+        if constexpr (VW == 4) load4(src + e, v);
         else v[0] = (double)src[e];
         long cc = c;
 #pragma unroll
@@ -199,7 +186,7 @@ __global__ __launch_bounds__(PR_THREADS) void affine_flat_kernel(const TS* __res
             v[k] = affine(v[k], mean[cc], scale[cc], inverse);
             if (++cc == C) cc = 0;
         }
-        if constexpr (VW == 4) Vec4<TD>::store(dst + e, v);
+        if constexpr (VW == 4) store4(dst + e, v);
         else dst[e] = (TD)v[0];
         c += cstep;
         if (c >= C) c -= C;
@@ -243,7 +230,7 @@ __global__ __launch_bounds__(PR_THREADS) void affine_nchw_kernel(const TS* __res
 // registers (KMAX is the compile-time capacity) and walks t over [t0, t1) = chunk blockIdx.y of the axis, so every load
 // and store of a wave is a run of consecutive elements of one row.  The chunk's columns of the table sit in LDS (at most
 // GD_FREQ_LDS_BYTES: a longer axis is cut into more chunks) and a wave reads coef[k, t] as a broadcast.  The terms are added in ascending k and x is added last.
-template <typename T> struct Vec2;
+template <typename T> struct Vec2;   // two consecutive elements: 8 bytes of fp32, 16 of fp64
 template <> struct Vec2<float> { typedef float2 type; };
 template <> struct Vec2<double> { typedef double2 type; };
 
@@ -327,12 +314,7 @@ static void freq_launch(const T* src, T* dst, long outer, long L, long inner, co
                            nitems, tchunk, noise, K1, coef);
 }
 
-static bool elem_aligned(const void* p, int dtype) { return ((uintptr_t)p % (dtype ? 8 : 4)) == 0; }
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static int stream_grid(long n) {
-    long g = (n + PR_THREADS - 1) / PR_THREADS;
-    return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
-}
+static int stream_grid(long n) { return gd_stream_grid(n, PR_THREADS, 65536); }
 
 template <typename TS, typename TD>
 static void affine_launch(const TS* src, TD* dst, long M, long C, const double* mean, const double* scale, int inverse, long N,
@@ -348,7 +330,7 @@ static void affine_launch(const TS* src, TD* dst, long M, long C, const double* 
         return;
     }
     const long n = M * C;
-    const long n4 = aligned16(src) && aligned16(dst) ? n / 4 : 0;
+    const long n4 = gd_aligned(src, 16) && gd_aligned(dst, 16) ? n / 4 : 0;
     if (n4 > 0)
         hipLaunchKernelGGL((affine_flat_kernel<TS, TD, 4>), dim3(stream_grid(n4)), dim3(PR_THREADS), 0, st, src, dst, 0L, n4, C, mean,
                            scale, inverse);
@@ -359,9 +341,6 @@ static void affine_launch(const TS* src, TD* dst, long M, long C, const double* 
 
 }  // namespace
 
-#define GD_S ((hipStream_t)stream)
-#define PR_DTYPE_OK(d) ((d) == GD_FILTER_F32 || (d) == GD_FILTER_F64)
-
 extern "C" size_t gd_channel_moments_ws_bytes(long M, long C) {
     if (M <= 0 || C <= 0) return 0;
     return (size_t)mom_blocks(M, C) * (size_t)C * 3 * sizeof(double);
@@ -369,11 +348,11 @@ extern "C" size_t gd_channel_moments_ws_bytes(long M, long C) {
 
 extern "C" int gd_channel_moments(const void* x, int dtype, long M, long C, double* rec, void* ws, size_t ws_bytes, void* stream) {
     GD_CHECK_ARG(x && rec && ws, "gd_channel_moments: null pointer");
-    GD_CHECK_ARG(PR_DTYPE_OK(dtype), "gd_channel_moments: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_channel_moments: dtype outside {0, 1}");
     GD_CHECK_ARG(M > 0 && C > 0, "gd_channel_moments: M <= 0 or C <= 0");
     GD_CHECK_ARG(C <= 65535L * MOM_CHUNK && M < (1L << 53) / C, "gd_channel_moments: C or M * C too large");
     GD_CHECK_ARG(ws_bytes >= gd_channel_moments_ws_bytes(M, C), "gd_channel_moments: workspace too small");
-    GD_CHECK_ARG(elem_aligned(x, dtype) && ((uintptr_t)rec % 8) == 0 && ((uintptr_t)ws % 8) == 0,
+    GD_CHECK_ARG(gd_elem_aligned(x, dtype) && gd_aligned(rec, 8) && gd_aligned(ws, 8),
                  "gd_channel_moments: pointer not element aligned");
     const long rb = mom_rows_per_block(M, C), nb = mom_blocks(M, C), chunks = (C + MOM_CHUNK - 1) / MOM_CHUNK;
     const int cw = (int)(C < MOM_CHUNK ? C : MOM_CHUNK), G = (int)mom_groups(C);
@@ -413,14 +392,14 @@ extern "C" int gd_channel_affine(const void* src, int src_dtype, void* dst, int 
                                  const double* scale_dev, int inverse, long N, long HW, void* stream) {
     GD_CHECK_ARG(src && dst && mean_dev && scale_dev, "gd_channel_affine: null pointer");
     GD_CHECK_ARG(src != dst, "gd_channel_affine: src == dst");
-    GD_CHECK_ARG(PR_DTYPE_OK(src_dtype) && PR_DTYPE_OK(dst_dtype), "gd_channel_affine: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(src_dtype) && gd_dtype_ok(dst_dtype), "gd_channel_affine: dtype outside {0, 1}");
     GD_CHECK_ARG(M > 0 && C > 0, "gd_channel_affine: M <= 0 or C <= 0");
     GD_CHECK_ARG(M < (1L << 53) / C, "gd_channel_affine: M * C too large");
     GD_CHECK_ARG(inverse == 0 || inverse == 1, "gd_channel_affine: inverse outside {0, 1}");
     GD_CHECK_ARG(N >= 0 && (N == 0 || (HW > 0 && M / N == HW && M % N == 0)), "gd_channel_affine: layout change needs N * HW == M");
     GD_CHECK_ARG(N == 0 || (C <= 65535L * TR_CH), "gd_channel_affine: C too large for the layout change");
-    GD_CHECK_ARG(elem_aligned(src, src_dtype) && elem_aligned(dst, dst_dtype) && ((uintptr_t)mean_dev % 8) == 0 &&
-                     ((uintptr_t)scale_dev % 8) == 0,
+    GD_CHECK_ARG(gd_elem_aligned(src, src_dtype) && gd_elem_aligned(dst, dst_dtype) && gd_aligned(mean_dev, 8) &&
+                     gd_aligned(scale_dev, 8),
                  "gd_channel_affine: pointer not element aligned");
     if (src_dtype == GD_FILTER_F64 && dst_dtype == GD_FILTER_F64)
         affine_launch((const double*)src, (double*)dst, M, C, mean_dev, scale_dev, inverse, N, HW, GD_S);
@@ -450,7 +429,7 @@ extern "C" int gd_freq_augment_axis(const void* src, void* dst, int dtype, long 
                                     int K1, const double* coef, void* stream) {
     GD_CHECK_ARG(src && dst && noise && coef, "gd_freq_augment_axis: null pointer");
     GD_CHECK_ARG(src != dst, "gd_freq_augment_axis: src == dst (the input is never modified)");
-    GD_CHECK_ARG(PR_DTYPE_OK(dtype), "gd_freq_augment_axis: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(dtype), "gd_freq_augment_axis: dtype outside {0, 1}");
     GD_CHECK_ARG(L > 0 && outer > 0 && inner > 0, "gd_freq_augment_axis: L <= 0 (or outer, inner <= 0)");
     GD_CHECK_ARG(K1 >= 1, "gd_freq_augment_axis: K1 < 1");
     GD_CHECK_ARG(K1 <= L, "gd_freq_augment_axis: K1 > L");
@@ -458,11 +437,11 @@ extern "C" int gd_freq_augment_axis(const void* src, void* dst, int dtype, long 
     GD_CHECK_ARG((long)K1 * L * (long)sizeof(double) <= GD_FREQ_MAX_TABLE_BYTES,
                  "gd_freq_augment_axis: table of K1 * L doubles over the cap (GD_FREQ_MAX_TABLE_BYTES)");
     GD_CHECK_ARG(outer < (1L << 53) / L / inner, "gd_freq_augment_axis: tensor too large");
-    GD_CHECK_ARG(elem_aligned(src, dtype) && elem_aligned(dst, dtype) && ((uintptr_t)noise % 8) == 0 && ((uintptr_t)coef % 8) == 0,
+    GD_CHECK_ARG(gd_elem_aligned(src, dtype) && gd_elem_aligned(dst, dtype) && gd_aligned(noise, 8) && gd_aligned(coef, 8),
                  "gd_freq_augment_axis: pointer not element aligned");
     GD_CHECK_ARG((outer * inner + PR_THREADS - 1) / PR_THREADS < (1L << 31), "gd_freq_augment_axis: outer * inner too large");
     // two series per lane where the rows are whole pairs and both tensors start on a 16-byte boundary; one otherwise
-    const bool vec = inner % 2 == 0 && aligned16(src) && aligned16(dst);
+    const bool vec = inner % 2 == 0 && gd_aligned(src, 16) && gd_aligned(dst, 16);
     if (dtype == GD_FILTER_F64) {
         if (vec) freq_launch<double, 2>((const double*)src, (double*)dst, outer, L, inner, noise, K1, coef, GD_S);
         else freq_launch<double, 1>((const double*)src, (double*)dst, outer, L, inner, noise, K1, coef, GD_S);

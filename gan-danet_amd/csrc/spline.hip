@@ -8,8 +8,8 @@
 // prefilter's recursion runs along a line, so a line is cut into chunks and every chunk is warm-started: |z| = 0.268, so
 // SP_H = 40 samples of look-back (look-ahead for the anticausal pass) leave z^40 = 1.3e-23 of the unknown state.  The
 // exact boundary sums apply where a chunk's horizon reaches the end of the line.
-#include "common.h"
-#include "../../include/gandanet.h"
+// From elem_util.h: gd_stream_grid, gd_dtype_ok, gd_elem_aligned, gd_aligned, GD_S.
+#include "elem_util.h"
 
 #include <math.h>
 
@@ -272,10 +272,7 @@ __global__ __launch_bounds__(SP_THREADS) void zoom_interp_kernel(const TS* __res
     }
 }
 
-static int stream_grid(long n) {
-    long g = (n + SP_THREADS - 1) / SP_THREADS;
-    return (int)(g < 1 ? 1 : (g > (1L << 20) ? (1L << 20) : g));
-}
+static int stream_grid(long n) { return gd_stream_grid(n, SP_THREADS, 1L << 20); }
 
 template <typename TS, typename TD, int ORDER>
 static void interp_launch_o(const TS* src, TD* dst, long outer, long nsrc, long Lin, long Lout, long inner, double pad,
@@ -335,14 +332,10 @@ static void restore_launch(const TX* x, const void* trend, int trend_dtype, cons
         restore_launch_d<TX, float>(x, (const float*)trend, mask, n, hw, scale, mean, unit, dst, dst_dtype, st);
 }
 
-static bool is_dtype(int d) { return d == GD_FILTER_F32 || d == GD_FILTER_F64; }
-static bool elem_aligned(const void* p, int dtype) { return ((uintptr_t)p % (dtype ? 8 : 4)) == 0; }
 // a product of three positive longs that does not fit in 2^62 is refused rather than wrapped
 static bool fits(long a, long b, long c) { return a <= (1L << 62) / b && a * b <= (1L << 62) / c; }
 
 }  // namespace
-
-#define GD_S ((hipStream_t)stream)
 
 extern "C" size_t gd_zoom_axis_ws_bytes(long outer, long Lin, long inner, int order, int mode) {
     if (order != 3 || outer <= 0 || Lin <= 0 || inner <= 0) return 0;
@@ -355,19 +348,19 @@ extern "C" int gd_zoom_axis(const void* src, void* dst, int src_dtype, int dst_d
                             long inner, int order, int mode, void* ws, size_t ws_bytes, void* stream) {
     GD_CHECK_ARG(src && dst, "gd_zoom_axis: null pointer");
     GD_CHECK_ARG(src != dst, "gd_zoom_axis: src == dst (the zoom is not in place)");
-    GD_CHECK_ARG(is_dtype(src_dtype) && is_dtype(dst_dtype), "gd_zoom_axis: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(src_dtype) && gd_dtype_ok(dst_dtype), "gd_zoom_axis: dtype outside {0, 1}");
     GD_CHECK_ARG(Lin > 0 && outer > 0 && inner > 0, "gd_zoom_axis: L <= 0 (or outer, inner <= 0)");
     GD_CHECK_ARG(Lout > 0, "gd_zoom_axis: Lout <= 0");
     GD_CHECK_ARG(order == 0 || order == 1 || order == 3, "gd_zoom_axis: order outside {0, 1, 3}");
     GD_CHECK_ARG(mode == GD_ZOOM_MIRROR || mode == GD_ZOOM_NEAREST, "gd_zoom_axis: unknown mode");
     GD_CHECK_ARG(fits(outer, Lin + 2 * SP_PAD, inner) && fits(outer, Lout, inner), "gd_zoom_axis: tensor of 2^62 elements or more");
-    GD_CHECK_ARG(elem_aligned(src, src_dtype) && elem_aligned(dst, dst_dtype), "gd_zoom_axis: pointer not element aligned");
+    GD_CHECK_ARG(gd_elem_aligned(src, src_dtype) && gd_elem_aligned(dst, dst_dtype), "gd_zoom_axis: pointer not element aligned");
     const long pad = order == 3 && mode == GD_ZOOM_NEAREST ? SP_PAD : 0;
     if (order == 3) {
         GD_CHECK_ARG(ws, "gd_zoom_axis: null pointer (order 3 needs the workspace)");
         GD_CHECK_ARG(ws_bytes >= gd_zoom_axis_ws_bytes(outer, Lin, inner, order, mode),
                      "gd_zoom_axis: workspace smaller than gd_zoom_axis_ws_bytes");
-        GD_CHECK_ARG(((uintptr_t)ws % 8) == 0 && ws != src && ws != dst, "gd_zoom_axis: workspace not 8-byte aligned, or src / dst");
+        GD_CHECK_ARG(gd_aligned(ws, 8) && ws != src && ws != dst, "gd_zoom_axis: workspace not 8-byte aligned, or src / dst");
         double* coef = (double*)ws;
         if (src_dtype == GD_FILTER_F64) prefilter_launch<double>((const double*)src, coef, outer, Lin, inner, pad, pad != 0, GD_S);
         else prefilter_launch<float>((const float*)src, coef, outer, Lin, inner, pad, pad != 0, GD_S);
@@ -394,10 +387,10 @@ extern "C" int gd_spline_prefilter_axis(const void* src, double* dst, int src_dt
                                         void* stream) {
     GD_CHECK_ARG(src && dst, "gd_spline_prefilter_axis: null pointer");
     GD_CHECK_ARG(src != (const void*)dst, "gd_spline_prefilter_axis: src == dst (the filter is not in place)");
-    GD_CHECK_ARG(is_dtype(src_dtype), "gd_spline_prefilter_axis: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(src_dtype), "gd_spline_prefilter_axis: dtype outside {0, 1}");
     GD_CHECK_ARG(L > 0 && outer > 0 && inner > 0, "gd_spline_prefilter_axis: L <= 0 (or outer, inner <= 0)");
     GD_CHECK_ARG(fits(outer, L, inner), "gd_spline_prefilter_axis: tensor of 2^62 elements or more");
-    GD_CHECK_ARG(elem_aligned(src, src_dtype) && ((uintptr_t)dst % 8) == 0, "gd_spline_prefilter_axis: pointer not element aligned");
+    GD_CHECK_ARG(gd_elem_aligned(src, src_dtype) && gd_aligned(dst, 8), "gd_spline_prefilter_axis: pointer not element aligned");
     if (src_dtype == GD_FILTER_F64) prefilter_launch<double>((const double*)src, dst, outer, L, inner, 0, 0, GD_S);
     else prefilter_launch<float>((const float*)src, dst, outer, L, inner, 0, 0, GD_S);
     GD_LAUNCH_CHECK();
@@ -408,12 +401,12 @@ extern "C" int gd_restore_units(const void* x, int x_dtype, const void* trend, i
                                 long planes, long hw, double scale, double mean, double unit, void* dst, int dst_dtype,
                                 void* stream) {
     GD_CHECK_ARG(x && dst, "gd_restore_units: null pointer");
-    GD_CHECK_ARG(is_dtype(x_dtype) && is_dtype(dst_dtype) && (!trend || is_dtype(trend_dtype)), "gd_restore_units: dtype outside {0, 1}");
+    GD_CHECK_ARG(gd_dtype_ok(x_dtype) && gd_dtype_ok(dst_dtype) && (!trend || gd_dtype_ok(trend_dtype)), "gd_restore_units: dtype outside {0, 1}");
     GD_CHECK_ARG(planes > 0 && hw > 0, "gd_restore_units: n <= 0");
     GD_CHECK_ARG(fits(planes, hw, 1), "gd_restore_units: tensor of 2^62 elements or more");
     GD_CHECK_ARG(x != dst || x_dtype == dst_dtype, "gd_restore_units: dst aliases x with another dtype");
     GD_CHECK_ARG(dst != trend && dst != (const void*)mask, "gd_restore_units: dst aliases trend or mask");
-    GD_CHECK_ARG(elem_aligned(x, x_dtype) && elem_aligned(dst, dst_dtype) && (!trend || elem_aligned(trend, trend_dtype)),
+    GD_CHECK_ARG(gd_elem_aligned(x, x_dtype) && gd_elem_aligned(dst, dst_dtype) && (!trend || gd_elem_aligned(trend, trend_dtype)),
                  "gd_restore_units: pointer not element aligned");
     const long n = planes * hw;
     if (!trend) trend_dtype = GD_FILTER_F64;

@@ -10,9 +10,9 @@
 // steps; a pair's value is computed by one thread from start to end in an order fixed by (T, parameters), so a series'
 // result depends on nothing but the series: not on M, its place in the group, or the launch.  No global atomics, no
 // workspace.  The order statistics behind the robustness weights are found by counting ranks in LDS.
-#include "common.h"
+// From elem_util.h: gd_dtype_ok, gd_elem_aligned, GD_S.
+#include "elem_util.h"
 #include "stl_core.h"
-#include "../../include/gandanet.h"
 
 #include <vector>
 
@@ -117,11 +117,10 @@ static bool odd3(int v) { return v >= 3 && (v & 1); }
 
 }  // namespace
 
-#define STL_ALIGNED(p, n) (((uintptr_t)(p) % (n)) == 0)
 // the checks gd_stl_decompose and its host twin share
 #define STL_CHECKS(fn)                                                                                                       \
     GD_CHECK_ARG(x && trend_out && seasonal_out && resid_out, fn ": null pointer");                                        \
-    GD_CHECK_ARG(dtype == GD_FILTER_F32 || dtype == GD_FILTER_F64, fn ": dtype outside {0, 1}");                           \
+    GD_CHECK_ARG(gd_dtype_ok(dtype), fn ": dtype outside {0, 1}");                                                         \
     GD_CHECK_ARG(T > 0 && M > 0, fn ": T <= 0 or M <= 0");                                                                  \
     GD_CHECK_ARG(period >= 2, fn ": period < 2");                                                                           \
     GD_CHECK_ARG(odd3(seasonal), fn ": seasonal must be an odd integer >= 3");                                             \
@@ -135,8 +134,8 @@ static bool odd3(int v) { return v >= 3 && (v & 1); }
     GD_CHECK_ARG(T <= GD_STL_MAX_T, fn ": T above GD_STL_MAX_T");                                                          \
     GD_CHECK_ARG(T >= 2L * period, fn ": T < 2 * period");                                                                  \
     GD_CHECK_ARG(M < (1L << 31) && M < (1L << 53) / T, fn ": too many series");                                             \
-    GD_CHECK_ARG(STL_ALIGNED(x, dtype ? 8 : 4) && STL_ALIGNED(trend_out, dtype ? 8 : 4) && STL_ALIGNED(seasonal_out, dtype ? 8 : 4) && \
-                     STL_ALIGNED(resid_out, dtype ? 8 : 4) && STL_ALIGNED(weights_out, dtype ? 8 : 4),                        \
+    GD_CHECK_ARG(gd_elem_aligned(x, dtype) && gd_elem_aligned(trend_out, dtype) && gd_elem_aligned(seasonal_out, dtype) &&  \
+                     gd_elem_aligned(resid_out, dtype) && gd_elem_aligned(weights_out, dtype),                               \
                  fn ": pointer not element aligned");                                                                        \
     const GdStlParams P = {(int)T, period, seasonal, trend, low_pass, seasonal_deg, trend_deg, low_pass_deg, inner_iter, outer_iter}
 
@@ -147,9 +146,9 @@ extern "C" int gd_stl_decompose(const void* x, int dtype, long T, long M, int pe
     static_assert(gd_stl_work_doubles(GD_STL_MAX_T, GD_STL_MAX_T / 2, 1) * 8 <= STL_LDS_MAX, "one series at the cap must fit the LDS");
     if (dtype == GD_FILTER_F64)
         return stl_launch((const double*)x, M, P, (double*)trend_out, (double*)seasonal_out, (double*)resid_out, (double*)weights_out,
-                          (hipStream_t)stream);
+                          GD_S);
     return stl_launch((const float*)x, M, P, (float*)trend_out, (float*)seasonal_out, (float*)resid_out, (float*)weights_out,
-                      (hipStream_t)stream);
+                      GD_S);
 }
 
 // Host only, no GPU call: the same fit (stl_core.h) in plain loops, series after series, every pointer in HOST memory.

@@ -34,8 +34,8 @@ def _chk(t: Tensor, name: str = "tensor", dtype=torch.float32) -> None:
         raise L.GandanetError(f"{name}: expected {dtype}, got {t.dtype}")
 
 
-def _dense(t: Tensor, name: str = "tensor") -> Tensor:
-    _chk(t, name)
+def _dense(t: Tensor, name: str = "tensor", dtype=torch.float32) -> Tensor:
+    _chk(t, name, dtype)
     if not t.is_contiguous():
         raise L.GandanetError(f"{name}: expected a contiguous tensor, got strides {t.stride()}")
     return t
@@ -1337,7 +1337,8 @@ def nhwc_l1_grad(a: Tensor, b: Tensor, upstream: Tensor, relu_mask: bool, split:
 
 
 # ---- evaluation (evalstats.hip) ----------------------------------------------------------------------------------------
-def _eval_dtype(t: Tensor, name: str) -> int:
+def _filter_dtype(t: Tensor, name: str) -> int:
+    """fp32 -> GD_FILTER_F32, fp64 -> GD_FILTER_F64 for a dense GPU tensor; the tag of every analysis entry point"""
     if not t.is_cuda:
         raise L.GandanetError(f"{name}: expected a GPU tensor (there is no CPU fallback in the product path)")
     if t.dtype not in (torch.float32, torch.float64):
@@ -1345,6 +1346,20 @@ def _eval_dtype(t: Tensor, name: str) -> int:
     if not t.is_contiguous():
         raise L.GandanetError(f"{name}: expected a contiguous tensor, got strides {t.stride()}")
     return int(t.dtype == torch.float64)
+
+
+def _out_dtype(out_dtype, src: Tensor, fn: str):
+    """the output dtype of ``fn``: fp32 or fp64, the dtype of ``src`` by default"""
+    out_dtype = src.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise L.GandanetError(f"{fn}: expected float32 or float64 output, got {out_dtype}")
+    return out_dtype
+
+
+def _plane_chunks(planes: int):
+    """(lo, k): the planes [lo, lo + k) of one launch, at most 65535 (the grid.y limit)"""
+    for lo in range(0, planes, 65535):
+        yield lo, min(65535, planes - lo)
 
 
 def _eval_mask(mask: Optional[Tensor], hw: int) -> Optional[Tensor]:
@@ -1361,8 +1376,8 @@ def eval_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] 
     """the 8-double record of ``pred`` against ``truth`` (include/gandanet.h, "evaluation") written into ``rec`` (a view
     of 8 fp64 on the device); ``mask`` (uint8, one entry per element of the trailing dims it covers) is shared by all
     leading planes; ``affine`` = (a, b) reads both inputs as v * a + b.  No host sync."""
-    f64 = _eval_dtype(pred, "pred")
-    if _eval_dtype(truth, "truth") != f64 or pred.shape != truth.shape:
+    f64 = _filter_dtype(pred, "pred")
+    if _filter_dtype(truth, "truth") != f64 or pred.shape != truth.shape:
         raise L.GandanetError(f"eval_stats: pred {tuple(pred.shape)} {pred.dtype} vs truth {tuple(truth.shape)} {truth.dtype}")
     _chk(rec, "record", torch.float64)
     if rec.numel() != 8 or not rec.is_contiguous():
@@ -1381,23 +1396,32 @@ def eval_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] 
     return rec
 
 
-def masked_plane_mean(x: Tensor, mask: Optional[Tensor] = None, plane_dims: int = 2) -> Tuple[Tensor, Tensor]:
-    """np.nanmean over the last ``plane_dims`` dims of ``x`` with the pixels where ``mask`` is 0 left out: (mean fp64,
-    valid count int64), both shaped like the leading dims; a plane without a valid pixel gives NaN"""
-    _dense(x, "planes")
+def _plane_mean(x: Tensor, mask: Optional[Tensor], plane_dims: int, dtype) -> Tuple[Tensor, Tensor]:
+    _dense(x, "planes", dtype)
+    fn = "gd_masked_plane_mean" + ("_f64" if dtype == torch.float64 else "")
+    launch, ws_bytes = getattr(lib(), fn), getattr(lib(), fn + "_ws_bytes")
     lead = tuple(x.shape[:x.dim() - plane_dims])
     hw = math.prod(x.shape[x.dim() - plane_dims:])
-    planes = math.prod(lead)
     mask = _eval_mask(mask, hw)
     mean = torch.empty(lead, device=x.device, dtype=torch.float64)
     count = torch.empty(lead, device=x.device, dtype=torch.int64)
-    for lo in range(0, planes, 65535):                          # grid.y limit of one launch
-        k = min(65535, planes - lo)
-        nbytes = int(lib().gd_masked_plane_mean_ws_bytes(k, hw))
+    for lo, k in _plane_chunks(math.prod(lead)):
+        nbytes = int(ws_bytes(k, hw))
         ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-        L.check(lib().gd_masked_plane_mean(x.data_ptr() + 4 * lo * hw, k, hw, _ptr(mask), mean.data_ptr() + 8 * lo,
-                                           count.data_ptr() + 8 * lo, _ptr(ws), nbytes, _stream()), "gd_masked_plane_mean")
+        L.check(launch(x.data_ptr() + x.element_size() * lo * hw, k, hw, _ptr(mask), mean.data_ptr() + 8 * lo,
+                       count.data_ptr() + 8 * lo, _ptr(ws), nbytes, _stream()), fn)
     return mean, count
+
+
+def masked_plane_mean(x: Tensor, mask: Optional[Tensor] = None, plane_dims: int = 2) -> Tuple[Tensor, Tensor]:
+    """np.nanmean over the last ``plane_dims`` dims of the fp32 ``x`` with the pixels where ``mask`` is 0 left out: (mean
+    fp64, valid count int64), both shaped like the leading dims; a plane without a valid pixel gives NaN"""
+    return _plane_mean(x, mask, plane_dims, torch.float32)
+
+
+def masked_plane_mean_f64(x: Tensor, mask: Optional[Tensor] = None, plane_dims: int = 2) -> Tuple[Tensor, Tensor]:
+    """``masked_plane_mean`` of an fp64 tensor; NaN pixels are left out as well, as np.nanmean leaves them out"""
+    return _plane_mean(x, mask, plane_dims, torch.float64)
 
 
 def ensemble_stats(x: Tensor, mean: Optional[Tensor] = None, std: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
@@ -1484,10 +1508,6 @@ def adamw_guarded(p: Tensor, g: Tensor, m: Tensor, v: Tensor, rec: Tensor, lr: f
 
 
 # ---- filters (include/gandanet.h, "filters"; filters.hip) ------------------------------------------------------------
-def _filter_dtype(t: Tensor, name: str) -> int:
-    return _eval_dtype(t, name)                                  # fp32 -> GD_FILTER_F32, fp64 -> GD_FILTER_F64
-
-
 def _axis_view(t: Tensor, axis: int) -> Tuple[int, int, int]:
     """(outer, L, inner) of a dense tensor around ``axis``"""
     return math.prod(t.shape[:axis]), t.shape[axis], math.prod(t.shape[axis + 1:])
@@ -1569,9 +1589,7 @@ def zoom_axis(src: Tensor, axis: int, n_out: int, order: int, mode: int, out_dty
     """``src`` zoomed to ``n_out`` samples along ``axis`` (scipy.ndimage.zoom's rule for one axis); a new tensor of
     ``out_dtype`` (default: the dtype of ``src``).  The order-3 coefficients live in a temporary.  No host sync."""
     sdt = _filter_dtype(src, "zoom src")
-    out_dtype = src.dtype if out_dtype is None else out_dtype
-    if out_dtype not in (torch.float32, torch.float64):
-        raise L.GandanetError(f"zoom_axis: expected float32 or float64 output, got {out_dtype}")
+    out_dtype = _out_dtype(out_dtype, src, "zoom_axis")
     outer, n, inner = _axis_view(src, axis)
     shape = list(src.shape)
     shape[axis] = int(n_out)
@@ -1617,27 +1635,6 @@ def restore_units(x: Tensor, trend: Optional[Tensor], mask: Optional[Tensor], sc
     return out
 
 
-def masked_plane_mean_f64(x: Tensor, mask: Optional[Tensor] = None, plane_dims: int = 2) -> Tuple[Tensor, Tensor]:
-    """``masked_plane_mean`` of an fp64 tensor; NaN pixels are left out as well, as np.nanmean leaves them out"""
-    _chk(x, "planes", torch.float64)
-    if not x.is_contiguous():
-        raise L.GandanetError(f"planes: expected a contiguous tensor, got strides {x.stride()}")
-    lead = tuple(x.shape[:x.dim() - plane_dims])
-    hw = math.prod(x.shape[x.dim() - plane_dims:])
-    planes = math.prod(lead)
-    mask = _eval_mask(mask, hw)
-    mean = torch.empty(lead, device=x.device, dtype=torch.float64)
-    count = torch.empty(lead, device=x.device, dtype=torch.int64)
-    for lo in range(0, planes, 65535):                          # grid.y limit of one launch
-        k = min(65535, planes - lo)
-        nbytes = int(lib().gd_masked_plane_mean_f64_ws_bytes(k, hw))
-        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-        L.check(lib().gd_masked_plane_mean_f64(x.data_ptr() + 8 * lo * hw, k, hw, _ptr(mask), mean.data_ptr() + 8 * lo,
-                                               count.data_ptr() + 8 * lo, _ptr(ws), nbytes, _stream()),
-                "gd_masked_plane_mean_f64")
-    return mean, count
-
-
 # ---- dataset preparation (include/gandanet.h, "dataset preparation"; prepare.hip) ----------------------------------------
 def channel_moments(x: Tensor, channels: int) -> Tensor:
     """(count, mean, M2) of every channel of the dense channel-last ``x`` seen as (numel / channels, channels): a new
@@ -1673,9 +1670,7 @@ def channel_affine(src: Tensor, mean: Tensor, scale: Tensor, inverse: bool = Fal
     ``src`` (``mean``, ``scale``: C fp64 device values); with ``to_nchw`` a 4-D (N, H, W, C) input comes out as a dense
     (N, C, H, W) tensor.  A new tensor of ``out_dtype`` (default: the dtype of ``src``)."""
     sdt = _filter_dtype(src, "channel_affine input")
-    out_dtype = src.dtype if out_dtype is None else out_dtype
-    if out_dtype not in (torch.float32, torch.float64):
-        raise L.GandanetError(f"channel_affine: expected float32 or float64 output, got {out_dtype}")
+    out_dtype = _out_dtype(out_dtype, src, "channel_affine")
     _chk(mean, "channel_affine mean", torch.float64)
     _chk(scale, "channel_affine scale", torch.float64)
     c = mean.numel()
@@ -1742,9 +1737,7 @@ def zone_rasterize(edges: Tensor, offsets, xs: Tensor, ys: Tensor, out: Optional
     ``out`` is written.  No host sync."""
     import numpy as np
     for t, nm in ((edges, "zone edges"), (xs, "zone grid xs"), (ys, "zone grid ys")):
-        _chk(t, nm, torch.float64)
-        if not t.is_contiguous():
-            raise L.GandanetError(f"{nm}: expected a contiguous tensor, got strides {t.stride()}")
+        _dense(t, nm, torch.float64)
     if edges.dim() != 2 or edges.shape[1] != 4 or xs.dim() != 1 or ys.dim() != 1:
         raise L.GandanetError(f"zone_rasterize: edges {tuple(edges.shape)}, xs {tuple(xs.shape)}, ys {tuple(ys.shape)}")
     off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
@@ -1778,7 +1771,7 @@ def zone_mean(x: Tensor, bits: Tensor, zones: int, weights: Optional[Tensor] = N
     the dense fp32 / fp64 ``x`` and is shared by all leading planes; a pixel counts for zone z iff its bit is set and its
     value is not NaN; ``weights`` (fp64, the shape of ``bits``) or None = 1.  Returns (mean fp64, count int64), both shaped
     like the leading dims of ``x`` followed by ``zones``; a zone without a contributing pixel gives NaN and 0."""
-    dt = _eval_dtype(x, "zone_mean input")
+    dt = _filter_dtype(x, "zone_mean input")
     _chk(bits, "zone bits", torch.uint32)
     hw = bits.numel()
     nd = x.dim() - bits.dim()
@@ -1797,12 +1790,10 @@ def zone_mean(x: Tensor, bits: Tensor, zones: int, weights: Optional[Tensor] = N
         raise L.GandanetError("zone_mean: empty tensor")
     mean = torch.empty(lead + (z,), device=x.device, dtype=torch.float64)
     count = torch.empty(lead + (z,), device=x.device, dtype=torch.int64)
-    esz = x.element_size()
-    for lo in range(0, planes, 65535):                          # grid.y limit of one launch
-        k = min(65535, planes - lo)
+    for lo, k in _plane_chunks(planes):
         nbytes = int(lib().gd_zone_mean_ws_bytes(k, hw, z))
         ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-        L.check(lib().gd_zone_mean(x.data_ptr() + esz * lo * hw, dt, k, hw, _ptr(bits), z, _ptr(weights), mean.data_ptr() + 8 * lo * z,
+        L.check(lib().gd_zone_mean(x.data_ptr() + x.element_size() * lo * hw, dt, k, hw, _ptr(bits), z, _ptr(weights), mean.data_ptr() + 8 * lo * z,
                                    count.data_ptr() + 8 * lo * z, _ptr(ws), nbytes, _stream()), "gd_zone_mean")
     return mean, count
 

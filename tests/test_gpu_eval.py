@@ -150,6 +150,73 @@ def test_masked_plane_mean():
     np.testing.assert_allclose(mean.cpu().numpy(), want, rtol=1e-12, atol=0)
 
 
+_MB_SHAPE = (2, 3, 37, 61)   # 6 planes of 2257 elements: three workgroups per plane, every 16-byte misalignment of a plane
+
+
+def _multiblock_case(dtype):
+    """(x, mask, np.nanmean of the masked planes in fp64) for test_masked_plane_mean_multiblock"""
+    if dtype not in _multiblock_case.cache:
+        g = torch.Generator().manual_seed(17)
+        x = torch.randn(*_MB_SHAPE, generator=g, dtype=dtype) + 2.0
+        mask = np.random.default_rng(6).random(_MB_SHAPE[2:]) < 0.6
+        xm = x.numpy().astype(np.float64)
+        xm[:, :, ~mask] = np.nan
+        _multiblock_case.cache[dtype] = (x, mask, np.nanmean(xm, axis=(2, 3)))
+    return _multiblock_case.cache[dtype]
+
+
+_multiblock_case.cache = {}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_masked_plane_mean_multiblock(dtype):
+    """planes of 2257 elements take three workgroups each (2257 > 2 * 1024; the cap of 2048 / planes does not bind), so
+    the per-plane partials and their ordered final add are in play; 2257 is odd, so successive planes start 0, 3, 2, 1
+    (fp32) or 0, 1 (fp64) elements before a 16-byte boundary.  Means against np.nanmean in fp64 at rtol 1e-12 (a few
+    1e-16 expected over ~1350 fp64 addends), counts exact.  A NaN at a mask-valid pixel: the fp32 entry propagates it
+    into that plane's mean, the fp64 entry leaves the pixel out and counts one less."""
+    K = _K()
+    fn = K.masked_plane_mean if dtype == torch.float32 else K.masked_plane_mean_f64
+    x, mask, want = _multiblock_case(dtype)
+    hw = math.prod(_MB_SHAPE[2:])
+    assert hw == 2257 and mask[0, 0] and not mask.all()
+    md = torch.from_numpy(mask.astype(np.uint8)).to(DEV)
+    xd = x.to(DEV)
+    assert xd.data_ptr() % 16 == 0
+
+    def check(mean, count, want_mean, want_count, where):
+        print(where, dtype, "max rel err", np.max(np.abs(mean.cpu().numpy() / want_mean - 1.0)))
+        assert mean.shape == _MB_SHAPE[:2] and mean.dtype == torch.float64 and count.dtype == torch.int64, where
+        assert np.array_equal(count.cpu().numpy(), np.broadcast_to(want_count, _MB_SHAPE[:2])), where
+        np.testing.assert_allclose(mean.cpu().numpy(), want_mean, rtol=1e-12, atol=0, err_msg=where)
+
+    check(*fn(xd, md), want, mask.sum(), "mask")
+    check(*fn(xd, None), np.nanmean(x.numpy().astype(np.float64), axis=(2, 3)), hw, "no mask")
+    # the same planes one element into a larger buffer: every plane's head changes
+    buf = torch.empty(x.numel() + 1, dtype=dtype, device=DEV)
+    buf[1:] = xd.reshape(-1)
+    check(*fn(buf[1:].view(_MB_SHAPE), md), want, mask.sum(), "offset view")
+    # the masked-out pixels may hold NaN
+    xn = x.clone()
+    xn[:, :, torch.from_numpy(~mask)] = float("nan")
+    check(*fn(xn.to(DEV), md), want, mask.sum(), "mask over NaN")
+    # a NaN at a valid pixel of plane (1, 2)
+    xv = x.clone()
+    xv[1, 2, 0, 0] = float("nan")
+    mean, count = fn(xv.to(DEV), md)
+    mean, count = mean.cpu().numpy(), count.cpu().numpy()
+    other = np.ones(_MB_SHAPE[:2], dtype=bool)
+    other[1, 2] = False
+    np.testing.assert_allclose(mean[other], want[other], rtol=1e-12, atol=0)
+    if dtype == torch.float32:
+        assert np.isnan(mean[1, 2]) and np.all(count == mask.sum())
+    else:
+        xm = xv.numpy().copy()
+        xm[:, :, ~mask] = np.nan
+        np.testing.assert_allclose(mean[1, 2], np.nanmean(xm[1, 2]), rtol=1e-12, atol=0)
+        assert count[1, 2] == mask.sum() - 1 and np.all(count[other] == mask.sum())
+
+
 @pytest.mark.parametrize("dtype,rtol", [(torch.float32, 2.4e-7), (torch.float64, 1e-14)])
 @pytest.mark.parametrize("M", [1, 5, 32])
 def test_ensemble_stats(M, dtype, rtol):
