@@ -272,13 +272,12 @@ struct NhwcConvArgs {
     int H, W, Ho, Wo, K, M, act, tiles_x, nchunks;   // act: 0 none, 1 ReLU, 2 LeakyReLU(slope)
     float slope;
     int osplit;                   // 1: y holds 3 M channels per pixel, the result split as [hi | lo | hi] (operand mode "x3")
-    int epi_lds;                  // 1: 16-bit pixel-major output through the LDS-transposed epilogue (16-byte stores)
 };
 
 // S = stride (1: VGG stack; 2: the down-sampling convs of Discriminator1, discriminator.py:60-63 -- the patch of a
 // 4 x 32 output tile is then 9 x 65 input pixels and consecutive output pixels read patch pixels two apart)
-// EPI = 1: the LDS-transposed 16-bit pixel-major epilogue (its own instantiation, so that the fp32 NCHW / direct form keeps
-// its registers)
+// EPI = 1: the LDS-transposed 16-bit pixel-major epilogue (y32 == null); EPI = 0: the fp32 NCHW epilogue (y32 != null).  Two
+// instantiations, so that the fp32 NCHW form keeps its registers
 template <int BM, int S, int EPI = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_nhwc_kernel(const NhwcConvArgs a) {
     constexpr int TH = S == 1 ? 8 : 4;
@@ -399,8 +398,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_nhwc_kernel(const NhwcConvArgs
 
     // ---- pixel-major 16-bit output: every 32 x 32 accumulator tile goes through a per-wave LDS scratch (the patch image is
     // dead behind the loop's last barrier) and leaves as 16-byte stores, four lanes covering the 64 contiguous bytes of a
-    // pixel's 32 channels -- the direct form below writes 8 bytes per lane 2 M (6 M) bytes apart.  GD_NHWC_EPI_LDS=0 (host)
-    // selects the direct form for A/B.
+    // pixel's 32 channels (the direct form, 8-byte stores per lane 2 M (6 M) bytes apart, measured 2 % slower on the mixed
+    // step and was removed).
     if constexpr (EPI == 1) {
         constexpr int SLD = LD;                              // 80-byte scratch rows: 16-byte aligned reads
         static_assert(4 * 2 * 32 * SLD <= NPIX * LD, "per-wave scratch must fit in the patch image");
@@ -480,7 +479,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_nhwc_kernel(const NhwcConvArgs
         return;
     }
 
-    // ---- epilogue: lane = pixel, accumulator registers 4g..4g+3 = four consecutive output channels (8-byte stores) ----
+    // ---- fp32 NCHW epilogue (EPI = 0: the launcher passes y32): lane = pixel, accumulator registers 4g..4g+3 = four
+    // consecutive output channels ----
     const int ox = x0 + r;
     if (ox < a.Wo) {
 #pragma unroll
@@ -521,25 +521,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_nhwc_kernel(const NhwcConvArgs
                             v[3] += gd_bf2f((unsigned short)(rr.y >> 16));
                         }
                     }
-                    if (a.y32) {
-                        // fp32 NCHW: for one channel the 32 lanes of a half-wave are 32 consecutive pixels (128-byte rows)
-                        float* yp = a.y32 + (long)b * a.y32_bs + (long)m * a.Ho * a.Wo + (long)oy * a.Wo + ox;
+                    // fp32 NCHW: for one channel the 32 lanes of a half-wave are 32 consecutive pixels (128-byte rows)
+                    float* yp = a.y32 + (long)b * a.y32_bs + (long)m * a.Ho * a.Wo + (long)oy * a.Wo + ox;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) yp[(long)k * a.Ho * a.Wo] = v[k];
-                        continue;
-                    }
-                    uint2 o;
-                    if (a.osplit) {
-                        uint2 lo;
-                        gd_split_bf2(v[0], v[1], o.x, lo.x);
-                        gd_split_bf2(v[2], v[3], o.y, lo.y);
-                        *reinterpret_cast<uint2*>(a.y + pbase + a.M + m) = lo;
-                        *reinterpret_cast<uint2*>(a.y + pbase + 2 * a.M + m) = o;
-                    } else {
-                        o.x = gd_pack_bf2(v[0], v[1]);
-                        o.y = gd_pack_bf2(v[2], v[3]);
-                    }
-                    *reinterpret_cast<uint2*>(a.y + pbase + m) = o;
+                    for (int k = 0; k < 4; ++k) yp[(long)k * a.Ho * a.Wo] = v[k];
                 }
         }
     }
@@ -739,8 +724,7 @@ static int nhwc_conv_launch(const void* x, const void* wpack, const float* bias,
                             void* y, int B, int H, int W, int K, int M, int stride, int act, float slope, void* stream,
                             float* y32 = nullptr, long y32_bs = 0, int osplit = 0) {
     NhwcConvArgs a;
-    static const int epi_env = getenv("GD_NHWC_EPI_LDS") ? atoi(getenv("GD_NHWC_EPI_LDS")) : 1;
-    a.y32 = y32; a.y32_bs = y32_bs; a.osplit = osplit; a.epi_lds = epi_env;
+    a.y32 = y32; a.y32_bs = y32_bs; a.osplit = osplit;
     a.x = (const unsigned short*)x; a.wp = (const unsigned short*)wpack; a.bias = bias;
     a.mask = (const unsigned short*)mask; a.res = (const unsigned short*)res; a.y = (unsigned short*)y;
     a.H = H; a.W = W; a.K = K; a.M = M; a.act = act; a.slope = slope;
@@ -753,7 +737,7 @@ static int nhwc_conv_launch(const void* x, const void* wpack, const float* bias,
     const int tiles_y = (a.Ho + th - 1) / th;
     dim3 grid(a.tiles_x * tiles_y, mtiles, B);
     hipStream_t s = (hipStream_t)stream;
-    if (!a.y32 && a.epi_lds) {
+    if (!a.y32) {
         if (stride == 1) {
             if (bm == 64) hipLaunchKernelGGL((conv3x3_nhwc_kernel<64, 1, 1>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((conv3x3_nhwc_kernel<128, 1, 1>), grid, dim3(256), 0, s, a);
@@ -1136,9 +1120,6 @@ __global__ __launch_bounds__(NW * 64, PIPED ? GD_WGRAD_PIPED_MINW : 2) void conv
 
 }  // namespace
 
-static const bool g_wgrad_cs_piped = getenv("GD_WGRAD_CS_PIPED") ? atoi(getenv("GD_WGRAD_CS_PIPED")) != 0 : true;   // A/B switch
-static const bool g_wgrad_s2_piped = getenv("GD_WGRAD_S2_PIPED") ? atoi(getenv("GD_WGRAD_S2_PIPED")) != 0 : true;   // A/B switch
-
 // Launch shape of the weight gradient: a pure function of the sizes, the deterministic mode and the workspace size, shared
 // by gd_conv3x3_wgrad_plan and the launcher so that the two cannot drift.
 namespace {
@@ -1236,7 +1217,7 @@ extern "C" int gd_conv3x3_wgrad_ws(const float* dy, long dy_bs, const void* dy_b
         if (p.ordered) hipLaunchKernelGGL((conv3x3_wgrad_kernel<NW_, S_, CS_, PIPED_, true>), grid, dim3(THREADS_), 0, s, a); \
         else hipLaunchKernelGGL((conv3x3_wgrad_kernel<NW_, S_, CS_, PIPED_, false>), grid, dim3(THREADS_), 0, s, a);          \
     } while (0)
-    if (cs && a.dy16 && a.x16 && g_wgrad_cs_piped) {
+    if (cs && a.dy16 && a.x16) {
         // both operands 16-bit (the dense layers' packs): the same software pipeline as the wide convs below
         if (cs_nw == 3) WG_LAUNCH(3, 1, true, true, 192);
         else WG_LAUNCH(4, 1, true, true, 256);
@@ -1252,7 +1233,7 @@ extern "C" int gd_conv3x3_wgrad_ws(const float* dy, long dy_bs, const void* dy_b
         if (best_nw == 2) WG_LAUNCH(2, 1, false, false, 128);
         else if (best_nw == 4) WG_LAUNCH(4, 1, false, false, 256);
         else WG_LAUNCH(6, 1, false, false, 384);
-    } else if (a.dy16 && a.x16 && best_nw == 4 && g_wgrad_s2_piped) {
+    } else if (a.dy16 && a.x16 && best_nw == 4) {
         // stride 2, both operands 16-bit (Discriminator1's trunk): the same software pipeline
         WG_LAUNCH(4, 2, false, true, 256);
     } else {

@@ -67,7 +67,6 @@ def lib():
     return L.load()
 
 
-WGRAD_X_NHWC = os.environ.get("GD_WGRAD_X_NHWC", "1") != "0"   # pixel-major bf16 x for wide 3x3 weight gradients (A/B switch)
 USE_CONV3X3_FAST = True   # route eligible 3x3/s1/p1 bf16 convs to the LDS-patch kernel (tests flip it to A/B)
 
 
@@ -238,7 +237,7 @@ def _conv2d_wgrad(dy, x, k, stride, pad, precision, in_scale, in_shift, in_relu,
         if Cout > 32 and Cin >= 4 * 32:
             # every 32-channel chunk of ci re-reads each dY tile: hand the kernel a bf16 copy made once
             dy16, _ = pack_bf16(dy.view(B, Cout, Ho * Wo), Cout, Ho * Wo, plain_shape=(Cout, Ho * Wo))
-            if WGRAD_X_NHWC and in_scale is None and x.dim() == 4:
+            if in_scale is None and x.dim() == 4:
                 # and a pixel-major bf16 copy of x: each of the Cout/BM m-blocks re-stages every patch, as 16-byte
                 # copies instead of strided 4-byte gathers (the 2C -> C fuse convs: 12.4 -> 10.5 ms incl. the pack, bench shape)
                 x_ld = (Cin + 7) // 8 * 8
@@ -796,9 +795,6 @@ def pam_f16_scale(dout: Tensor, gamma: Tensor, delta: Tensor) -> Tensor:
     return scales
 
 
-PAM_NOMAX = os.environ.get("GD_PAM_NOMAX", "1") != "0"      # let the forward drop the running maximum where a bound allows
-
-
 def pam_key_sqnorm_max(kt: Tensor, N: int, f16: bool = False) -> Tensor:
     """max_j |k_j|^2 per image of the packed keys kt (B, Npad, 32) (gd_pam_key_sqnorm_max)"""
     B, Npad = kt.shape[0], kt.shape[1]
@@ -836,10 +832,6 @@ def pam_flash_fwd_shift(qt, kt, v, B, N, Npad, Cn, Cp, gamma, x, out, o_attn, ls
     return None
 
 
-# backward form (gandanet.h GD_PAM_BWD_*): GD_PAM_BWD=0 K64 + fp32 atomics for dQ (default), 1 K64 + bf16 parts
-# (bitwise reproducible), 2 the round-1 K32 kernel with bf16 parts, 3 two kernels without scratch.
-# set_deterministic(True) moves the default from 0 to 1.
-PAM_BWD_FORM = int(os.environ.get("GD_PAM_BWD", "0"))
 PAM_SCRATCH_CAP = 40 << 30                                         # scratch of one call: at most 40 GiB
 DETERMINISTIC = False
 DET_REDUCE = "unsplit"            # how deterministic mode reduces over splits: "unsplit" or "ordered" (gd_set_det_reduce)
@@ -905,7 +897,10 @@ def gemm_nt_plan(*, B: int, M: int, N: int, kseg: int, klen: int, splits: int = 
 
 
 def pam_bwd_form() -> int:
-    return L.PAM_BWD_K64_PARTS if (DETERMINISTIC and PAM_BWD_FORM == 0) else PAM_BWD_FORM
+    """the backward form (gandanet.h GD_PAM_BWD_*) that pam_flash_bwd takes without an explicit ``form``: K64 with fp32
+    atomics for dQ, or under set_deterministic(True) K64 with bf16 parts (bitwise reproducible).  Forms 2 (the round-1 K32
+    kernel with bf16 parts) and 3 (two kernels without scratch) are reached through ``form`` only."""
+    return L.PAM_BWD_K64_PARTS if DETERMINISTIC else L.PAM_BWD_K64_ATOMIC
 
 
 def pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Npad, Cp, dqn, dkn, dv, r_alg: int = 32, c_alg: int = 0,
@@ -926,10 +921,7 @@ def pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Npad, Cp, dqn, dkn, dv
                                        _ptr(scratch), scratch_bytes, _stream()), "gd_pam_flash_bwd")
 
 
-# wide attention blocks (192 < C <= 511, gd_pam_wide_*): GD_PAM_WIDE=0 keeps them on the product chain (A/B runs)
-PAM_WIDE = os.environ.get("GD_PAM_WIDE", "1") != "0"
-
-
+# wide attention blocks (192 < C <= 511, gd_pam_wide_*)
 def pam_wide_slots(r: int) -> int:
     """q / k slots of the wide kernels: 32 while the spare slot for the running maximum fits (r <= 31), else 64"""
     return 32 if r <= 31 else 64

@@ -2,7 +2,6 @@
 BCE-with-logits / MSE criteria the notebook takes from torch.nn (GAN_DANet_train.ipynb:L190-191)."""
 from __future__ import annotations
 
-import os
 import warnings
 from typing import Optional, Sequence, Set
 
@@ -151,8 +150,6 @@ class PerceptualLoss(nn.Module):
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         from .config import operand_mode
         mode = operand_mode("vgg")
-        if mode == "x3" and not VGG_SPLIT_NHWC:
-            mode = "layers"                            # A/B: the per-layer split route (fp32 NCHW between the convs)
         if (mode in ("16", "x3") and x.shape == y.shape and x.shape[1] in (1, 3) and x.shape[2] % 8 == 0
                 and x.shape[3] % 8 == 0 and self._nhwc_plan(mode == "x3") is not None):
             return _PerceptualNhwcFn.apply(x, y, self, mode == "x3")
@@ -163,9 +160,6 @@ class PerceptualLoss(nn.Module):
         fx = self._features(x3)
         terms = [ops.l1_loss(fx[i], fy[i]) for i in sorted(self.feature_layers)]
         return ops.weighted_sum([1.0] * len(terms), terms)
-
-
-VGG_SPLIT_NHWC = os.environ.get("GD_VGG_SPLIT_NHWC", "1") != "0"
 
 
 class _PerceptualNhwcFn(torch.autograd.Function):

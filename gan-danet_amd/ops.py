@@ -11,7 +11,6 @@ CAM always runs in fp32 (its logits scale with N).
 """
 from __future__ import annotations
 
-import os
 from typing import List, Optional
 
 import torch
@@ -54,12 +53,16 @@ def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+# Test hooks, not configuration: the tests (and tools/disc_ab.py) clear one to compare a packed route against the route that
+# serves the other shapes and modes.  Nothing else sets them.
+DISC_NHWC = True          # Discriminator1's trunk as one node on pixel-major 16-bit / split activations
+CONV_WIDE_NHWC = True     # wide 3x3 convs through the packed route (_wide3x3)
+DENSE_NHWC = True         # dense-block layers on packed BN + ReLU inputs
+
+
 # =====================================================================================================
 # Discriminator1 conv trunk on pixel-major bf16      discriminator.py:60-63, 66-72
 # =====================================================================================================
-DISC_NHWC = os.environ.get("GD_DISC_NHWC", "1") != "0"
-
-
 def disc1_trunk_eligible(x: torch.Tensor, ws) -> bool:
     """16-bit or split-bf16 operand mode, the reference's channel ladder (.. -> 64 -> .. multiples of 8), at most 4 image
     channels, and a mode in which the trunk's bias sums and weight gradients are reproducible when that is asked for:
@@ -119,10 +122,7 @@ class Disc1TrunkFn(Function):
 # =====================================================================================================
 # convolution (+ bias + activation)        nn.Conv2d  (generator.py / discriminator.py / VGG)
 # =====================================================================================================
-CONV_WIDE_NHWC = os.environ.get("GD_CONV_WIDE_NHWC", "1") != "0"
-DENSE_NHWC = os.environ.get("GD_DENSE_NHWC", "1") != "0"
-PAM_CAT = os.environ.get("GD_PAM_CAT", "1") != "0"        # q / k / v projections (and their gradients) as one GEMM each
-WIDE_MIN_CIN = int(os.environ.get("GD_WIDE_MIN_CIN", "128"))     # 64 -> 64 at 512 x 512: conv time halves, the two packs eat it (measured equal)
+WIDE_MIN_CIN = 128     # 64 -> 64 at 512 x 512: conv time halves, the two packs eat it (measured equal)
 
 
 def _wide3x3(x, w, stride, pad, act, prec) -> bool:
@@ -430,7 +430,7 @@ def _cp(c: int) -> int:
 
 def _pam_wide(Cn: int, r: int) -> bool:
     """16-bit modes, 192 < C <= 511 (r <= 63): the wide flash kernels (gd_pam_wide_*) instead of the product chain"""
-    return K.PAM_WIDE and sixteen_bit("pam") and 192 < Cn <= 511 and r <= 63
+    return sixteen_bit("pam") and 192 < Cn <= 511 and r <= 63
 
 
 def _pam_f32(B: int, Cn: int, r: int, N: int) -> bool:
@@ -482,7 +482,7 @@ def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
     r = wq.shape[0]
     x3 = x.view(B, Cn, N)
     route = _pam_route(B, Cn, r, N)
-    if route != "chain" and PAM_CAT and (bq is None) == (bk is None) == (bv is None):
+    if route != "chain" and (bq is None) == (bk is None) == (bv is None):
         # q, k, v as ONE 1x1 conv over the concatenated weights: x is read once instead of three times
         wc = torch.empty(2 * r + Cn, Cn, 1, 1, device=x.device, dtype=torch.float32)
         for w_, lo in ((wq, 0), (wk, r), (wv, 2 * r)):
@@ -516,7 +516,8 @@ def _pam_forward(x, wq, bq, wk, bk, wv, bv, gamma_p, out3, prec):
             # bf16 operands: per-query softmax shift from a strided key sample, max-free sweep for logits of any magnitude
             K.pam_flash_fwd_shift(qt, kt, vn, B, N, Np, Cn, Cp, gamma_p, x3, out3, o_attn, lse, r_alg=r, v_ones=ones >= 0)
         else:
-            k_sqmax = K.pam_key_sqnorm_max(kt, N, f16) if K.PAM_NOMAX else None
+            # max_j |k_j|^2: lets the kernel drop the running maximum where the logit bound allows
+            k_sqmax = K.pam_key_sqnorm_max(kt, N, f16)
             K.pam_flash_fwd(qt, kt, vn, B, N, Np, Cn, Cp, gamma_p, x3, out3, o_attn, lse, r_alg=r, v_ones=ones >= 0, f16=f16,
                             k_sqmax=k_sqmax)
         return route, (qt, kt, kn, vt, o_attn, lse)
@@ -621,7 +622,7 @@ def _pam_backward(route, pam_saved, x, wq, wk, wv, gamma_p, d_pam, dx, prec, has
             dkn = torch.empty(B, D, Np, device=x.device, dtype=torch.float32)
             dvp = torch.empty(B, Cp, Np, device=x.device, dtype=torch.float32)
             K.pam_wide_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, D, dqn, dkn, dvp, r_alg=r, c_alg=Cn, f16=f16)
-        elif PAM_CAT and Np == N and K.pam_bwd_form() == L.PAM_BWD_K64_ATOMIC:
+        elif Np == N and K.pam_bwd_form() == L.PAM_BWD_K64_ATOMIC:
             # dq | dk | dv as row blocks of ONE buffer: the three projection data / weight / bias gradients below become
             # one GEMM each over it (dx read-modify-written once instead of three times, x read once)
             R = 64 + Cp

@@ -80,7 +80,7 @@ def test_wide_conv3x3_through_the_pixel_major_kernel(gd, shape):
     """wide 3x3 / stride 1 / pad 1 convs in 16-bit mode (ops._wide3x3: DANetAttention's fuse conv, generator.py:108) run on
     a pixel-major bf16 copy of x through the NHWC kernel with an fp32 NCHW result; forward, both gradients and the input
     given as a channel slice of a wider buffer, against ATen on the bf16-rounded operands and against the fp32-NCHW
-    patch kernel (GD_CONV_WIDE_NHWC off), which rounds the same operands"""
+    patch kernel (ops.CONV_WIDE_NHWC off), which rounds the same operands"""
     ops, _ = _ops()
     B, Cin, H, W, Cout, bias, relu = shape
     assert ops._wide3x3(torch.empty(B, Cin, H, W), torch.empty(Cout, Cin, 3, 3), 1, 1, ops.ACT_NONE, ops.L.PREC_BF16)
@@ -467,11 +467,14 @@ def test_conv3x3_stride2_patch_kernel(gd, shape):
     assert_close(outs[True][1], dwr, BF16_TOL, "stride-2 wgrad vs oracle", rell2)
 
 
-@pytest.mark.parametrize("shape", [(2, 184, 16, 16, 184), (1, 88, 8, 12, 44), (2, 520, 8, 8, 64), (1, 32, 5, 7, 24)])
+@pytest.mark.parametrize("shape", [(2, 184, 16, 16, 184), (1, 88, 8, 12, 44), (2, 520, 8, 8, 64), (1, 32, 5, 7, 24),
+                                   (1, 40, 512, 512, 72)])
 def test_conv1x1_transpose_read_kernel(gd, shape):
     """1x1 convs (projections, transitions, channel_adjust): transpose-read kernel with and without the fused
     BN-affine+ReLU prologue, forward / data gradient / weight gradient, against the oracle (bf16 operands).
-    The last shape (35 pixels) is not 16-byte friendly and must fall back to the generic kernel."""
+    (1, 32, 5, 7, 24) (35 pixels) is not 16-byte friendly and must fall back to the generic kernel.  The last shape has
+    B H W = 2^18 pixels (2048 pixel tiles), a ragged 128-row M tile (72) and Ck = 40 below one k-tile.  Forward and data
+    gradient also run with split-bf16 operands (GD_PREC_X3), both modes against the fp64 convolution of the same operands."""
     ops, K = _ops()
     from gan_danet_amd import _lib as L
     B, Cin, H, W, Cout = shape
@@ -489,6 +492,11 @@ def test_conv1x1_transpose_read_kernel(gd, shape):
     assert_close(yp, F.relu(F.conv2d(xin, w.cpu(), bias.cpu())), BF16_TOL, "1x1 fwd prologue")
     assert_close(dx, torch.nn.grad.conv2d_input((B, Cin, H, W), w.cpu(), dy.cpu()), BF16_TOL, "1x1 dgrad", rell2)
     assert_close(dw, torch.nn.grad.conv2d_weight(x.cpu(), (Cout, Cin, 1, 1), dy.cpu()), BF16_TOL, "1x1 wgrad", rell2)
+    y64 = F.conv2d(x.cpu().double(), w.cpu().double(), bias.cpu().double()).float()
+    dx64 = torch.nn.grad.conv2d_input((B, Cin, H, W), w.cpu().double(), dy.cpu().double()).float()
+    for prec, name in ((L.PREC_BF16, "bf16"), (L.PREC_X3, "x3")):
+        assert_close(K.conv2d_fwd(x, w, bias, 1, 0, prec), y64, BF16_TOL, f"1x1 fwd {name} vs fp64")
+        assert_close(K.conv2d_dgrad(dy, w, (H, W), 1, 0, prec), dx64, BF16_TOL, f"1x1 dgrad {name} vs fp64", rell2)
 
 
 # ---- pixel-major bf16 kernels of the VGG feature stack -------------------------------------------------------------

@@ -311,7 +311,7 @@ def test_denseblock_mixed_split_bf16_vs_reference_fixture(gd, golden_dir):
 def test_denseblock_bf16_pixel_major_packs_vs_reference_fixture(gd, golden_dir):
     """16-bit mode: every dense layer's conv input max(0, bn(x)) is packed once as a pixel-major bf16 copy
     (gd_pack_16_affine) that feeds the NHWC forward kernel and the weight gradient; the data gradient runs on the packed dY.
-    Against the reference fixture at the 16-bit tolerances, and against the fp32-NCHW slab path (GD_DENSE_NHWC off), which
+    Against the reference fixture at the 16-bit tolerances, and against the fp32-NCHW slab path (ops.DENSE_NHWC off), which
     rounds the same operands at the same points."""
     from gan_danet_amd.generator import DenseBlock
     from gan_danet_amd import ops

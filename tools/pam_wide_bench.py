@@ -1,5 +1,6 @@
 """Wide flash PAM (gd_pam_wide_*) against the narrow kernels, kernel level, HIP-event times (median of repeats after
-warm-up), plus one module-level A/B against the product chain (GD_PAM_WIDE=0) with time and peak memory.
+warm-up).  (The module-level A/B against the product chain is recorded in DESIGN.md section 5.4; the chain no longer serves
+these widths.)
     python tools/pam_wide_bench.py --out profiles/r04_pam_wide.json
 Work per image: 2 N^2 (r + C) forward, twice that backward; share of the 2.5 PF dense 16-bit peak."""
 import argparse
@@ -11,7 +12,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-import gan_danet_amd as gd  # noqa: E402
+import gan_danet_amd  # noqa: E402,F401
 from gan_danet_amd import kern as K, ops  # noqa: E402
 
 PEAK = 2.5e15
@@ -23,8 +24,6 @@ ap.add_argument("--channels", default="184,224,256,352")
 ap.add_argument("--precisions", default="bf16,fp16")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=2)
-ap.add_argument("--ab-tile", type=int, default=128, help="0: skip the product-chain A/B")
-ap.add_argument("--ab-channels", type=int, default=224)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 dev = torch.device("cuda")
@@ -74,7 +73,7 @@ def problem(B, C, N, f16):
             K.pam_wide_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, D, dqn, dkn, dv, r_alg=r, c_alg=C, f16=f16)
     else:
         def fwd():
-            k_sqmax = K.pam_key_sqnorm_max(kt, N, f16) if K.PAM_NOMAX else None
+            k_sqmax = K.pam_key_sqnorm_max(kt, N, f16)
             K.pam_flash_fwd(qt, kt, vn, B, N, Np, C, Cp, gamma, x, out, o_attn, lse, r_alg=r, v_ones=ones >= 0, f16=f16,
                             k_sqmax=k_sqmax)
 
@@ -102,32 +101,6 @@ for prec in a.precisions.split(","):
         del fwd, bwd
         torch.cuda.empty_cache()
 
-# module-level A/B: PAMModule(C) forward + backward, product chain (GD_PAM_WIDE=0) against the wide kernels
-from gan_danet_amd.generator import PAMModule  # noqa: E402
-C, hw = a.ab_channels, a.ab_tile
-m = PAMModule(C).to(dev).train()
-x = torch.randn(1, C, hw, hw, device=dev).requires_grad_(True)
-go = torch.randn(1, C, hw, hw, device=dev)
-ab = dict(C=C, N=hw * hw, B=1, prec="bf16")
-
-
-def step():
-    with gd.precision("bf16"):
-        m(x).backward(go)
-
-
-for name, on in ((("chain", False), ("wide", True)) if hw else ()):
-    K.PAM_WIDE = on
-    step()
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    step()
-    torch.cuda.synchronize()
-    ab[f"{name}_peak_gib"] = round((torch.cuda.max_memory_allocated() - base) / 2**30, 3)
-    ab[f"{name}_fwdbwd_ms"] = round(timed(step, a.reps, 1), 3)
-K.PAM_WIDE = True
-print(json.dumps(dict(ab=ab)), flush=True)
 if a.out:
     with open(a.out, "w") as f:
-        json.dump(dict(device=torch.cuda.get_device_name(0), peak_flops=PEAK, rows=rows, ab=ab), f, indent=1)
+        json.dump(dict(device=torch.cuda.get_device_name(0), peak_flops=PEAK, rows=rows), f, indent=1)
