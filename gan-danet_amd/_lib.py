@@ -24,6 +24,8 @@ ZOOM_MIRROR, ZOOM_NEAREST = 0, 1   # GD_ZOOM_*
 FREQ_MAX_BINS, FREQ_MAX_TABLE_BYTES = 33, 16 << 20   # GD_FREQ_MAX_BINS, GD_FREQ_MAX_TABLE_BYTES
 ZONE_MAX, ZONE_EDGE_CHUNK = 32, 512   # GD_ZONE_MAX, GD_ZONE_EDGE_CHUNK
 STL_MAX_T = 2048                 # GD_STL_MAX_T
+SKILL_MAPS = ("n", "mean_p", "mean_t", "bias", "rmse", "mae", "std_p", "std_t", "cc", "nse", "kge", "crmsd")   # GD_SKILL_*: bit k of `which`
+LSTSQ_MAX_P = 8                  # GD_LSTSQ_MAX_P
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -199,6 +201,15 @@ SIGNATURES = {
     "gd_zone_mean": (_i, [_p, _i, _l, _l, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "gd_stl_decompose": (_i, [_p, _i, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "gd_stl_decompose_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "gd_series_stats": (_i, [_p, _p, _i, _l, _l, _p, _i, _p, _i, _p]),
+    "gd_series_stats_host": (_i, [_p, _p, _i, _l, _l, _p, _i, _p, _i]),
+    "gd_series_skill": (_i, [_p, _l, _i, _i, _p, _p]),
+    "gd_series_skill_host": (_i, [_p, _l, _i, _i, _p]),
+    "gd_series_lstsq": (_i, [_p, _i, _l, _l, _p, _i, _p, _p, _p, _p]),
+    "gd_series_lstsq_host": (_i, [_p, _i, _l, _l, _p, _i, _p, _p, _p]),
+    "gd_harmonic_finalize": (_i, [_p, _i, _l, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p]),
+    "gd_block_mean": (_i, [_p, _i, _l, _l, _l, _i, _i, _p, _i, _p, _p, _p]),
+    "gd_block_mean_host": (_i, [_p, _i, _l, _l, _l, _i, _i, _p, _i, _p, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

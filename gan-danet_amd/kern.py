@@ -1821,3 +1821,171 @@ def stl_decompose_host(x, p: dict):
     L.check(lib().gd_stl_decompose_host(x.ctypes.data, L.FILTER_F64 if x.dtype == np.float64 else L.FILTER_F32, x.shape[0], x.shape[1],
                                         *_stl_args(p), *[o.ctypes.data for o in outs]), "gd_stl_decompose_host")
     return tuple(outs)
+
+
+# ---- per-pixel time series (include/gandanet.h, "Per-pixel time series"; series.hip) -----------------------------------------
+def skill_which(metrics) -> int:
+    """the ``which`` bit set of gd_series_skill for an iterable of map names (L.SKILL_MAPS)"""
+    which = 0
+    for name in metrics:
+        if name not in L.SKILL_MAPS:
+            raise L.GandanetError(f"unknown skill map {name!r}: expected one of {L.SKILL_MAPS}")
+        which |= 1 << L.SKILL_MAPS.index(name)
+    if which == 0:
+        raise L.GandanetError("no skill map selected")
+    return which
+
+
+def _series_2d(x: Tensor, name: str) -> int:
+    dt = _filter_dtype(x, name)
+    if x.dim() != 2 or x.numel() == 0:
+        raise L.GandanetError(f"{name}: expected a dense, non-empty (T, M) tensor, got {tuple(x.shape)}")
+    return dt
+
+
+def series_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] = None, skip_nan: bool = True,
+                 accumulate: bool = False) -> Tensor:
+    """the records of the M series of ``pred`` against ``truth`` (dense fp32 / fp64 (T, M), series m at ``[:, m]``) into
+    ``rec`` (8, M) fp64; ``mask``: M uint8, 0 = skip the series; ``accumulate`` continues from the records in ``rec``.  No
+    host sync."""
+    dt = _series_2d(pred, "series_stats pred")
+    if _series_2d(truth, "series_stats truth") != dt or truth.shape != pred.shape:
+        raise L.GandanetError(f"series_stats: pred {tuple(pred.shape)} {pred.dtype} vs truth {tuple(truth.shape)} {truth.dtype}")
+    T, M = pred.shape
+    _dense(rec, "series records", torch.float64)
+    if tuple(rec.shape) != (8, M):
+        raise L.GandanetError(f"series_stats: the records are (8, {M}) float64, got {tuple(rec.shape)}")
+    mask = _eval_mask(mask, M)
+    L.check(lib().gd_series_stats(_ptr(pred), _ptr(truth), dt, T, M, _ptr(mask), L.EVAL_SKIP_NAN if skip_nan else 0, _ptr(rec),
+                                  int(accumulate), _stream()), "gd_series_stats")
+    return rec
+
+
+def series_skill(rec: Tensor, metrics, ddof: int = 0) -> Tensor:
+    """the maps named by ``metrics`` from (8, M) records: a new (len(set(metrics)), M) fp64 tensor, the maps in the order of
+    L.SKILL_MAPS"""
+    _dense(rec, "series records", torch.float64)
+    if rec.dim() != 2 or rec.shape[0] != 8 or rec.shape[1] == 0:
+        raise L.GandanetError(f"series_skill: the records are (8, M) float64, got {tuple(rec.shape)}")
+    which = skill_which(metrics)
+    M = rec.shape[1]
+    out = torch.empty((bin(which).count("1"), M), device=rec.device, dtype=torch.float64)
+    L.check(lib().gd_series_skill(_ptr(rec), M, int(ddof), which, _ptr(out), _stream()), "gd_series_skill")
+    return out
+
+
+def series_lstsq(x: Tensor, basis: Tensor, want_rss: bool = True) -> Tuple[Tensor, Optional[Tensor], Tensor]:
+    """least squares of the M series of ``x`` (dense fp32 / fp64 (T, M)) against ``basis`` (T, P) fp64, NaN samples left
+    out: new fp64 tensors (coef (P, M), rss (M) or None, n (M))"""
+    dt = _series_2d(x, "series_lstsq input")
+    T, M = x.shape
+    _dense(basis, "series_lstsq basis", torch.float64)
+    if basis.dim() != 2 or basis.shape[0] != T or not 1 <= basis.shape[1] <= L.LSTSQ_MAX_P:
+        raise L.GandanetError(f"series_lstsq: the basis is ({T}, P) float64 with 1 <= P <= {L.LSTSQ_MAX_P}, got {tuple(basis.shape)}")
+    P = basis.shape[1]
+    coef = torch.empty((P, M), device=x.device, dtype=torch.float64)
+    rss = torch.empty(M, device=x.device, dtype=torch.float64) if want_rss else None
+    n = torch.empty(M, device=x.device, dtype=torch.float64)
+    L.check(lib().gd_series_lstsq(_ptr(x), dt, T, M, _ptr(basis), P, _ptr(coef), _ptr(rss), _ptr(n), _stream()), "gd_series_lstsq")
+    return coef, rss, n
+
+
+def harmonic_finalize(coef: Tensor, K: int, has_trend: bool, tau_scale: float, rss: Optional[Tensor], n: Optional[Tensor]):
+    """(amp (K, M), phase (K, M), slope (M) or None, rms (M) or None) from the coefficient planes (P, M) of a fit against
+    1, [tau], cos, sin, ...; all fp64, new tensors"""
+    _dense(coef, "harmonic coefficients", torch.float64)
+    P, M = coef.shape
+    dev = coef.device
+    amp = torch.empty((K, M), device=dev, dtype=torch.float64)
+    phase = torch.empty((K, M), device=dev, dtype=torch.float64)
+    slope = torch.empty(M, device=dev, dtype=torch.float64) if has_trend else None
+    rms = torch.empty(M, device=dev, dtype=torch.float64) if rss is not None else None
+    L.check(lib().gd_harmonic_finalize(_ptr(coef), P, M, int(K), int(has_trend), float(tau_scale), _ptr(rss), _ptr(n),
+                                       _ptr(amp) if K else None, _ptr(phase) if K else None, _ptr(slope), _ptr(rms), _stream()),
+            "gd_harmonic_finalize")
+    return amp, phase, slope, rms
+
+
+def block_mean(x: Tensor, fy: int, fx: int, weights: Optional[Tensor] = None, min_count: int = 1) -> Tuple[Tensor, Tensor]:
+    """NaN-aware mean of every ``fy`` x ``fx`` block of the last two dims of the dense fp32 / fp64 ``x`` (..., H, W);
+    ``weights``: (H, W) fp64 or None.  Returns (mean in the dtype of ``x``, count int32), shaped (..., H / fy, W / fx)."""
+    dt = _filter_dtype(x, "block_mean input")
+    if x.dim() < 2 or x.numel() == 0:
+        raise L.GandanetError(f"block_mean: expected a non-empty (..., H, W) tensor, got {tuple(x.shape)}")
+    H, W = x.shape[-2:]
+    fy, fx = int(fy), int(fx)
+    if fy < 1 or fx < 1 or H % fy or W % fx:
+        raise L.GandanetError(f"block_mean: blocks of {fy} x {fx} do not divide ({H}, {W})")
+    if weights is not None:
+        _dense(weights, "block_mean weights", torch.float64)
+        if tuple(weights.shape) != (H, W):
+            raise L.GandanetError(f"block_mean: weights {tuple(weights.shape)} vs planes ({H}, {W})")
+    shape = tuple(x.shape[:-2]) + (H // fy, W // fx)
+    out = torch.empty(shape, device=x.device, dtype=x.dtype)
+    count = torch.empty(shape, device=x.device, dtype=torch.int32)
+    L.check(lib().gd_block_mean(_ptr(x), dt, math.prod(x.shape[:-2]), H, W, fy, fx, _ptr(weights), int(min_count), _ptr(out),
+                                _ptr(count), _stream()), "gd_block_mean")
+    return out, count
+
+
+def _host_f(x, name: str):
+    import numpy as np
+    x = np.asarray(x)
+    if x.dtype not in (np.float32, np.float64) or x.size == 0:
+        raise L.GandanetError(f"{name}: expected a non-empty float32 / float64 array, got {x.dtype} {x.shape}")
+    return np.ascontiguousarray(x), (L.FILTER_F64 if x.dtype == np.float64 else L.FILTER_F32)
+
+
+def series_stats_host(pred, truth, mask=None, skip_nan: bool = True, rec=None):
+    """``series_stats`` on HOST arrays (plain C++ loops over the same arithmetic, no GPU): the (8, M) records, continued
+    from ``rec`` when one is given"""
+    import numpy as np
+    pred, dt = _host_f(pred, "series_stats_host")
+    truth, dt2 = _host_f(truth, "series_stats_host")
+    if dt != dt2 or pred.shape != truth.shape or pred.ndim != 2:
+        raise L.GandanetError(f"series_stats_host: pred {pred.dtype} {pred.shape} vs truth {truth.dtype} {truth.shape}")
+    T, M = pred.shape
+    acc = rec is not None
+    rec = np.ascontiguousarray(rec, dtype=np.float64).copy() if acc else np.empty((8, M))
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    L.check(lib().gd_series_stats_host(pred.ctypes.data, truth.ctypes.data, dt, T, M, None if mask is None else mask.ctypes.data,
+                                       L.EVAL_SKIP_NAN if skip_nan else 0, rec.ctypes.data, int(acc)), "gd_series_stats_host")
+    return rec
+
+
+def series_skill_host(rec, metrics, ddof: int = 0):
+    """``series_skill`` on (8, M) HOST records: a dict name -> (M) array"""
+    import numpy as np
+    rec = np.ascontiguousarray(rec, dtype=np.float64)
+    which = skill_which(metrics)
+    names = [nm for nm in L.SKILL_MAPS if which >> L.SKILL_MAPS.index(nm) & 1]
+    out = np.empty((len(names), rec.shape[1]))
+    L.check(lib().gd_series_skill_host(rec.ctypes.data, rec.shape[1], int(ddof), which, out.ctypes.data), "gd_series_skill_host")
+    return dict(zip(names, out))
+
+
+def series_lstsq_host(x, basis):
+    """``series_lstsq`` on HOST arrays: (coef (P, M), rss (M), n (M))"""
+    import numpy as np
+    x, dt = _host_f(x, "series_lstsq_host")
+    basis = np.ascontiguousarray(basis, dtype=np.float64)
+    T, M = x.shape
+    P = basis.shape[1]
+    coef, rss, n = np.empty((P, M)), np.empty(M), np.empty(M)
+    L.check(lib().gd_series_lstsq_host(x.ctypes.data, dt, T, M, basis.ctypes.data, P, coef.ctypes.data, rss.ctypes.data, n.ctypes.data),
+            "gd_series_lstsq_host")
+    return coef, rss, n
+
+
+def block_mean_host(x, fy: int, fx: int, weights=None, min_count: int = 1):
+    """``block_mean`` on a HOST array (..., H, W): (mean, count)"""
+    import numpy as np
+    x, dt = _host_f(x, "block_mean_host")
+    H, W = x.shape[-2:]
+    weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    planes = math.prod(x.shape[:-2])
+    shape = tuple(x.shape[:-2]) + (H // max(fy, 1), W // max(fx, 1))
+    out, count = np.empty(shape, dtype=x.dtype), np.empty(shape, dtype=np.int32)
+    L.check(lib().gd_block_mean_host(x.ctypes.data, dt, planes, H, W, int(fy), int(fx), None if weights is None else weights.ctypes.data,
+                                     int(min_count), out.ctypes.data, count.ctypes.data), "gd_block_mean_host")
+    return out, count

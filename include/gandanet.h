@@ -887,6 +887,75 @@ int gd_stl_decompose_host(const void* x, int dtype, long T, long M, int period, 
                           int seasonal_deg, int trend_deg, int low_pass_deg, int inner_iter, int outer_iter, void* trend_out,
                           void* seasonal_out, void* resid_out, void* weights_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pixel time series (series.hip, csrc/series_core.h): skill of one cube against another along the time axis of every
+ * pixel, a masked least-squares fit of every pixel's series against a common design matrix (trend and annual /
+ * semi-annual harmonics) and the NaN-aware block mean that takes the 0.05 degree product back to the 0.25 degree grid.
+ * The reference gestures at these: the map comparison of test.ipynb `_plot_spatial_distribution`, `pearsonr` of two
+ * series, and taylorDiagram.py:151-159 (std with ddof 1 and corrcoef).
+ * A series is a column of a dense (T, M) array, series m at x[t * M + m], as for gd_stl_decompose.  Storage fp32 (dtype 0)
+ * or fp64 (dtype 1), all arithmetic fp64, one rounding to the output.  One thread owns a series and walks t in ascending
+ * order, neighbouring threads own neighbouring m (every time step is one coalesced row read); T is never split, so a
+ * series' result depends on the series and the parameters alone, not on M, its column or the launch.  The caller owns all
+ * memory, nothing is allocated, nothing waits for the device; no global atomics, no workspace.  Pointers need element
+ * alignment only.  Every device entry but gd_harmonic_finalize has a host twin (`_host`, no GPU call, every pointer in
+ * HOST memory) that runs the same operations in the same order (series_core.h): records, maps, coefficients, rss and
+ * block means agree bit for bit.
+ * ---------------------------------------------------------------------------------------- */
+/* the maps of gd_series_skill: bit k of `which` selects map k; the selected maps are written in ascending k */
+enum { GD_SKILL_N = 0, GD_SKILL_MEAN_P = 1, GD_SKILL_MEAN_T = 2, GD_SKILL_BIAS = 3, GD_SKILL_RMSE = 4, GD_SKILL_MAE = 5,
+       GD_SKILL_STD_P = 6, GD_SKILL_STD_T = 7, GD_SKILL_CC = 8, GD_SKILL_NSE = 9, GD_SKILL_KGE = 10, GD_SKILL_CRMSD = 11,
+       GD_SKILL_MAPS = 12 };
+#define GD_LSTSQ_MAX_P 8 /* columns of the design matrix: P (P + 1) / 2 + P = 44 fp64 accumulators per thread at the cap */
+/* The RECORD ("Evaluation") of every series: rec is (8, M) doubles, planar, plane k of series m at rec[k * M + m].  The
+ * update is sequential, one pair at a time in ascending t (the single-pair form of the merge stated under "Evaluation"):
+ *   n' = n + 1, dp = p - mean_p, dt = t - mean_t, f = n / n', mean += d / n', M2_p += dp^2 f, M2_t += dt^2 f,
+ *   C += dp dt f, sum|d| += |p - t|, sum d^2 += (p - t)^2.
+ * mask: NULL, or M bytes; a series whose byte is 0 is skipped: its record is zeroed (n = 0), or left as it is under
+ * `accumulate`.  flags: GD_EVAL_SKIP_NAN drops a pair with a NaN on either side, without it NaNs propagate.
+ * accumulate != 0 continues from the record in rec (n <= 0 there counts as empty), so a cube may be fed in chunks of time
+ * steps: the recurrence being sequential, chunks give the same bits as one call. */
+int gd_series_stats(const void* pred, const void* truth, int dtype, long T, long M, const unsigned char* mask, int flags,
+                    double* rec, int accumulate, void* stream);
+int gd_series_stats_host(const void* pred, const void* truth, int dtype, long T, long M, const unsigned char* mask, int flags,
+                         double* rec, int accumulate);
+/* The maps selected by `which` from the records, M doubles each, the j-th selected map at out[j * M + m]:
+ *   n, mean_p, mean_t, bias = mean_p - mean_t, rmse = sqrt(sum d^2 / n), mae = sum|d| / n,
+ *   std_p, std_t = sqrt(M2 / (n - ddof)) (ddof 0 as np.std, 1 as taylorDiagram.py:151; NaN when n <= ddof),
+ *   cc = C / sqrt(M2_p M2_t) clipped to [-1, 1] as np.corrcoef, NaN at zero variance,
+ *   nse = 1 - sum d^2 / M2_t with the r2_score rules of gd_eval_merge_host at M2_t == 0,
+ *   kge = 1 - sqrt((cc - 1)^2 + (sqrt(M2_p / M2_t) - 1)^2 + (mean_p / mean_t - 1)^2)  (the std ratio is free of ddof),
+ *   crmsd = sqrt((M2_p + M2_t - 2 C) / n), the centred RMS difference of the Taylor diagram (clamped at 0).
+ * n == 0 gives NaN everywhere except n.  A record of gd_eval_stats is an (8, 1) record set. */
+int gd_series_skill(const double* rec, long M, int ddof, int which, double* out, void* stream);
+int gd_series_skill_host(const double* rec, long M, int ddof, int which, double* out);
+/* Masked linear least squares of every series against a common design matrix: basis is (T, P) doubles, row t at
+ * basis[t * P], 1 <= P <= GD_LSTSQ_MAX_P; a sample that is NaN is left out of that series' fit.  Per series: a first pass
+ * accumulates the P (P + 1) / 2 entries of A^T A and the P of A^T y in registers (the basis rows are the same for every
+ * lane and come through the scalar cache), a Cholesky solve in fp64, and a second pass over the series that sums the
+ * squared residuals y - A c directly (y^T y - c^T A^T y cancels).  coef: (P, M) planar.  rss, n_out: (M) doubles, either
+ * may be NULL; n_out is the number of samples that entered the fit.  With fewer valid samples than P, or a pivot
+ * <= P 2^-52 times its diagonal entry, coef and rss are NaN (n_out stays the valid count). */
+int gd_series_lstsq(const void* x, int dtype, long T, long M, const double* basis, int P, double* coef, double* rss,
+                    double* n_out, void* stream);
+int gd_series_lstsq_host(const void* x, int dtype, long T, long M, const double* basis, int P, double* coef, double* rss,
+                         double* n_out);
+/* From the coefficient planes of a fit against the columns 1, [tau], cos w_1 t, sin w_1 t, ... cos w_K t, sin w_K t
+ * (P = 1 + has_trend + 2 K, 0 <= K <= 3): amp (K, M) = hypot(c_k, s_k) and phase (K, M) = atan2(s_k, c_k), so that
+ * c cos wt + s sin wt = amp cos(wt - phase); slope (M) = coef[1] * tau_scale (has_trend only); rms (M) = sqrt(rss / n).
+ * Every output may be NULL; rms needs rss and n.  Device only: hypot and atan2 are the device library's. */
+int gd_harmonic_finalize(const double* coef, int P, long M, int K, int has_trend, double tau_scale, const double* rss,
+                         const double* n, double* amp, double* phase, double* slope, double* rms, void* stream);
+/* NaN-aware mean of every fy x fx block of the last two axes of x (planes, H, W): the inverse of the notebook's
+ * np.repeat(np.repeat(bias, 4, 1), 4, 2).  H % fy == 0 and W % fx == 0.  weights: NULL, or (H, W) doubles shared by all
+ * planes (for instance cos(lat)).  out (planes, H / fy, W / fx), in the input dtype: sum w v / sum w over the non-NaN
+ * members of the block, added in row-major order; NaN when fewer than min_count members contribute or the weight sum is
+ * 0.  count (int32, may be NULL): the contributors. */
+int gd_block_mean(const void* x, int dtype, long planes, long H, long W, int fy, int fx, const double* weights,
+                  int min_count, void* out, int* count, void* stream);
+int gd_block_mean_host(const void* x, int dtype, long planes, long H, long W, int fy, int fx, const double* weights,
+                       int min_count, void* out, int* count);
+
 #ifdef __cplusplus
 }
 #endif
