@@ -21,6 +21,8 @@ from . import stl
 from .stl import detrend_and_compare, stl_decompose
 from . import timeseries
 from .timeseries import SeriesSkill, coarsen, consistency, harmonic_fit, lstsq_series, skill_maps, taylor_stats
+from . import trend
+from .trend import TrendTest, mann_kendall, normal_quantile, sen_slope, trend_test
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)

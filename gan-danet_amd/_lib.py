@@ -26,6 +26,9 @@ ZONE_MAX, ZONE_EDGE_CHUNK = 32, 512   # GD_ZONE_MAX, GD_ZONE_EDGE_CHUNK
 STL_MAX_T = 2048                 # GD_STL_MAX_T
 SKILL_MAPS = ("n", "mean_p", "mean_t", "bias", "rmse", "mae", "std_p", "std_t", "cc", "nse", "kge", "crmsd")   # GD_SKILL_*: bit k of `which`
 LSTSQ_MAX_P = 8                  # GD_LSTSQ_MAX_P
+TREND_MAX_T = 2048               # GD_TREND_MAX_T
+TREND_MAPS = ("n", "s", "var_s", "z", "p", "tau", "slope", "intercept", "slope_lo", "slope_hi")   # GD_TREND_*: plane k of `out`
+TREND_SEN, TREND_CI, TREND_CONTINUITY = 1, 2, 4   # GD_TREND_SEN, GD_TREND_CI, GD_TREND_CONTINUITY
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -210,6 +213,8 @@ SIGNATURES = {
     "gd_harmonic_finalize": (_i, [_p, _i, _l, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p]),
     "gd_block_mean": (_i, [_p, _i, _l, _l, _l, _i, _i, _p, _i, _p, _p, _p]),
     "gd_block_mean_host": (_i, [_p, _i, _l, _l, _l, _i, _i, _p, _i, _p, _p]),
+    "gd_trend_test": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p, _p]),
+    "gd_trend_test_host": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

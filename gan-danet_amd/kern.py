@@ -1989,3 +1989,48 @@ def block_mean_host(x, fy: int, fx: int, weights=None, min_count: int = 1):
     L.check(lib().gd_block_mean_host(x.ctypes.data, dt, planes, H, W, int(fy), int(fx), None if weights is None else weights.ctypes.data,
                                      int(min_count), out.ctypes.data, count.ctypes.data), "gd_block_mean_host")
     return out, count
+
+
+# ---- per-pixel trend tests (include/gandanet.h, "Per-pixel trend tests"; trend.hip) ------------------------------------------
+def trend_flags(sen: bool, ci: bool, continuity: bool) -> int:
+    return (L.TREND_SEN if sen else 0) | (L.TREND_CI if ci else 0) | (L.TREND_CONTINUITY if continuity else 0)
+
+
+def trend_test(x: Tensor, times: Tensor, period: int = 0, mask: Optional[Tensor] = None, flags: int = L.TREND_CONTINUITY,
+               zq: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """Mann-Kendall / Theil-Sen of the M series of a dense fp32 / fp64 ``x`` (T, M) at the fp64 device ``times`` (T), which
+    the caller has checked to be finite and increasing; ``period`` 0 = not seasonal; ``mask``: M uint8.  The planes
+    (L.TREND_MAPS) go into ``out`` (10, M) fp64, a new tensor unless one is given; those that ``flags`` does not ask for are
+    left as they are.  No host sync."""
+    dt = _series_2d(x, "trend_test input")
+    T, M = x.shape
+    _dense(times, "trend_test times", torch.float64)
+    if times.dim() != 1 or times.shape[0] != T:
+        raise L.GandanetError(f"trend_test: {tuple(times.shape)} times for {T} samples")
+    if out is None:
+        out = torch.empty((len(L.TREND_MAPS), M), device=x.device, dtype=torch.float64)
+    _dense(out, "trend_test output", torch.float64)
+    if tuple(out.shape) != (len(L.TREND_MAPS), M):
+        raise L.GandanetError(f"trend_test: the output is ({len(L.TREND_MAPS)}, {M}) float64, got {tuple(out.shape)}")
+    mask = _eval_mask(mask, M)
+    L.check(lib().gd_trend_test(_ptr(x), dt, T, M, _ptr(times), int(period), _ptr(mask), int(flags), float(zq), _ptr(out), _stream()),
+            "gd_trend_test")
+    return out
+
+
+def trend_test_host(x, times, period: int = 0, mask=None, flags: int = L.TREND_CONTINUITY, zq: float = 0.0, out=None):
+    """``trend_test`` on HOST arrays (plain C++ over the same per-pair arithmetic; the order statistics by sorting the
+    stored slopes): the (10, M) planes"""
+    import numpy as np
+    x, dt = _host_f(x, "trend_test_host")
+    if x.ndim != 2:
+        raise L.GandanetError(f"trend_test_host: expected a (T, M) array, got {x.shape}")
+    T, M = x.shape
+    times = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    if times.size != T:
+        raise L.GandanetError(f"trend_test_host: {times.size} times for {T} samples")
+    out = np.empty((len(L.TREND_MAPS), M)) if out is None else out
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    L.check(lib().gd_trend_test_host(x.ctypes.data, dt, T, M, times.ctypes.data, int(period), None if mask is None else mask.ctypes.data,
+                                     int(flags), float(zq), out.ctypes.data), "gd_trend_test_host")
+    return out

@@ -956,6 +956,49 @@ int gd_block_mean(const void* x, int dtype, long planes, long H, long W, int fy,
 int gd_block_mean_host(const void* x, int dtype, long planes, long H, long W, int fy, int fx, const double* weights,
                        int min_count, void* out, int* count);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pixel trend tests (trend.hip, csrc/trend_core.h): the Mann-Kendall test and the Theil-Sen slope with its confidence
+ * interval for every series of a (T, M) cube, plain or in the seasonal form of Hirsch and Slack -- the significance and the
+ * robust slope that a GRACE trend map carries.  scipy.stats.theilslopes (method 'separate') and scipy.stats.kendalltau
+ * compute the same quantities with the same arithmetic; slope, intercept, the interval and tau equal theirs bit for bit.
+ * The layout is that of the section above: series m of a dense (T, M) array at x[t * M + m], storage fp32 (dtype 0) or
+ * fp64 (dtype 1), all arithmetic fp64 with every operation rounded on its own.  2 <= T <= GD_TREND_MAX_T.  times: T
+ * doubles, finite and strictly increasing (the device entry does not look: its caller checks; the host twin does).  NaN
+ * samples are dropped from their series; a series that holds an infinity has unspecified outputs.  mask: NULL, or M bytes,
+ * 0 = leave the series out (n = 0).
+ * For one series with the valid samples (t_k, y_k), k = 0 .. n - 1, in time order:
+ *   s      = sum over i < j of sign(y_j - y_i);
+ *   var_s  = (1.0 / 18.0) * (n (n - 1)(2 n + 5) - sum over samples of (c_i - 1)(2 c_i + 5)), c_i the samples equal to y_i;
+ *   z      = (s - sgn(s)) / sqrt(var_s) under GD_TREND_CONTINUITY, else s / sqrt(var_s); NaN at var_s = 0, 0 at s = 0;
+ *   p      = erfc(|z| * 0.7071067811865476), two-sided;
+ *   tau    = s / sqrt(tot) / sqrt(tot - ytie) clipped to [-1, 1] (tau-b with tie-free times), tot = n (n - 1) / 2,
+ *            ytie = sum over tie groups of c (c - 1) / 2; NaN when ytie = tot;
+ *   slope  = the median of the nt = tot values (y_j - y_i) / (t_j - t_i), i < j (zeros as +0.0): (a + b) * 0.5 of the
+ *            order statistics (nt - 1) / 2 and nt / 2;
+ *   intercept = median(y) - slope * median(t);
+ *   slope_lo, slope_hi = the order statistics Rl = max(rint((nt + zq sigma) / 2) - 1, 0) and
+ *            Ru = min(rint((nt - zq sigma) / 2), nt - 1), sigma = sqrt(var_s), rint to even; zq is the normal quantile of
+ *            alpha / 2 (negative), computed by the caller.
+ * period >= 2 (0 = none): sample index k of the T belongs to season k mod period; only pairs inside a season count, ties
+ * are counted inside a season, s, n (n - 1)(2 n + 5), the tie sum, tot, ytie and nt are sums over the seasons, and slope
+ * and interval are order statistics of the pooled slopes; the medians of y and t are over all valid samples.
+ * n < 2: n is exact, s = 0, everything else NaN.  nt = 0 (no season with two samples): slope .. slope_hi are NaN.
+ * out: planar doubles, map k of series m at out[k * M + m], k as below.  flags: GD_TREND_SEN computes slope and
+ * intercept, GD_TREND_CI (needs SEN) the interval; planes that were not asked for are left untouched.
+ * One wave owns a series, its samples in LDS; the sums are integers; the order statistics are found by an exact radix
+ * select on the monotone 64-bit key of the slope, whose every pass recomputes the slopes: no storage proportional to T^2,
+ * no workspace, no global atomics, and a series' result depends on the series and the parameters alone.  The host twin
+ * sorts the stored slopes of a series instead and agrees bit for bit on every map but p (each side's erfc).
+ * ---------------------------------------------------------------------------------------- */
+#define GD_TREND_MAX_T 2048
+enum { GD_TREND_N = 0, GD_TREND_S = 1, GD_TREND_VAR_S = 2, GD_TREND_Z = 3, GD_TREND_P = 4, GD_TREND_TAU = 5, GD_TREND_SLOPE = 6,
+       GD_TREND_INTERCEPT = 7, GD_TREND_SLOPE_LO = 8, GD_TREND_SLOPE_HI = 9, GD_TREND_MAPS = 10 };
+enum { GD_TREND_SEN = 1, GD_TREND_CI = 2, GD_TREND_CONTINUITY = 4 };
+int gd_trend_test(const void* x, int dtype, long T, long M, const double* times, int period, const unsigned char* mask,
+                  int flags, double zq, double* out, void* stream);
+int gd_trend_test_host(const void* x, int dtype, long T, long M, const double* times, int period, const unsigned char* mask,
+                       int flags, double zq, double* out);
+
 #ifdef __cplusplus
 }
 #endif
