@@ -11,8 +11,10 @@ constexpr int CHUNK = 16384;  // elements of one channel plane per workgroup
 static inline int chunks_per_image(long HW) { return (int)((HW + CHUNK - 1) / CHUNK); }
 
 // ---- statistics ---------------------------------------------------------------------------------
-// partial (n, mean, M2) per (c, part); sums are taken relative to the first element of the run so
-// that E[x^2]-E[x]^2 style cancellation cannot happen even for |mean| >> std.
+// partial (n, mean, M2) per (c, part); sums are taken relative to a shift near the mean of the run so that
+// E[x^2]-E[x]^2 style cancellation cannot happen even for |mean| >> std.  The shift is the first element plus the
+// mean of (x - first element) over the run's first 256 elements: one outlier there (the first element is a corner
+// pixel) moves it by 1/256 of its distance, and a constant run still gives shift == x exactly, so M2 == 0 exactly.
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, long x_bs, int C, long HW,
                                                         int cpi, float* __restrict__ ws) {
     __shared__ float red[8];
@@ -22,7 +24,9 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
     const long i0 = (long)j * CHUNK;
     const long i1 = min(HW, i0 + (long)CHUNK);
     const float* p = x + (long)b * x_bs + (long)c * HW;
-    const float shift = p[i0];
+    const float p0 = p[i0];
+    const long nh = min(i1 - i0, 256L);
+    const float shift = p0 + gd_block_sum(threadIdx.x < nh ? p[i0 + threadIdx.x] - p0 : 0.f, red) / (float)nh;
     float s1 = 0.f, s2 = 0.f;
     for (long i = i0 + threadIdx.x; i < i1; i += 256) {
         const float v = p[i] - shift;
@@ -33,31 +37,35 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
     s2 = gd_block_sum(s2, red);
     if (threadIdx.x == 0) {
         const float n = (float)(i1 - i0);
-        float* o = ws + ((long)c * gridDim.y + part) * 3;
+        // the mean goes out as two floats, shift + s1 / n: rounded to one float it would be off by up to half an ulp
+        // of |mean|, which the merge turns into an M2 error of order n_c |m_c - mu| ulp(mean) when |mean| >> std
+        float* o = ws + ((long)c * gridDim.y + part) * 4;
         o[0] = n;
-        o[1] = shift + s1 / n;
+        o[1] = shift;
         o[2] = fmaxf(s2 - s1 * s1 / n, 0.f);
+        o[3] = s1 / n;
     }
 }
 
 // Chan merge (fp64) of `parts` (count, mean, M2) records of a channel; record i of channel c sits at
-// ws[(c * c_stride + i * p_stride) * 3] (the kernel's own partials: c_stride = parts, p_stride = 1; the all-gathered
-// per-rank records of SyncBN, (world, C, 3): c_stride = 1, p_stride = C).  stats_out != NULL: the merged record is
+// ws[(c * c_stride + i * p_stride) * rec] (the kernel's own partials: c_stride = parts, p_stride = 1, rec = 4, the
+// mean being w[1] + w[3]; the all-gathered per-rank records of SyncBN, (world, C, 3): c_stride = 1, p_stride = C,
+// rec = 3).  stats_out != NULL: the merged record is
 // written there instead of mean / invstd (the local half of SyncBN).
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ ws, int parts, long c_stride,
-                                                         long p_stride, float eps, float momentum,
+                                                         long p_stride, int rec, float eps, float momentum,
                                                          float* __restrict__ mean, float* __restrict__ invstd,
                                                          float* running_mean, float* running_var,
                                                          float* __restrict__ stats_out) {
     __shared__ double redd[4];
     const int c = blockIdx.x;
-    const float* w0 = ws + (long)c * c_stride * 3;
-    const long ps = p_stride * 3;
+    const float* w0 = ws + (long)c * c_stride * rec;
+    const long ps = p_stride * rec;
     double n = 0, sm = 0;
     for (int i = threadIdx.x; i < parts; i += 256) {
         const float* w = w0 + i * ps;
         n += w[0];
-        sm += (double)w[0] * w[1];
+        sm += (double)w[0] * (rec == 4 ? (double)w[1] + (double)w[3] : (double)w[1]);
     }
     auto bsum = [&](double v) {
         v = gd_wave_sum_d(v);
@@ -72,7 +80,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     double m2 = 0;
     for (int i = threadIdx.x; i < parts; i += 256) {
         const float* w = w0 + i * ps;
-        const double dm = (double)w[1] - mu;
+        const double dm = (rec == 4 ? (double)w[1] + (double)w[3] : (double)w[1]) - mu;
         m2 += (double)w[2] + (double)w[0] * dm * dm;
     }
     m2 = bsum(m2);
@@ -126,7 +134,8 @@ __global__ void bn_fold_kernel(const float* gamma, const float* beta, const floa
                                float* invstd_out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float is = invstd ? invstd[c] : 1.0f / sqrtf(running_var[c] + eps);
+    // eval: in double and rounded once, as bn_finalize_kernel forms the batch invstd
+    const float is = invstd ? invstd[c] : (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
     if (invstd_out) invstd_out[c] = is;
     const float sc = gamma[c] * is;
     scale[c] = sc;
@@ -168,7 +177,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
 
 // ---- backward of y = act(x*scale + shift) with batch statistics ----------------------------------------
 __device__ __forceinline__ float act_grad(float ypre, float dy, int act) {
-    if (act == GD_ACT_RELU) return ypre > 0.f ? dy : 0.f;
+    if (act == GD_ACT_RELU) return ypre >= 0.f ? dy : 0.f;  // at exactly 0 the gradient passes, as the oracle's clamp_min does
     if (act == GD_ACT_LEAKY02) return ypre >= 0.f ? dy : 0.2f * dy;
     return dy;
 }
@@ -258,7 +267,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float* __restrict_
 }  // namespace
 
 extern "C" size_t gd_bn_stats_ws_floats(int B, int C, long HW) {
-    return (size_t)C * (size_t)B * (size_t)chunks_per_image(HW) * 3;
+    return (size_t)C * (size_t)B * (size_t)chunks_per_image(HW) * 4;
 }
 
 extern "C" int gd_bn_stats(const float* x, long x_bs, int B, int C, long HW, float eps, float momentum, float* mean,
@@ -270,7 +279,7 @@ extern "C" int gd_bn_stats(const float* x, long x_bs, int B, int C, long HW, flo
     GD_CHECK_ARG((long)B * cpi <= 65535, "gd_bn_stats: too many parts");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_partial_kernel, dim3(C, B * cpi), dim3(256), 0, s, x, x_bs, C, HW, cpi, ws);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, ws, B * cpi, (long)B * cpi, 1L, eps, momentum, mean, invstd,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, ws, B * cpi, (long)B * cpi, 1L, 4, eps, momentum, mean, invstd,
                        running_mean, running_var, (float*)nullptr);
     GD_LAUNCH_CHECK();
     return 0;
@@ -288,7 +297,7 @@ extern "C" int gd_bn_stats_local(const float* x, long x_bs, int B, int C, long H
     GD_CHECK_ARG((long)B * cpi <= 65535, "gd_bn_stats_local: too many parts");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_partial_kernel, dim3(C, B * cpi), dim3(256), 0, s, x, x_bs, C, HW, cpi, ws);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, ws, B * cpi, (long)B * cpi, 1L, 0.f, 0.f, (float*)nullptr,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, ws, B * cpi, (long)B * cpi, 1L, 4, 0.f, 0.f, (float*)nullptr,
                        (float*)nullptr, (float*)nullptr, (float*)nullptr, stats);
     GD_LAUNCH_CHECK();
     return 0;
@@ -297,7 +306,7 @@ extern "C" int gd_bn_stats_merge(const float* stats_all, int world, int C, float
                                  float* invstd, float* running_mean, float* running_var, void* stream) {
     GD_CHECK_ARG(stats_all && mean && invstd && world > 0 && C > 0, "gd_bn_stats_merge: bad arguments");
     GD_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "gd_bn_stats_merge: running stats must come together");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, stats_all, world, 1L, (long)C, eps,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, stats_all, world, 1L, (long)C, 3, eps,
                        momentum, mean, invstd, running_mean, running_var, (float*)nullptr);
     GD_LAUNCH_CHECK();
     return 0;

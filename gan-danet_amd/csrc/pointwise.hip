@@ -34,6 +34,8 @@ __global__ void act_bwd_kernel(const float* __restrict__ y, const float* __restr
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const float o = y[i], g = dy[i];
         float v = g;
+        // from the OUTPUT: y == 0 is x <= 0, so x == 0 cannot be told from x < 0 here and gets 0.  norm.hip's act_grad sees
+        // the pre-activation and passes the gradient at exactly 0 (the oracle's clamp_min); the two differ there on purpose
         if (act == GD_ACT_RELU) v = o > 0.f ? g : 0.f;
         else if (act == GD_ACT_LEAKY02) v = o >= 0.f ? g : 0.2f * g;  // sign(y) == sign(x) for leaky
         else if (act == GD_ACT_SIGMOID) v = g * o * (1.f - o);
