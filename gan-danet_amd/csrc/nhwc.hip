@@ -201,13 +201,14 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const unsigned short* __r
         for (int q = 0; q < 3; ++q) {
             load8(xp + offs[q], C, o8, f, split);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) m[k] = fmaxf(m[k], f[k]);
+            for (int k = 0; k < 8; ++k) m[k] = (f[k] > m[k] || f[k] != f[k]) ? f[k] : m[k];   // ATen's scan: a NaN wins (fmaxf drops it)
         }
         store8(y + p * RS, C, o8, m, split);          // a maximum of values hi + lo splits back into the same hi, lo
     }
 }
-// dx = dy at the FIRST maximum of each window in row-major order (ATen's tie rule), else 0; with relu_mask the
-// result is also gated by x > 0 (backward of the ReLU that produced x)
+// dx = dy at the FIRST maximum of each window in row-major order (ATen's tie rule; a NaN counts as a new maximum, so
+// the last NaN of a window takes it), else 0; with relu_mask the result is also gated by x > 0 (backward of the ReLU
+// that produced x; a NaN maximum is not > 0 and passes nothing)
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ dy,
                                                       int H, int W, int C, int relu_mask, unsigned short* __restrict__ dx,
                                                       long total, int split) {
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const unsigned short* __r
             float m = v[0][k];
 #pragma unroll
             for (int q = 1; q < 4; ++q)
-                if (v[q][k] > m) { m = v[q][k]; arg = q; }
+                if (v[q][k] > m || v[q][k] != v[q][k]) { m = v[q][k]; arg = q; }
             const float gk = (relu_mask && !(m > 0.f)) ? 0.f : g[k];
 #pragma unroll
             for (int q = 0; q < 4; ++q) out[q][k] = q == arg ? gk : 0.f;

@@ -129,14 +129,14 @@ __global__ __launch_bounds__(256) void shift_sum9_bwd_kernel(const float* __rest
 }
 
 // conservative window of output coordinates that may read input coordinate i (cubic: |src - i| < 2 + clamp)
-__device__ __forceinline__ void cubic_window(int i, float rs, int n_in, int n_out, int& lo, int& hi) {
+__host__ __device__ __forceinline__ void cubic_window(int i, float rs, int n_in, int n_out, int& lo, int& hi) {
     const float inv = 1.f / rs;
     lo = (i == 0) ? 0 : (int)floorf(((float)i - 2.f + 0.5f) * inv - 0.5f) - 1;
     hi = (i == n_in - 1) ? n_out - 1 : (int)ceilf(((float)i + 2.f + 0.5f) * inv - 0.5f) + 1;
     lo = lo < 0 ? 0 : lo;
     hi = hi > n_out - 1 ? n_out - 1 : hi;
 }
-__device__ __forceinline__ void linear_window(int i, float rs, int n_in, int n_out, int& lo, int& hi) {
+__host__ __device__ __forceinline__ void linear_window(int i, float rs, int n_in, int n_out, int& lo, int& hi) {
     const float inv = 1.f / rs;
     lo = (i == 0) ? 0 : (int)floorf(((float)i - 1.f + 0.5f) * inv - 0.5f) - 1;
     hi = (i == n_in - 1) ? n_out - 1 : (int)ceilf(((float)i + 1.f + 0.5f) * inv - 0.5f) + 1;
@@ -330,7 +330,12 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const float* __restri
     const float* p = x + bc * (long)Hi * Wi + (long)(2 * oy) * Wi + 2 * ox;
     const float2 a = *reinterpret_cast<const float2*>(p);
     const float2 b = *reinterpret_cast<const float2*>(p + Wi);
-    y[bc * (long)Ho * Wo + (long)oy * Wo + ox] = fmaxf(fmaxf(a.x, a.y), fmaxf(b.x, b.y));
+    // ATen's scan: a later value replaces the maximum when it is greater OR a NaN (fmaxf would drop the NaN)
+    float m = a.x;
+    m = (a.y > m || a.y != a.y) ? a.y : m;
+    m = (b.x > m || b.x != b.x) ? b.x : m;
+    m = (b.y > m || b.y != b.y) ? b.y : m;
+    y[bc * (long)Ho * Wo + (long)oy * Wo + ox] = m;
 }
 
 __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -344,12 +349,13 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
     const float2 a = *reinterpret_cast<const float2*>(x + base);
     const float2 b = *reinterpret_cast<const float2*>(x + base + Wi);
     const float g = dy[bc * (long)Ho * Wo + (long)oy * Wo + ox];
-    // first maximum in row-major order takes the gradient (ATen's max_pool2d_with_indices tie rule)
+    // first maximum in row-major order takes the gradient (ATen's max_pool2d_with_indices tie rule); a NaN replaces
+    // whatever came before it, so a window with NaNs routes the gradient to its last NaN, as ATen does
     int arg = 0;
     float m = a.x;
-    if (a.y > m) { m = a.y; arg = 1; }
-    if (b.x > m) { m = b.x; arg = 2; }
-    if (b.y > m) { m = b.y; arg = 3; }
+    if (a.y > m || a.y != a.y) { m = a.y; arg = 1; }
+    if (b.x > m || b.x != b.x) { m = b.x; arg = 2; }
+    if (b.y > m || b.y != b.y) { m = b.y; arg = 3; }
     float2 oa, ob;
     oa.x = arg == 0 ? g : 0.f;
     oa.y = arg == 1 ? g : 0.f;
@@ -365,6 +371,20 @@ int check_plane(int BC, int Hi, int Wi, int Ho, int Wo, const char* who) {
         return -1;
     }
     return 0;
+}
+
+// The gather kernel walks WMAX columns from xlo.  Interior windows are bounded by the ratio alone (the launchers' ratio
+// guard), but column 0 is narrowed to start at 0 and the last column is widened to end at Wo - 1, so their widths also
+// depend on Wo -- which the C ABI takes independently of rsw.  Rows need no check: the kernel's row loop runs ylo..yhi.
+bool border_columns_fit(bool cubic, int Wi, int Wo, float rsw) {
+    const int cols[2] = {0, Wi - 1};
+    for (int c = 0; c < 2; ++c) {
+        int lo, hi;
+        if (cubic) cubic_window(cols[c], rsw, Wi, Wo, lo, hi);
+        else linear_window(cols[c], rsw, Wi, Wo, lo, hi);
+        if (hi - lo + 1 > WMAX) return false;
+    }
+    return true;
 }
 
 }  // namespace
@@ -423,7 +443,10 @@ extern "C" int gd_bicubic_bwd(const float* dy, int BC, int Hi, int Wi, float* dx
         GD_LAUNCH_CHECK();
         return 0;
     }
-    GD_CHECK_ARG(4.f / rsw + 5.f <= (float)WMAX, "gd_bicubic_bwd: scale factor too large for the gather window");
+    GD_CHECK_ARG(rsw > 0.f && rsh > 0.f && 4.f / rsw + 5.f <= (float)WMAX,
+                 "gd_bicubic_bwd: scale factor too large for the gather window");
+    GD_CHECK_ARG(border_columns_fit(true, Wi, Wo, rsw),
+                 "gd_bicubic_bwd: output width does not match the ratio (border column window exceeds the gather window)");
     GD_FOR_BC_SLICES(BC, hipLaunchKernelGGL((resize_bwd_gather_kernel<true>), dim3(gd_cdiv(Wi, 256), Hi, nz_), dim3(256),
                                             0, (hipStream_t)stream, dy + z0_ * (long)Ho * Wo, Hi, Wi,
                                             dx + z0_ * (long)Hi * Wi, Ho, Wo, rsh, rsw);)
@@ -449,6 +472,7 @@ extern "C" int gd_bilinear_bwd(const float* dy, int BC, int Hi, int Wi, float* d
     if (check_plane(BC, Hi, Wi, Ho, Wo, "gd_bilinear_bwd: bad sizes")) return -1;
     const float rsh = (float)Hi / (float)Ho, rsw = (float)Wi / (float)Wo;
     GD_CHECK_ARG(2.f / rsw + 5.f <= (float)WMAX, "gd_bilinear_bwd: scale factor too large for the gather window");
+    GD_CHECK_ARG(border_columns_fit(false, Wi, Wo, rsw), "gd_bilinear_bwd: border column window exceeds the gather window");
     GD_FOR_BC_SLICES(BC, hipLaunchKernelGGL((resize_bwd_gather_kernel<false>), dim3(gd_cdiv(Wi, 256), Hi, nz_), dim3(256),
                                             0, (hipStream_t)stream, dy + z0_ * (long)Ho * Wo, Hi, Wi,
                                             dx + z0_ * (long)Hi * Wi, Ho, Wo, rsh, rsw);)
