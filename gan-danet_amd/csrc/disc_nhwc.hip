@@ -7,122 +7,11 @@
 //   * the pixel-major -> channel-major bf16 transposer that hands a gradient to the weight-gradient kernel as its
 //     [co][pixel] operand, fused with the per-channel sums (= the bias gradient).
 // All HBM-bound byte shuffling: 16-byte accesses, no MFMA.
-#include "common.h"
-#include "../../include/gandanet.h"
+#include "nhwc_util.h"
 
 namespace {
 
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void unpack8(const u32x4_t v, float* f) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = gd_bf2f((unsigned short)(v[k] & 0xFFFFu));
-        f[2 * k + 1] = gd_bf2f((unsigned short)(v[k] >> 16));
-    }
-}
-__device__ __forceinline__ u32x4_t pack8(const float* f) {
-    const u32x4_t v = {gd_pack_bf2(f[0], f[1]), gd_pack_bf2(f[2], f[3]), gd_pack_bf2(f[4], f[5]), gd_pack_bf2(f[6], f[7])};
-    return v;
-}
-// bf16 > 0  <=>  sign clear and magnitude non-zero
-__device__ __forceinline__ bool bf_pos(unsigned int h) { return (h & 0x7FFFu) && !(h & 0x8000u); }
-
-// Split activations (set_precision("mixed"), operand mode "x3"): a pixel's C logical channels are stored as the 3 C bf16
-// [hi | lo | hi] with hi = bf16(v), lo = bf16(v - hi) -- the operand the pixel-major conv kernels take against weights
-// split [hi ; hi ; lo] along the contraction axis.  `row` = the pixel's first element, c8 = the channel octet.
-__device__ __forceinline__ void store8(unsigned short* row, int C, int c8, const float* v, int split) {
-    const u32x4_t hi = pack8(v);
-    *reinterpret_cast<u32x4_t*>(row + c8) = hi;
-    if (split) {
-        float r[8];
-        unpack8(hi, r);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = v[k] - r[k];
-        *reinterpret_cast<u32x4_t*>(row + C + c8) = pack8(r);
-        *reinterpret_cast<u32x4_t*>(row + 2 * C + c8) = hi;
-    }
-}
-__device__ __forceinline__ void load8(const unsigned short* row, int C, int c8, float* v, int split) {
-    unpack8(*reinterpret_cast<const u32x4_t*>(row + c8), v);
-    if (split) {
-        float l[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(row + C + c8), l);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] += l[k];
-    }
-}
-
-// ---- stem forward: thread = (output pixel, output-channel octet); weights in LDS as [ci][tap][co] ---------------------
-__global__ __launch_bounds__(256) void disc_stem_fwd_kernel(const float* __restrict__ img, int Ci, int H, int W, int Ho, int Wo,
-                                                           const float* __restrict__ w, const float* __restrict__ bias,
-                                                           int Co, float slope, unsigned short* __restrict__ y, long npix_total, int split) {
-    extern __shared__ float wl[];
-    const int RS = split ? 3 * Co : Co;                 // elements per output pixel
-    for (int i = threadIdx.x; i < Ci * 9 * Co; i += 256) {
-        const int co = i % Co, t = (i / Co) % 9, ci = i / (9 * Co);
-        wl[i] = w[((long)co * Ci + ci) * 9 + t];
-    }
-    __syncthreads();
-    const int oct = Co / 8;
-    const long HW = (long)H * W, HWo = (long)Ho * Wo;
-    if (Ci == 1 && Co == 64) {
-        // single-channel image, 64 filters: the thread's octet is fixed over the grid stride, weights and biases in registers
-        const int o8 = (threadIdx.x & 7) * 8;
-        float wr[9][8], br[8];
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) wr[t][k] = wl[t * 64 + o8 + k];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) br[k] = bias ? bias[o8 + k] : 0.f;
-        for (long p = ((long)blockIdx.x * 256 + threadIdx.x) >> 3; p < npix_total; p += ((long)gridDim.x * 256) >> 3) {
-            const long b = p / HWo;
-            const int rem = (int)(p - b * HWo);
-            const int py = rem / Wo, px = rem - py * Wo;
-            const float* plane = img + b * HW;
-            float acc[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] = br[k];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int iy = 2 * py + t / 3 - 1, ix = 2 * px + t % 3 - 1;
-                const float v = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? plane[(long)iy * W + ix] : 0.f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) acc[k] = fmaf(v, wr[t][k], acc[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] = acc[k] > 0.f ? acc[k] : acc[k] * slope;
-            store8(y + p * RS, 64, o8, acc, split);
-        }
-        return;
-    }
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < npix_total * oct; idx += (long)gridDim.x * 256) {
-        const long p = idx / oct;
-        const int o8 = (int)(idx - p * oct) * 8;
-        const long b = p / HWo;
-        const int rem = (int)(p - b * HWo);
-        const int py = rem / Wo, px = rem - py * Wo;
-        float acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = bias ? bias[o8 + k] : 0.f;
-        for (int ci = 0; ci < Ci; ++ci) {
-            const float* plane = img + (b * Ci + ci) * HW;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int iy = 2 * py + t / 3 - 1, ix = 2 * px + t % 3 - 1;
-                if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-                const float v = plane[(long)iy * W + ix];
-                const float* wp = wl + (ci * 9 + t) * Co + o8;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) acc[k] = fmaf(v, wp[k], acc[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = acc[k] > 0.f ? acc[k] : acc[k] * slope;
-        store8(y + p * RS, Co, o8, acc, split);
-    }
-}
+// (the stem forward is stem_fwd_kernel<2, true> of nhwc_util.h)
 
 // ---- stem weight / bias gradient: dw[co][ci][tap] = sum_p g[p][co] x[ci][2p + tap - 1], db[co] = sum_p g[p][co] -------
 // thread = (output pixel, channel octet), grid-strided; blockIdx.y = ci.  Ten accumulators per channel (nine taps + the
@@ -188,49 +77,17 @@ __global__ __launch_bounds__(256) void disc_stem_wgrad_kernel(const unsigned sho
 // ---- stem data gradient: g (B, Ho, Wo, Co) bf16 -> dimg (B, Ci, H, W) fp32 ---------------------------------------------
 // dimg[Y][X] = sum over taps with ky = Y+1 (mod 2), kx = X+1 (mod 2) of T[tap][(Y+1-ky)/2][(X+1-kx)/2],
 // T[tap][p] = sum_co g[p][co] w[co][ci][tap].  A workgroup owns 16 x 16 gradient pixels (= 32 x 32 image pixels) plus the
-// one-pixel high-side halo the odd image rows / columns reach into; phase 1 computes T once per gradient pixel into LDS.
+// one-pixel high-side halo the odd image rows / columns reach into; phase 1 (stem_dgrad_phase1) computes T once per
+// gradient pixel into LDS.
 constexpr int SD_T = 16, SD_HT = SD_T + 1, SD_NH = SD_HT * SD_HT;
 __global__ __launch_bounds__(256) void disc_stem_dgrad_kernel(const unsigned short* __restrict__ g, int Ci, int H, int W, int Ho,
                                                              int Wo, const float* __restrict__ w, int Co,
                                                              float* __restrict__ dimg, int tiles_x, int split) {
     extern __shared__ float smem[];
-    const int RS = split ? 3 * Co : Co;
-    float* wl = smem;                                   // [ci][tap][co]
-    float* T = smem + Ci * 9 * Co;                      // [ci*9 + tap][haloed gradient pixel]
-    for (int i = threadIdx.x; i < Ci * 9 * Co; i += 256) {
-        const int co = i % Co, t = (i / Co) % 9, ci = i / (9 * Co);
-        wl[i] = w[((long)co * Ci + ci) * 9 + t];
-    }
-    __syncthreads();
     const int b = blockIdx.y;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int u0 = ty * SD_T, v0 = tx * SD_T;
-    for (int hp = threadIdx.x; hp < SD_NH; hp += 256) {
-        const int hy = hp / SD_HT, hx = hp - hy * SD_HT;
-        const int qy = u0 + hy, qx = v0 + hx;
-        const bool inside = qy < Ho && qx < Wo;
-        for (int ci = 0; ci < Ci; ++ci) {
-            float t[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) t[k] = 0.f;
-            if (inside) {
-                const unsigned short* gp = g + (((long)b * Ho + qy) * Wo + qx) * RS;
-                for (int o8 = 0; o8 < Co; o8 += 8) {
-                    float f[8];
-                    load8(gp, Co, o8, f, split);
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) {
-                        const float* wp = wl + (ci * 9 + k) * Co + o8;      // uniform address: LDS broadcast
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) t[k] = fmaf(f[j], wp[j], t[k]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 9; ++k) T[(ci * 9 + k) * SD_NH + hp] = t[k];
-        }
-    }
-    __syncthreads();
+    const float* T = stem_dgrad_phase1<SD_HT>(smem, g, w, b, Ho, Wo, u0, v0, Ci, Co, split);
     const long HW = (long)H * W;
     for (int q = threadIdx.x; q < 4 * SD_T * SD_T; q += 256) {
         const int ly = q / (2 * SD_T), lx = q - ly * (2 * SD_T);
@@ -364,16 +221,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw16_kernel(const unsigned shor
     }
 }
 
-static inline int grid_n(long n, int cap = 16384) {
-    long g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 }  // namespace
-
-#define NS(s) ((hipStream_t)(s))
 
 extern "C" int gd_disc_stem_fwd(const float* img, int B, int Ci, int H, int W, const float* w, const float* bias, int Co,
                                 float slope, void* y, int split, void* stream) {
@@ -381,8 +229,8 @@ extern "C" int gd_disc_stem_fwd(const float* img, int B, int Ci, int H, int W, c
                  "gd_disc_stem_fwd: needs Ci <= 4, Co % 8 == 0");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long npix = (long)B * Ho * Wo;
-    hipLaunchKernelGGL(disc_stem_fwd_kernel, dim3(grid_n(npix * (Co / 8))), dim3(256), (size_t)Ci * 9 * Co * 4, NS(stream), img,
-                       Ci, H, W, Ho, Wo, w, bias, Co, slope, (unsigned short*)y, npix, split);
+    hipLaunchKernelGGL((stem_fwd_kernel<2, true>), dim3(grid_n(npix * (Co / 8))), dim3(256), (size_t)Ci * 9 * Co * 4, NS(stream),
+                       img, Ci, H, W, w, bias, Co, 0, slope, (unsigned short*)y, npix, split);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -422,7 +270,7 @@ extern "C" int gd_disc_stem_dgrad(const void* g, int B, int Ci, int H, int W, co
                                   void* stream) {
     GD_CHECK_ARG(g && w && dimg && B > 0 && B <= 65535 && Ci > 0 && Ci <= 4 && H > 0 && W > 0 && Co > 0 && Co % 8 == 0,
                  "gd_disc_stem_dgrad: needs Ci <= 4, Co % 8 == 0");
-    const size_t lds = ((size_t)Ci * 9 * Co + (size_t)Ci * 9 * SD_NH) * sizeof(float);
+    const size_t lds = stem_dgrad_lds(Ci, Co, SD_HT);
     GD_CHECK_ARG(lds <= 64 * 1024, "gd_disc_stem_dgrad: Ci * Co too large for the LDS tile");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     // tiles over the GRADIENT grid; a tile also writes the odd image row / column past its last gradient pixel

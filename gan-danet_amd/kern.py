@@ -1028,6 +1028,11 @@ def _bf(t: Tensor, name: str = "tensor") -> Tensor:
     return t
 
 
+def _nphys(split: bool) -> int:
+    """physical bf16 channels per logical channel of a pixel-major tensor: 3 when split ([hi | lo | hi]), else 1"""
+    return 3 if split else 1
+
+
 def conv3x3_nhwc_pack(w: Tensor, transposed: bool) -> Tensor:
     """w (Cout, Cin, 3, 3) fp32 -> packed bf16 operator (transposed: 0 forward, 1 stride-1 data gradient, 2 stride-2
     data gradient)"""
@@ -1047,7 +1052,7 @@ def conv3x3_nhwc(x: Tensor, wpack: Tensor, bias: Optional[Tensor], M: int, relu:
     channels, wpack from split weights, y / mask / res with 3 M channels ([hi | lo | hi])"""
     _bf(x, "nhwc conv input")
     B, H, W, Kc = x.shape
-    y = torch.empty(B, H, W, (3 if split else 1) * M, device=x.device, dtype=torch.bfloat16)
+    y = torch.empty(B, H, W, _nphys(split) * M, device=x.device, dtype=torch.bfloat16)
     for t, nm in ((mask, "mask"), (res, "res")):
         if t is not None and (_bf(t, nm).shape != y.shape):
             raise L.GandanetError(f"conv3x3_nhwc: {nm} {tuple(t.shape)} does not match the output {tuple(y.shape)}")
@@ -1126,7 +1131,7 @@ def conv3x3_wgrad16(dy16: Tensor, x16: Tensor, H: int, W: int, stride: int = 1, 
     parts = dy16 if split else dy16[None]
     _, B, Cout, _ = parts.shape
     x_ld = x16.shape[2]
-    Cin = x_ld // 3 if split else x_ld
+    Cin = x_ld // _nphys(split)
     dw = torch.empty(Cout, Cin, 3, 3, device=dy16.device, dtype=torch.float32)
     with _ConvBracket(tag, 3, stride, Cin, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1, B):
         for part, xblk, acc in _WGRAD16_SPLIT if split else _WGRAD16_SPLIT[:1]:
@@ -1151,25 +1156,42 @@ def _half_up(n: int) -> int:
     return (n - 1) // 2 + 1
 
 
-def disc_stem_fwd(img: Tensor, w: Tensor, bias: Optional[Tensor], slope: float, split: bool = False) -> Tensor:
-    """conv1: fp32 NCHW image -> LeakyReLU(conv3x3 s2 p1 + bias) as (B, Ho, Wo, Co) bf16; ``split`` (here and in the
-    functions below): pixel-major tensors carry 3 C channels per pixel, the values split [hi | lo | hi] (operand mode "x3")"""
+def _stem_fwd(name: str, img: Tensor, w: Tensor, bias: Optional[Tensor], stride: int, act, split: bool) -> Tensor:
+    """gd_<name>: fp32 NCHW image -> act(conv3x3 p1 + bias) at ``stride``, pixel-major bf16; act = its ReLU flag / LeakyReLU slope"""
     _dense(img, "stem image"), _dense(w, "stem weight")
     B, Ci, H, W = img.shape
     Co = w.shape[0]
     if w.shape[1] != Ci:
-        raise L.GandanetError(f"disc_stem_fwd: weight {tuple(w.shape)} does not match image {tuple(img.shape)}")
-    y = torch.empty(B, _half_up(H), _half_up(W), (3 if split else 1) * Co, device=img.device, dtype=torch.bfloat16)
-    L.check(lib().gd_disc_stem_fwd(_ptr(img), B, Ci, H, W, _ptr(w), _ptr(bias), Co, float(slope), _ptr(y), int(split), _stream()),
-            "gd_disc_stem_fwd")
+        raise L.GandanetError(f"{name}: weight {tuple(w.shape)} does not match image {tuple(img.shape)}")
+    y = torch.empty(B, (H - 1) // stride + 1, (W - 1) // stride + 1, _nphys(split) * Co, device=img.device, dtype=torch.bfloat16)
+    L.check(getattr(lib(), "gd_" + name)(_ptr(img), B, Ci, H, W, _ptr(w), _ptr(bias), Co, act, _ptr(y), int(split), _stream()),
+            "gd_" + name)
     return y
+
+
+def _stem_dgrad(name: str, g: Tensor, w: Tensor, H: int, W: int, stride: int, split: bool) -> Tensor:
+    """gd_<name>: pixel-major bf16 gradient of a stem's pre-activation -> fp32 gradient (B, Ci, H, W) of its image"""
+    _bf(g, "stem gradient"), _dense(w, "stem weight")
+    B, Ho, Wo, Co = g.shape
+    if (Ho, Wo) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise L.GandanetError(f"{name}: gradient {tuple(g.shape)} does not match a {H} x {W} image")
+    dimg = torch.empty(B, w.shape[1], H, W, device=g.device, dtype=torch.float32)
+    L.check(getattr(lib(), "gd_" + name)(_ptr(g), B, w.shape[1], H, W, _ptr(w), Co // _nphys(split), _ptr(dimg), int(split),
+                                         _stream()), "gd_" + name)
+    return dimg
+
+
+def disc_stem_fwd(img: Tensor, w: Tensor, bias: Optional[Tensor], slope: float, split: bool = False) -> Tensor:
+    """conv1: fp32 NCHW image -> LeakyReLU(conv3x3 s2 p1 + bias) as (B, Ho, Wo, Co) bf16; ``split`` (here and in the
+    functions below): pixel-major tensors carry 3 C channels per pixel, the values split [hi | lo | hi] (operand mode "x3")"""
+    return _stem_fwd("disc_stem_fwd", img, w, bias, 2, float(slope), split)
 
 
 def disc_stem_wgrad(g: Tensor, img: Tensor, want_bias: bool = True, split: bool = False):
     """(dw (Co, Ci, 3, 3), db (Co) or None) of conv1 from the pre-activation gradient g (B, Ho, Wo, Co) bf16"""
     _bf(g, "stem gradient"), _dense(img, "stem image")
     B, Ci, H, W = img.shape
-    Co = g.shape[3] // (3 if split else 1)
+    Co = g.shape[3] // _nphys(split)
     if g.shape[:3] != (B, _half_up(H), _half_up(W)):
         raise L.GandanetError(f"disc_stem_wgrad: gradient {tuple(g.shape)} does not match image {tuple(img.shape)}")
     dw = torch.empty(Co, Ci, 3, 3, device=g.device, dtype=torch.float32)
@@ -1180,15 +1202,7 @@ def disc_stem_wgrad(g: Tensor, img: Tensor, want_bias: bool = True, split: bool 
 
 
 def disc_stem_dgrad(g: Tensor, w: Tensor, H: int, W: int, split: bool = False) -> Tensor:
-    _bf(g, "stem gradient"), _dense(w, "stem weight")
-    B, Ho, Wo, Co = g.shape
-    Co //= 3 if split else 1
-    Ci = w.shape[1]
-    if (Ho, Wo) != (_half_up(H), _half_up(W)):
-        raise L.GandanetError(f"disc_stem_dgrad: gradient {tuple(g.shape)} does not match a {H} x {W} image")
-    dimg = torch.empty(B, Ci, H, W, device=g.device, dtype=torch.float32)
-    L.check(lib().gd_disc_stem_dgrad(_ptr(g), B, Ci, H, W, _ptr(w), Co, _ptr(dimg), int(split), _stream()), "gd_disc_stem_dgrad")
-    return dimg
+    return _stem_dgrad("disc_stem_dgrad", g, w, H, W, 2, split)
 
 
 def conv3x3_nhwc_s2(x: Tensor, wpack: Tensor, bias: Optional[Tensor], M: int, act: int, slope: float = 0.2,
@@ -1197,7 +1211,7 @@ def conv3x3_nhwc_s2(x: Tensor, wpack: Tensor, bias: Optional[Tensor], M: int, ac
     split: K = 3 Cin physical channels in, 3 M out, wpack from split3_weights(w, 1)"""
     _bf(x, "nhwc conv input")
     B, H, W, Kc = x.shape
-    y = torch.empty(B, _half_up(H), _half_up(W), (3 if split else 1) * M, device=x.device, dtype=torch.bfloat16)
+    y = torch.empty(B, _half_up(H), _half_up(W), _nphys(split) * M, device=x.device, dtype=torch.bfloat16)
     with _Bracket("conv3x3_nhwc_s2", 2.0 * 9 * Kc * M * y.shape[1] * y.shape[2] * B):
         L.check(lib().gd_conv3x3_nhwc_s2(_ptr(x), _ptr(wpack), _ptr(bias), _ptr(y), B, H, W, Kc, M, int(act), float(slope),
                                          int(split), _stream()), "gd_conv3x3_nhwc_s2")
@@ -1209,7 +1223,7 @@ def conv3x3_nhwc_s2_dgrad(dy: Tensor, wpack_t: Tensor, act_out: Tensor, slope: f
     split: dy carries M = 3 Cout physical channels, act_out and dx 3 K, wpack_t from split3_weights(w, 0)"""
     _bf(dy, "nhwc conv gradient"), _bf(act_out, "activation output")
     B, H, W, Kc = act_out.shape
-    Kc //= 3 if split else 1
+    Kc //= _nphys(split)
     M = dy.shape[3]
     if dy.shape[:3] != (B, _half_up(H), _half_up(W)):
         raise L.GandanetError(f"conv3x3_nhwc_s2_dgrad: dy {tuple(dy.shape)} does not match input {tuple(act_out.shape)}")
@@ -1224,7 +1238,7 @@ def nhwc_flatten_fwd(y: Tensor, split: bool = False) -> Tensor:
     """(B, h, w, C) bf16 -> (B, C*h*w) fp32 in the (c, h, w) order of NCHW .flatten(1)"""
     _bf(y, "flatten input")
     B, H, W, Cc = y.shape
-    Cc //= 3 if split else 1
+    Cc //= _nphys(split)
     f = torch.empty(B, Cc * H * W, device=y.device, dtype=torch.float32)
     L.check(lib().gd_nhwc_flatten_fwd(_ptr(y), B, H * W, Cc, _ptr(f), int(split), _stream()), "gd_nhwc_flatten_fwd")
     return f
@@ -1233,8 +1247,8 @@ def nhwc_flatten_fwd(y: Tensor, split: bool = False) -> Tensor:
 def nhwc_flatten_bwd(df: Tensor, y: Tensor, slope: float, split: bool = False) -> Tensor:
     _bf(y, "flatten input"), _dense(df, "flatten gradient")
     B, H, W, Cc = y.shape
-    Cc //= 3 if split else 1
-    if df.numel() * (3 if split else 1) != y.numel():
+    Cc //= _nphys(split)
+    if df.numel() * _nphys(split) != y.numel():
         raise L.GandanetError(f"nhwc_flatten_bwd: gradient {tuple(df.shape)} does not match {tuple(y.shape)}")
     g = torch.empty_like(y)
     L.check(lib().gd_nhwc_flatten_bwd(_ptr(df), _ptr(y), float(slope), B, H * W, Cc, _ptr(g), int(split), _stream()),
@@ -1247,7 +1261,7 @@ def nhwc_to_nchw16(g: Tensor, want_sum: bool, split: bool = False):
     [hi | lo | hi] and the result is (2, B, C, h, w), hi then lo, with the sums of hi + lo"""
     _bf(g, "nhwc gradient")
     B, H, W, Cc = g.shape
-    Cc //= 3 if split else 1
+    Cc //= _nphys(split)
     gt = torch.empty((2, B, Cc, H, W) if split else (B, Cc, H, W), device=g.device, dtype=torch.bfloat16)
     cs = torch.empty(Cc, device=g.device, dtype=torch.float32) if want_sum else None
     L.check(lib().gd_nhwc_to_nchw16_ws(_ptr(g), B, H * W, Cc, _ptr(gt), _ptr(cs), int(split), _stream(), *det_ws()),
@@ -1269,32 +1283,18 @@ def conv3x3_wgrad_nhwc(g: Tensor, x: Tensor, stride: int, want_bias: bool, split
 def nhwc_stem_fwd(img: Tensor, w: Tensor, bias: Optional[Tensor], relu: bool, split: bool = False) -> Tensor:
     """``split`` (here and in the nhwc_* functions below): the pixel-major tensors carry 3 C channels per pixel, the values
     split [hi | lo | hi] (operand mode "x3")"""
-    _dense(img, "stem image"), _dense(w, "stem weight")
-    B, Ci, H, W = img.shape
-    Co = w.shape[0]
-    if w.shape[1] != Ci:
-        raise L.GandanetError(f"nhwc_stem_fwd: weight {tuple(w.shape)} does not match image {tuple(img.shape)}")
-    y = torch.empty(B, H, W, (3 if split else 1) * Co, device=img.device, dtype=torch.bfloat16)
-    L.check(lib().gd_nhwc_stem_fwd(_ptr(img), B, Ci, H, W, _ptr(w), _ptr(bias), Co, int(relu), _ptr(y), int(split), _stream()),
-            "gd_nhwc_stem_fwd")
-    return y
+    return _stem_fwd("nhwc_stem_fwd", img, w, bias, 1, int(relu), split)
 
 
 def nhwc_stem_bwd(g: Tensor, w: Tensor, split: bool = False) -> Tensor:
-    _bf(g, "stem gradient"), _dense(w, "stem weight")
-    B, H, W, Co = g.shape
-    Co //= 3 if split else 1
-    Ci = w.shape[1]
-    dimg = torch.empty(B, Ci, H, W, device=g.device, dtype=torch.float32)
-    L.check(lib().gd_nhwc_stem_bwd(_ptr(g), B, Ci, H, W, _ptr(w), Co, _ptr(dimg), int(split), _stream()), "gd_nhwc_stem_bwd")
-    return dimg
+    return _stem_dgrad("nhwc_stem_bwd", g, w, g.shape[1], g.shape[2], 1, split)
 
 
 def nhwc_maxpool2_fwd(x: Tensor, split: bool = False) -> Tensor:
     _bf(x, "pool input")
     B, H, W, Cn = x.shape
     y = torch.empty(B, H // 2, W // 2, Cn, device=x.device, dtype=torch.bfloat16)
-    L.check(lib().gd_nhwc_maxpool2_fwd(_ptr(x), B, H, W, Cn // (3 if split else 1), _ptr(y), int(split), _stream()),
+    L.check(lib().gd_nhwc_maxpool2_fwd(_ptr(x), B, H, W, Cn // _nphys(split), _ptr(y), int(split), _stream()),
             "gd_nhwc_maxpool2_fwd")
     return y
 
@@ -1303,9 +1303,8 @@ def nhwc_maxpool2_bwd(x: Tensor, dy: Tensor, relu_mask: bool, split: bool = Fals
     _bf(x, "pool input"), _bf(dy, "pool dy")
     B, H, W, Cn = x.shape
     dx = torch.empty_like(x)
-    L.check(lib().gd_nhwc_maxpool2_bwd(_ptr(x), _ptr(dy), B, H, W, Cn // (3 if split else 1), int(relu_mask), _ptr(dx), int(split),
-                                       _stream()),
-            "gd_nhwc_maxpool2_bwd")
+    L.check(lib().gd_nhwc_maxpool2_bwd(_ptr(x), _ptr(dy), B, H, W, Cn // _nphys(split), int(relu_mask), _ptr(dx), int(split),
+                                       _stream()), "gd_nhwc_maxpool2_bwd")
     return dx
 
 
@@ -1314,7 +1313,7 @@ def nhwc_l1(a: Tensor, b: Tensor, out: Tensor, accumulate: bool, split: bool = F
     _bf(a, "l1 a"), _bf(b, "l1 b")
     ws = torch.empty(1024, device=a.device, dtype=torch.float32)
     sc = a.shape[-1] // 3 if split else 0
-    L.check(lib().gd_nhwc_l1(_ptr(a), _ptr(b), a.numel() // (3 if split else 1), _ptr(out), int(accumulate), _ptr(ws), sc,
+    L.check(lib().gd_nhwc_l1(_ptr(a), _ptr(b), a.numel() // _nphys(split), _ptr(out), int(accumulate), _ptr(ws), sc,
                              _stream()), "gd_nhwc_l1")
 
 
@@ -1322,9 +1321,8 @@ def nhwc_l1_grad(a: Tensor, b: Tensor, upstream: Tensor, relu_mask: bool, split:
     _bf(a, "l1 a"), _bf(b, "l1 b"), _dense(upstream, "upstream gradient")
     g = torch.empty_like(a)
     sc = a.shape[-1] // 3 if split else 0
-    L.check(lib().gd_nhwc_l1_grad(_ptr(a), _ptr(b), a.numel() // (3 if split else 1), _ptr(upstream), int(relu_mask), _ptr(g), sc,
-                                  _stream()),
-            "gd_nhwc_l1_grad")
+    L.check(lib().gd_nhwc_l1_grad(_ptr(a), _ptr(b), a.numel() // _nphys(split), _ptr(upstream), int(relu_mask), _ptr(g), sc,
+                                  _stream()), "gd_nhwc_l1_grad")
     return g
 
 

@@ -736,6 +736,39 @@ def test_nhwc_stem_pool_l1(gd, ci):
     assert_close(_nchw(gl), ref, 1e-2, "l1 grad")
 
 
+@pytest.mark.parametrize("split", [False, True], ids=["plain", "split"])
+@pytest.mark.parametrize("ci", [1, 3])
+@pytest.mark.parametrize("stem,hw", [("vgg", (17, 19)), ("vgg", (33, 16)), ("disc", (17, 19)), ("disc", (33, 16)), ("disc", (33, 37))],
+                         ids=lambda v: v if isinstance(v, str) else "%dx%d" % v)
+def test_stem_generic_path_and_tile_edges_vs_fp64(gd, stem, hw, ci, split):
+    """Both stems (VGG: stride 1 + ReLU; Discriminator1: stride 2 + LeakyReLU), forward and data gradient, at Co = 16: the
+    LDS-resident generic path for Ci = 1 as well (Co = 64 takes the register path there), against F.conv2d /
+    conv2d_input in fp64.  17 x 19 is one pixel past a 16 x 16 tile both ways and odd both ways (the stride-2 halo row and
+    column are live), 33 x 16 three tiles by one; 33 x 37 (Discriminator1 only) puts the GRADIENT grid, 17 x 19, one pixel
+    past that kernel's 16 x 16 gradient tile.  Bounds: bf16 storage 1e-2, [hi | lo | hi] storage 1e-5 (as the split stem
+    forward of test_disc_trunk_kernels_on_split_activations_vs_fp64), the fp32 data gradient 1e-4."""
+    _, K = _ops()
+    B, (H, W), Co, s = 2, hw, 16, 2 if stem == "disc" else 1
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    img = seeded((B, ci, H, W), 291)
+    w = seeded((Co, ci, 3, 3), 292, 0.3)
+    bias = seeded((Co,), 293, 0.1)
+    pre = F.conv2d(img.double(), w.double(), bias.double(), stride=s, padding=1)
+    if stem == "disc":
+        a, ar = K.disc_stem_fwd(img.to(DEV), w.to(DEV), bias.to(DEV), 0.2, split=split), F.leaky_relu(pre, 0.2)
+    else:
+        a, ar = K.nhwc_stem_fwd(img.to(DEV), w.to(DEV), bias.to(DEV), True, split=split), F.relu(pre)
+    assert a.shape == (B, Ho, Wo, (3 if split else 1) * Co)
+    assert_close(_nchw_split(a) if split else _nchw(a), ar.float(), 1e-5 if split else 1e-2, "stem fwd")
+    g = seeded((B, Co, Ho, Wo), 294)
+    if not split:
+        g = bf16_round(g)
+    gd_ = _nhwc_split(g) if split else _nhwc(g)
+    dimg = K.disc_stem_dgrad(gd_, w.to(DEV), H, W, split=split) if stem == "disc" else K.nhwc_stem_bwd(gd_, w.to(DEV), split=split)
+    dr = torch.nn.grad.conv2d_input((B, ci, H, W), w.double(), g.double(), stride=s, padding=1)
+    assert_close(dimg, dr.float(), 1e-4, "stem data gradient")
+
+
 def test_copy_slab_vector_and_scalar_paths(gd):
     """gd_copy_slab: channel slices of wider slabs in and out, plain and accumulating; 16-byte path (aligned, multiples of 4)
     and the scalar path (odd sizes / a slice starting at an odd channel of an odd-sized plane)"""
