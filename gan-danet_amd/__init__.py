@@ -24,6 +24,8 @@ from .timeseries import SeriesSkill, coarsen, consistency, harmonic_fit, lstsq_s
 from . import trend
 from .trend import TrendTest, mann_kendall, normal_quantile, sen_slope, trend_test
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
+from . import verification
+from .verification import EnsembleVerification, ensemble_scores
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

@@ -29,6 +29,12 @@ LSTSQ_MAX_P = 8                  # GD_LSTSQ_MAX_P
 TREND_MAX_T = 2048               # GD_TREND_MAX_T
 TREND_MAPS = ("n", "s", "var_s", "z", "p", "tau", "slope", "intercept", "slope_lo", "slope_hi")   # GD_TREND_*: plane k of `out`
 TREND_SEN, TREND_CI, TREND_CONTINUITY = 1, 2, 4   # GD_TREND_SEN, GD_TREND_CI, GD_TREND_CONTINUITY
+ENSV_MAX_M, ENSV_F64, ENSV_FAIR = 32, 1, 2   # GD_ENSV_MAX_M, GD_ENSV_F64, GD_ENSV_FAIR
+ENSV_FIELDS = ("n", "tied", "crps", "crps_gauss", "abs_e", "e2", "s2")   # GD_ENSV_*: record slot k; then cover, hist
+ENSV_COVER, ENSV_HIST, ENSV_BINS, ENSV_REC = 7, 11, 33, 44   # GD_ENSV_COVER, GD_ENSV_HIST, GD_ENSV_BINS, GD_ENSV_REC
+ENSV_METRIC_NAMES = ("crps", "crps_gauss", "mae", "rmse", "spread", "spread_skill")   # GD_ENSV_M_*: metric slot k
+ENSV_M_COVER, ENSV_M_RELIABILITY, ENSV_M_TIED, ENSV_M_HIST, ENSV_METRICS = 6, 10, 11, 12, 45
+ENSV_LEVELS = (0.5, 0.6826894921370859, 0.9, 0.95)   # the nominal levels of the four coverage counts
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -215,6 +221,10 @@ SIGNATURES = {
     "gd_block_mean_host": (_i, [_p, _i, _l, _l, _l, _i, _i, _p, _i, _p, _p]),
     "gd_trend_test": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p, _p]),
     "gd_trend_test_host": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p]),
+    "gd_ens_verify_ws_bytes": (_sz, [_l]),
+    "gd_ens_verify": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "gd_ens_verify_host": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p]),
+    "gd_ens_verify_merge_host": (_i, [C.POINTER(C.c_double), _l, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

@@ -23,6 +23,7 @@ from torch import nn
 
 from . import kern as K
 from . import parallel
+from .verification import EnsembleVerification
 
 METRIC_KEYS = ("n", "mse", "mae", "r2", "cc")
 
@@ -165,7 +166,8 @@ def evaluate(model: nn.Module, dataset, batch_size: int, input_attention: Option
 
 
 def evaluate_ensemble(models: Iterable[nn.Module], dataset, batch_size: int, mask=None, affine=None,
-                      input_attentions: Optional[Sequence[Optional[nn.Module]]] = None) -> Dict[str, object]:
+                      input_attentions: Optional[Sequence[Optional[nn.Module]]] = None, verify: bool = False,
+                      fair: bool = False) -> Dict[str, object]:
     """``EnsembleTrainer.compute_uncertainty`` (deep_ensemble.ipynb:L438-476) with the member axis on the device.
 
     ``mask`` (H, W): nonzero = valid (the notebook's ``tpbh != 0``).  Per batch the members' predictions are written into
@@ -174,7 +176,13 @@ def evaluate_ensemble(models: Iterable[nn.Module], dataset, batch_size: int, mas
     metrics (``members``; ``affine`` = the scaler's inverse, and the mask, apply to them), the maps ``mean_map`` /
     ``std_map`` (T, C, H, W) and the series ``preds_ts`` (M, T, C) / ``trues_ts`` (T, C).  Tensors stay on the device; one
     device -> host copy at the end.  Single process: members are not spread over ranks here.  The samples are read as
-    stored, whatever the dataset's ``augment`` flag, so every member sees the same batch and runs repeat."""
+    stored, whatever the dataset's ``augment`` flag, so every member sees the same batch and runs repeat.
+
+    ``verify``: the slab of every batch also goes through ``EnsembleVerification`` (verification.py) against the batch's
+    truth, under ``mask`` and with ``affine[0]`` (> 0) as the scale; the result gains ``verification`` (CRPS, rank
+    histogram, spread-skill and coverage: the dict of ``kern.ens_verify_merge_host``; ``fair`` = the unbiased CRPS) and the
+    maps ``crps_map`` (fp32, NaN where invalid) and ``rank_map`` (uint8, 255 where invalid), both (T, C, H, W).  Without
+    it the result is what it was."""
     models = list(models)
     M, T, dev = len(models), len(dataset), dataset.device
     if not (1 <= M <= 32):
@@ -187,6 +195,10 @@ def evaluate_ensemble(models: Iterable[nn.Module], dataset, batch_size: int, mas
     if len(gates) != M:
         raise ValueError("one input gate (or None) per member")
     mask_u8 = _mask_u8(mask, dev)
+    verif = crps_map = rank_map = None
+    if verify:
+        verif = EnsembleVerification(dev, M, mask=mask_u8, scale=1.0 if affine is None else affine[0], fair=fair,
+                                     capacity=-(-T // batch_size))
     member_metrics = [RegressionMetrics(dev, affine=affine, mask=mask_u8) for _ in range(M)]
     slab = mean_map = std_map = preds_ts = trues_ts = None
     with _eval_mode(models + gates), torch.no_grad():
@@ -203,10 +215,15 @@ def evaluate_ensemble(models: Iterable[nn.Module], dataset, batch_size: int, mas
                     std_map = torch.empty_like(mean_map)
                     preds_ts = torch.empty((M, T, Cn), device=dev, dtype=torch.float64)
                     trues_ts = torch.empty((T, Cn), device=dev, dtype=torch.float64)
+                    if verify:
+                        crps_map = torch.empty_like(mean_map)
+                        rank_map = torch.empty((T, Cn, H, W), device=dev, dtype=torch.uint8)
                 K.copy_slab(hr, slab[m, :hi - lo])
                 member_metrics[m].update(slab[m, :hi - lo], truth)
                 preds_ts[m, lo:hi].copy_(K.masked_plane_mean(slab[m, :hi - lo], mask_u8)[0])
             K.ensemble_stats(slab[:, :hi - lo], mean_map[lo:hi], std_map[lo:hi])
+            if verify:
+                verif.update(slab[:, :hi - lo], truth, crps_map=crps_map[lo:hi], rank_map=rank_map[lo:hi])
             trues_ts[lo:hi].copy_(K.masked_plane_mean(truth if truth.is_contiguous() else truth.contiguous(), mask_u8)[0])
         mean_preds, std_preds = K.ensemble_stats(preds_ts)
         final = torch.zeros(8, dtype=torch.float64, device=dev)
@@ -217,5 +234,8 @@ def evaluate_ensemble(models: Iterable[nn.Module], dataset, batch_size: int, mas
     for k in counts:
         members.append(K.eval_merge_host(host[at:at + k])[1])
         at += k
-    return {"mean_preds": mean_preds, "std_preds": std_preds, "r2": K.eval_merge_host(host[at:])[1]["r2"],
-            "members": members, "mean_map": mean_map, "std_map": std_map, "preds_ts": preds_ts, "trues_ts": trues_ts}
+    out = {"mean_preds": mean_preds, "std_preds": std_preds, "r2": K.eval_merge_host(host[at:])[1]["r2"],
+           "members": members, "mean_map": mean_map, "std_map": std_map, "preds_ts": preds_ts, "trues_ts": trues_ts}
+    if verify:
+        out.update(verification=verif.compute(), crps_map=crps_map, rank_map=rank_map)
+    return out

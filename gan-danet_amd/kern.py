@@ -2032,3 +2032,101 @@ def trend_test_host(x, times, period: int = 0, mask=None, flags: int = L.TREND_C
     L.check(lib().gd_trend_test_host(x.ctypes.data, dt, T, M, times.ctypes.data, int(period), None if mask is None else mask.ctypes.data,
                                      int(flags), float(zq), out.ctypes.data), "gd_trend_test_host")
     return out
+
+
+# ---- ensemble verification (include/gandanet.h, "Ensemble verification"; ensverify.hip) ------------------------------------
+def ens_verify_flags(f64: bool, fair: bool) -> int:
+    return (L.ENSV_F64 if f64 else 0) | (L.ENSV_FAIR if fair else 0)
+
+
+def _ens_members(x, is_host: bool, fn: str):
+    """(M, n, member stride in elements) of a stack of members (M, ...): every member dense, a constant stride apart"""
+    M = x.shape[0] if x.ndim >= 2 else 0
+    if not (1 <= M <= L.ENSV_MAX_M):
+        raise L.GandanetError(f"{fn}: expected (M, ...) members with 1 <= M <= {L.ENSV_MAX_M}, got shape {tuple(x.shape)}")
+    dense = x[0].flags["C_CONTIGUOUS"] if is_host else x[0].is_contiguous()
+    n = int(x[0].size if is_host else x[0].numel())
+    if not dense or n == 0:
+        raise L.GandanetError(f"{fn}: every member must be dense and non-empty")
+    stride = n if M == 1 else (x.strides[0] // x.itemsize if is_host else x.stride(0))
+    if M > 1 and stride < n:
+        raise L.GandanetError(f"{fn}: members {stride} elements apart overlap ({n} elements each)")
+    return M, n, int(stride)
+
+
+def ens_verify(x: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] = None, scale: float = 1.0, fair: bool = False,
+               crps_map: Optional[Tensor] = None, err_map: Optional[Tensor] = None, spread_map: Optional[Tensor] = None,
+               rank_map: Optional[Tensor] = None) -> Tensor:
+    """the verification record (L.ENSV_REC fp64) of the members ``x`` (M, ...) against ``truth`` (...) written into
+    ``rec`` (a dense view on the device), and the per-element maps that are given (the float ones in the input dtype,
+    ``rank_map`` uint8, each dense with as many elements as ``truth``).  ``mask`` (uint8) covers the trailing dims and is
+    shared by all leading planes.  No host sync."""
+    if not x.is_cuda or x.dtype not in (torch.float32, torch.float64):
+        raise L.GandanetError(f"ens_verify: expected float32 / float64 GPU members, got {x.dtype} on {x.device}")
+    M, n, stride = _ens_members(x, False, "ens_verify")
+    _dense(truth, "ens_verify truth", x.dtype)
+    if truth.numel() != n:
+        raise L.GandanetError(f"ens_verify: members of {n} elements against a truth of {truth.numel()}")
+    _dense(rec, "ens_verify record", torch.float64)
+    if rec.numel() != L.ENSV_REC:
+        raise L.GandanetError(f"ens_verify: the record is {L.ENSV_REC} contiguous float64")
+    hw = n if mask is None else mask.numel()
+    if hw <= 0 or n % hw:
+        raise L.GandanetError(f"ens_verify: a mask of {hw} entries does not tile {tuple(truth.shape)}")
+    mask = _eval_mask(mask, hw)
+    for o, nm, dt in ((crps_map, "crps_map", x.dtype), (err_map, "err_map", x.dtype), (spread_map, "spread_map", x.dtype),
+                      (rank_map, "rank_map", torch.uint8)):
+        if o is not None and (_dense(o, "ens_verify " + nm, dt).numel() != n):
+            raise L.GandanetError(f"ens_verify: {nm} must hold {n} elements, got {tuple(o.shape)}")
+    nbytes = int(lib().gd_ens_verify_ws_bytes(n))
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    L.check(lib().gd_ens_verify(_ptr(x), M, stride, _ptr(truth), n // hw, hw, _ptr(mask), float(scale),
+                                ens_verify_flags(x.dtype == torch.float64, fair), _ptr(rec), _ptr(crps_map), _ptr(err_map),
+                                _ptr(spread_map), _ptr(rank_map), _ptr(ws), nbytes, _stream()), "gd_ens_verify")
+    return rec
+
+
+def ens_verify_host(x, truth, mask=None, scale: float = 1.0, fair: bool = False, maps: bool = True):
+    """``ens_verify`` on HOST arrays (plain C++ over the same per-element core, walking the device's grid; no GPU):
+    (record, maps) with maps = dict(crps, err, spread, rank) shaped like ``truth``, or None"""
+    import numpy as np
+    x = np.asarray(x)
+    if x.dtype not in (np.float32, np.float64):
+        raise L.GandanetError(f"ens_verify_host: expected float32 / float64 members, got {x.dtype}")
+    M, n, stride = _ens_members(x, True, "ens_verify_host")
+    truth = np.ascontiguousarray(truth, dtype=x.dtype)
+    if truth.size != n:
+        raise L.GandanetError(f"ens_verify_host: members of {n} elements against a truth of {truth.size}")
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    hw = n if mask is None else mask.size
+    if hw <= 0 or n % hw:
+        raise L.GandanetError(f"ens_verify_host: a mask of {hw} entries does not tile {truth.shape}")
+    rec = np.empty(L.ENSV_REC)
+    out = None
+    if maps:
+        out = {"crps": np.empty(truth.shape, x.dtype), "err": np.empty(truth.shape, x.dtype), "spread": np.empty(truth.shape, x.dtype),
+               "rank": np.empty(truth.shape, np.uint8)}
+    ptr = lambda k: out[k].ctypes.data if maps else None
+    L.check(lib().gd_ens_verify_host(x.ctypes.data, M, stride, truth.ctypes.data, n // hw, hw, None if mask is None else mask.ctypes.data,
+                                     float(scale), ens_verify_flags(x.dtype == np.float64, fair), rec.ctypes.data, ptr("crps"), ptr("err"),
+                                     ptr("spread"), ptr("rank")), "gd_ens_verify_host")
+    return rec, out
+
+
+def ens_verify_merge_host(records, M: int) -> Tuple[list, dict]:
+    """add (k, L.ENSV_REC) host records in the given order (plain C++ on the host, no GPU): (merged record, metrics dict).
+    ``coverage`` maps the nominal levels L.ENSV_LEVELS to the observed fractions; ``rank_hist`` holds M + 1 fractions"""
+    import numpy as np
+    recs = np.ascontiguousarray(np.asarray(records, dtype=np.float64).reshape(-1, L.ENSV_REC))
+    out, met = (C.c_double * L.ENSV_REC)(), (C.c_double * L.ENSV_METRICS)()
+    ptr = recs.ctypes.data_as(C.POINTER(C.c_double)) if len(recs) else None
+    L.check(lib().gd_ens_verify_merge_host(ptr, len(recs), int(M), out, met), "gd_ens_verify_merge_host")
+    d = {"n": out[0], "M": int(M)}
+    d.update({nm: met[k] for k, nm in enumerate(L.ENSV_METRIC_NAMES)})
+    d["coverage"] = {lv: met[L.ENSV_M_COVER + k] for k, lv in enumerate(L.ENSV_LEVELS)}
+    d["reliability"] = met[L.ENSV_M_RELIABILITY]
+    d["tied"] = met[L.ENSV_M_TIED]
+    d["rank_hist"] = [met[L.ENSV_M_HIST + b] for b in range(int(M) + 1)]
+    d["rank_counts"] = [out[L.ENSV_HIST + b] for b in range(int(M) + 1)]
+    d["cover_counts"] = [out[L.ENSV_COVER + k] for k in range(4)]
+    return list(out), d

@@ -999,6 +999,63 @@ int gd_trend_test(const void* x, int dtype, long T, long M, const double* times,
 int gd_trend_test_host(const void* x, int dtype, long T, long M, const double* times, int period, const unsigned char* mask,
                        int flags, double zq, double* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Ensemble verification (ensverify.hip, csrc/ensverify_core.h): is the spread of an ensemble the right size?  The
+ * continuous ranked probability score, the rank (Talagrand) histogram, the spread against the error of the ensemble mean
+ * and the coverage of the +-k sigma intervals, of the members in the slab of evaluate_ensemble against the truth of the
+ * same batch, without a copy of any prediction to the host.
+ * x: M member arrays (1 <= M <= GD_ENSV_MAX_M) of n = planes * hw elements, member_stride elements apart (>= n when M > 1);
+ * y: the truth, n elements; storage fp32, or fp64 with GD_ENSV_F64.  mask: NULL or hw bytes shared by all planes, nonzero =
+ * valid.  An element is VALID when the mask allows it, the truth is not NaN and no member is NaN (an input that holds an
+ * infinity has unspecified outputs).  All arithmetic fp64, every operation rounded on its own.  Per valid element, with
+ * d_i = (double)x_i - (double)y sorted ascending to d_(0) <= ... <= d_(M-1) and every sum taken in that order from +0.0:
+ *   less = #{d_i < 0}, ties = #{d_i == 0};  rank bin = less + ties / 2 (integer division): 0 .. M;
+ *   e    = (sum d_(i)) / M, the error of the ensemble mean;  s^2 = sum (d_(i) - e)^2 / (M - 1), 0 at M = 1;  s = sqrt(s^2);
+ *   A    = (sum |d_(i)|) / M;  G = sum (2 i - M + 1) d_(i), which is sum over i < j of |x_i - x_j|;
+ *   crps = A - G / M^2, and A - G / (M (M - 1)) under GD_ENSV_FAIR (refused at M = 1);
+ *   crps_gauss = s (z erf(z / sqrt 2) + 2 phi(z) - 1 / sqrt pi), z = -e / s, phi the normal density; |e| where s = 0:
+ *          the CRPS of the normal distribution N(mean, s^2) that a mean map and a std map stand for;
+ *   cover_k = |e| <= z_k s for z_k = 0.674489750196082, 1, 1.644853626951472, 1.959963984540054: the nominal levels
+ *          0.5, 0.6826894921370859, 0.9, 0.95.
+ * The affine v a + b of a scaler's inverse acts on differences as `scale` = a > 0 alone; it is applied last: crps,
+ * crps_gauss, e and s are multiplied by scale (s^2 by scale^2).
+ * Maps (each may be NULL; n elements; every element is written): crps_map, err_map (e), spread_map (s) in the input
+ * dtype, rounded once, NaN at an invalid element; rank_map uint8, 255 at an invalid element.
+ * rec: GD_ENSV_REC doubles on the device, the sums over the valid elements:
+ *   [GD_ENSV_N] n   [GD_ENSV_TIED] elements with ties > 0   [GD_ENSV_CRPS] sum crps   [GD_ENSV_CRPS_GAUSS] sum crps_gauss
+ *   [GD_ENSV_ABS_E] sum |e|   [GD_ENSV_E2] sum e^2   [GD_ENSV_S2] sum s^2   [GD_ENSV_COVER + k] the four coverage counts
+ *   [GD_ENSV_HIST + b] the rank histogram, b = 0 .. M (GD_ENSV_BINS slots; those behind M stay 0).
+ * Counts are exact integers (below 2^53).  A zero record is neutral and records add, so they travel between batches and
+ * ranks like those of gd_eval_stats.
+ * Reduction: a workgroup of 256 threads, one element per lane and trip over the grid gd_ensv_grid(planes, hw) of
+ * ensverify_core.h (at most 1024 workgroups; without a mask the array is one plane); float sums in registers, then a fixed
+ * tree per wave, the waves ascending, one partial record per workgroup in ws (gd_ens_verify_ws_bytes), and one wave that
+ * adds the partials in ascending order.  Counts by integer adds in LDS.  No global atomics, no float atomics: bitwise
+ * reproducible.  gd_ens_verify_host is plain C++ over the same core without a GPU; it walks the same grid in the same
+ * order, so every map and every record field equals the device's bit for bit, except [GD_ENSV_CRPS_GAUSS] (erf and exp
+ * are each side's library), which agrees to the rounding of those two functions.
+ * gd_ens_verify_merge_host (host only): adds k records (k x GD_ENSV_REC doubles) in the given order into rec_out (may be
+ * NULL) and derives metrics[GD_ENSV_METRICS]: crps, crps_gauss, mae = sum |e| / n, rmse = sqrt(sum e^2 / n), spread =
+ * sqrt(sum s^2 / n), spread_skill = sqrt((M + 1) / M) spread / rmse (1 for a statistically consistent ensemble; NaN at
+ * M = 1 or rmse = 0), the four coverage fractions, reliability = sum over b <= M of |hist_b / n - 1 / (M + 1)|, tied =
+ * the share of elements with a tie, and the histogram as fractions.  n = 0 (or k = 0): every metric is NaN.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_ENSV_MAX_M 32
+enum { GD_ENSV_F64 = 1, GD_ENSV_FAIR = 2 };
+enum { GD_ENSV_N = 0, GD_ENSV_TIED = 1, GD_ENSV_CRPS = 2, GD_ENSV_CRPS_GAUSS = 3, GD_ENSV_ABS_E = 4, GD_ENSV_E2 = 5, GD_ENSV_S2 = 6,
+       GD_ENSV_COVER = 7, GD_ENSV_HIST = 11, GD_ENSV_BINS = 33, GD_ENSV_REC = 44 };
+enum { GD_ENSV_M_CRPS = 0, GD_ENSV_M_CRPS_GAUSS = 1, GD_ENSV_M_MAE = 2, GD_ENSV_M_RMSE = 3, GD_ENSV_M_SPREAD = 4,
+       GD_ENSV_M_SPREAD_SKILL = 5, GD_ENSV_M_COVER = 6, GD_ENSV_M_RELIABILITY = 10, GD_ENSV_M_TIED = 11, GD_ENSV_M_HIST = 12,
+       GD_ENSV_METRICS = 45 };
+size_t gd_ens_verify_ws_bytes(long n);
+int gd_ens_verify(const void* x, int M, long member_stride, const void* y, long planes, long hw, const unsigned char* mask,
+                  double scale, int flags, double* rec, void* crps_map, void* err_map, void* spread_map, unsigned char* rank_map,
+                  void* ws, size_t ws_bytes, void* stream);
+int gd_ens_verify_host(const void* x, int M, long member_stride, const void* y, long planes, long hw, const unsigned char* mask,
+                       double scale, int flags, double* rec, void* crps_map, void* err_map, void* spread_map,
+                       unsigned char* rank_map);
+int gd_ens_verify_merge_host(const double* recs, long k, int M, double* rec_out, double* metrics);
+
 #ifdef __cplusplus
 }
 #endif
