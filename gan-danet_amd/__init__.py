@@ -26,6 +26,8 @@ from .trend import TrendTest, mann_kendall, normal_quantile, sen_slope, trend_te
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from . import verification
 from .verification import EnsembleVerification, ensemble_scores
+from . import eof
+from .eof import EOFResult, eof_analysis
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

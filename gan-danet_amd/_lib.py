@@ -35,6 +35,8 @@ ENSV_COVER, ENSV_HIST, ENSV_BINS, ENSV_REC = 7, 11, 33, 44   # GD_ENSV_COVER, GD
 ENSV_METRIC_NAMES = ("crps", "crps_gauss", "mae", "rmse", "spread", "spread_skill")   # GD_ENSV_M_*: metric slot k
 ENSV_M_COVER, ENSV_M_RELIABILITY, ENSV_M_TIED, ENSV_M_HIST, ENSV_METRICS = 6, 10, 11, 12, 45
 ENSV_LEVELS = (0.5, 0.6826894921370859, 0.9, 0.95)   # the nominal levels of the four coverage counts
+EOF_MAX_T, EOF_MAX_K = 256, 16   # GD_EOF_MAX_T, GD_EOF_MAX_K
+EOF_CHUNK, EOF_SPLIT_MIN, EOF_SPLIT_MAX = 32, 8, 256   # GD_EOF_CHUNK, GD_EOF_SPLIT_MIN, GD_EOF_SPLIT_MAX (csrc/eof_core.h)
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -225,6 +227,15 @@ SIGNATURES = {
     "gd_ens_verify": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gd_ens_verify_host": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p]),
     "gd_ens_verify_merge_host": (_i, [C.POINTER(C.c_double), _l, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gd_eof_prepare": (_i, [_p, _i, _l, _l, _p, _p, _i, _p, _p, _p]),
+    "gd_eof_prepare_host": (_i, [_p, _i, _l, _l, _p, _p, _i, _p, _p]),
+    "gd_eof_gram_ws_bytes": (_sz, [_l, _l]),
+    "gd_eof_gram": (_i, [_p, _i, _l, _l, _p, _p, _p, _p, _p, _sz, _p]),
+    "gd_eof_gram_host": (_i, [_p, _i, _l, _l, _p, _p, _p, _p]),
+    "gd_eof_project": (_i, [_p, _i, _l, _l, _p, _p, _p, _i, _p, _i, _p, _p]),
+    "gd_eof_project_host": (_i, [_p, _i, _l, _l, _p, _p, _p, _i, _p, _i, _p]),
+    "gd_eof_reconstruct": (_i, [_p, _p, _p, _p, _p, _l, _l, _i, _p, _i, _p]),
+    "gd_eof_reconstruct_host": (_i, [_p, _p, _p, _p, _p, _l, _l, _i, _p, _i]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

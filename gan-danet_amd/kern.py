@@ -2130,3 +2130,172 @@ def ens_verify_merge_host(records, M: int) -> Tuple[list, dict]:
     d["rank_counts"] = [out[L.ENSV_HIST + b] for b in range(int(M) + 1)]
     d["cover_counts"] = [out[L.ENSV_COVER + k] for k in range(4)]
     return list(out), d
+
+
+# ---- EOF analysis (include/gandanet.h, "EOF analysis"; eof.hip) ---------------------------------------------------------------
+def _eof_vec(t: Optional[Tensor], M: int, name: str, dtype=torch.float64) -> Optional[Tensor]:
+    if t is None:
+        return None
+    _dense(t, name, dtype)
+    if t.numel() != M:
+        raise L.GandanetError(f"{name}: expected {M} entries (one per series), got {tuple(t.shape)}")
+    return t
+
+
+def eof_prepare(x: Tensor, mask: Optional[Tensor] = None, weight: Optional[Tensor] = None, center: bool = True,
+                mean: Optional[Tensor] = None, valid: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(mean (M) fp64, valid (M) uint8) of the M series of a dense fp32 / fp64 ``x`` (T, M); ``mask``: M uint8; ``weight``:
+    M fp64; ``mean`` and ``valid`` may be dense views to write into.  No host sync."""
+    dt = _series_2d(x, "eof_prepare input")
+    T, M = x.shape
+    mask, weight = _eval_mask(mask, M), _eof_vec(weight, M, "eof_prepare weight")
+    mean = torch.empty(M, device=x.device, dtype=torch.float64) if mean is None else _eof_vec(mean, M, "eof_prepare mean")
+    valid = torch.empty(M, device=x.device, dtype=torch.uint8) if valid is None else _eof_vec(valid, M, "eof_prepare valid", torch.uint8)
+    L.check(lib().gd_eof_prepare(_ptr(x), dt, T, M, _ptr(mask), _ptr(weight), int(bool(center)), _ptr(mean), _ptr(valid), _stream()),
+            "gd_eof_prepare")
+    return mean, valid
+
+
+def eof_gram_ws_bytes(T: int, M: int) -> int:
+    return int(lib().gd_eof_gram_ws_bytes(int(T), int(M)))
+
+
+def eof_gram(x: Tensor, mean: Tensor, valid: Tensor, weight: Optional[Tensor] = None, out: Optional[Tensor] = None,
+             ws: Optional[Tensor] = None) -> Tensor:
+    """the (T, T) fp64 Gram matrix of the weighted anomalies of the dense fp32 / fp64 ``x`` (T, M), 2 <= T <= L.EOF_MAX_T;
+    ``out`` and the uint8 workspace ``ws`` (eof_gram_ws_bytes) are allocated unless given.  No host sync."""
+    dt = _series_2d(x, "eof_gram input")
+    T, M = x.shape
+    _eof_vec(mean, M, "eof_gram mean")
+    _eof_vec(valid, M, "eof_gram valid", torch.uint8)
+    _eof_vec(weight, M, "eof_gram weight")
+    if out is None:
+        out = torch.empty((T, T), device=x.device, dtype=torch.float64)
+    _dense(out, "eof_gram output", torch.float64)
+    if out.numel() != T * T:
+        raise L.GandanetError(f"eof_gram: the output is ({T}, {T}) float64, got {tuple(out.shape)}")
+    nbytes = eof_gram_ws_bytes(T, M)
+    if ws is None:
+        ws = torch.empty(max(nbytes, 8), device=x.device, dtype=torch.uint8)
+    _dense(ws, "eof_gram workspace", torch.uint8)
+    L.check(lib().gd_eof_gram(_ptr(x), dt, T, M, _ptr(mean), _ptr(valid), _ptr(weight), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+            "gd_eof_gram")
+    return out
+
+
+def eof_project(x: Tensor, mean: Tensor, valid: Tensor, coef: Tensor, weight: Optional[Tensor] = None, use_weight: bool = False,
+                out: Optional[Tensor] = None) -> Tensor:
+    """(K, M) fp64 planes out[k, m] = s_m sum_t coef[t, k] (x[t, m] - mean[m]) for ``coef`` (T, K) fp64 on the device,
+    1 <= K <= L.EOF_MAX_K; ``out`` may be a dense (K, M) view to write into.  No host sync."""
+    dt = _series_2d(x, "eof_project input")
+    T, M = x.shape
+    _eof_vec(mean, M, "eof_project mean")
+    _eof_vec(valid, M, "eof_project valid", torch.uint8)
+    _eof_vec(weight, M, "eof_project weight")
+    _dense(coef, "eof_project coefficients", torch.float64)
+    if coef.dim() != 2 or coef.shape[0] != T or not 1 <= coef.shape[1] <= L.EOF_MAX_K:
+        raise L.GandanetError(f"eof_project: the coefficients are ({T}, K) float64 with 1 <= K <= {L.EOF_MAX_K}, got {tuple(coef.shape)}")
+    K = coef.shape[1]
+    if out is None:
+        out = torch.empty((K, M), device=x.device, dtype=torch.float64)
+    _dense(out, "eof_project output", torch.float64)
+    if tuple(out.shape) != (K, M):
+        raise L.GandanetError(f"eof_project: the output is ({K}, {M}) float64, got {tuple(out.shape)}")
+    L.check(lib().gd_eof_project(_ptr(x), dt, T, M, _ptr(mean), _ptr(valid), _ptr(weight), int(bool(use_weight)), _ptr(coef), K, _ptr(out),
+                                 _stream()), "gd_eof_project")
+    return out
+
+
+def eof_reconstruct(eofs: Tensor, pcs: Tensor, mean: Tensor, valid: Tensor, weight: Optional[Tensor] = None,
+                    dtype=torch.float64, out: Optional[Tensor] = None) -> Tensor:
+    """(T, M) in ``dtype`` (fp32 / fp64): mean[m] + (sum_k pcs[t, k] eofs[k, m]) / sqrt(weight[m]) for ``eofs`` (K, M) and
+    ``pcs`` (T, K) fp64 on the device, 1 <= K <= L.EOF_MAX_K; ``out`` may be a dense (T, M) view of ``dtype`` to write into.
+    No host sync."""
+    _dense(eofs, "eof_reconstruct eofs", torch.float64)
+    _dense(pcs, "eof_reconstruct pcs", torch.float64)
+    if eofs.dim() != 2 or pcs.dim() != 2 or pcs.shape[1] != eofs.shape[0] or not 1 <= eofs.shape[0] <= L.EOF_MAX_K:
+        raise L.GandanetError(f"eof_reconstruct: eofs (K, M) and pcs (T, K) with 1 <= K <= {L.EOF_MAX_K}, got {tuple(eofs.shape)} and "
+                              f"{tuple(pcs.shape)}")
+    if dtype not in (torch.float32, torch.float64):
+        raise L.GandanetError(f"eof_reconstruct: the output is float32 or float64, got {dtype}")
+    (K, M), T = eofs.shape, pcs.shape[0]
+    _eof_vec(mean, M, "eof_reconstruct mean")
+    _eof_vec(valid, M, "eof_reconstruct valid", torch.uint8)
+    _eof_vec(weight, M, "eof_reconstruct weight")
+    if out is None:
+        out = torch.empty((T, M), device=eofs.device, dtype=dtype)
+    _dense(out, "eof_reconstruct output", dtype)
+    if tuple(out.shape) != (T, M):
+        raise L.GandanetError(f"eof_reconstruct: the output is ({T}, {M}) {dtype}, got {tuple(out.shape)}")
+    L.check(lib().gd_eof_reconstruct(_ptr(eofs), _ptr(pcs), _ptr(mean), _ptr(valid), _ptr(weight), T, M, K, _ptr(out),
+                                     int(dtype == torch.float64), _stream()), "gd_eof_reconstruct")
+    return out
+
+
+def _np_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _eof_host_args(x, mean, valid, weight, fn: str):
+    import numpy as np
+    x, dt = _host_f(x, fn)
+    if x.ndim != 2:
+        raise L.GandanetError(f"{fn}: expected a (T, M) array, got {x.shape}")
+    M = x.shape[1]
+    mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+    valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+    weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+    if mean.size != M or valid.size != M or (weight is not None and weight.size != M):
+        raise L.GandanetError(f"{fn}: mean, valid and weight hold one entry per series ({M})")
+    return x, dt, mean, valid, weight
+
+
+def eof_prepare_host(x, mask=None, weight=None, center: bool = True):
+    """``eof_prepare`` on HOST arrays (plain C++ over the same arithmetic, no GPU): (mean, valid)"""
+    import numpy as np
+    x, dt = _host_f(x, "eof_prepare_host")
+    T, M = x.shape
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+    mean, valid = np.empty(M), np.empty(M, dtype=np.uint8)
+    L.check(lib().gd_eof_prepare_host(x.ctypes.data, dt, T, M, _np_ptr(mask), _np_ptr(weight), int(bool(center)), mean.ctypes.data,
+                                      valid.ctypes.data), "gd_eof_prepare_host")
+    return mean, valid
+
+
+def eof_gram_host(x, mean, valid, weight=None):
+    """``eof_gram`` on HOST arrays: the (T, T) Gram matrix, every entry summed over m in ascending order"""
+    import numpy as np
+    x, dt, mean, valid, weight = _eof_host_args(x, mean, valid, weight, "eof_gram_host")
+    T, M = x.shape
+    G = np.empty((T, T))
+    L.check(lib().gd_eof_gram_host(x.ctypes.data, dt, T, M, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), G.ctypes.data),
+            "gd_eof_gram_host")
+    return G
+
+
+def eof_project_host(x, mean, valid, coef, weight=None, use_weight: bool = False):
+    """``eof_project`` on HOST arrays: (K, M)"""
+    import numpy as np
+    x, dt, mean, valid, weight = _eof_host_args(x, mean, valid, weight, "eof_project_host")
+    T, M = x.shape
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    K = coef.shape[1]
+    out = np.empty((K, M))
+    L.check(lib().gd_eof_project_host(x.ctypes.data, dt, T, M, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), int(bool(use_weight)),
+                                      coef.ctypes.data, K, out.ctypes.data), "gd_eof_project_host")
+    return out
+
+
+def eof_reconstruct_host(eofs, pcs, mean, valid, weight=None, dtype="float64"):
+    """``eof_reconstruct`` on HOST arrays: (T, M) in ``dtype``"""
+    import numpy as np
+    eofs, pcs = np.ascontiguousarray(eofs, dtype=np.float64), np.ascontiguousarray(pcs, dtype=np.float64)
+    (K, M), T = eofs.shape, pcs.shape[0]
+    mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+    valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+    weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+    out = np.empty((T, M), dtype=np.dtype(dtype))
+    L.check(lib().gd_eof_reconstruct_host(eofs.ctypes.data, pcs.ctypes.data, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), T, M, K,
+                                          out.ctypes.data, int(out.dtype == np.float64)), "gd_eof_reconstruct_host")
+    return out

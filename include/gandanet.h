@@ -1056,6 +1056,66 @@ int gd_ens_verify_host(const void* x, int M, long member_stride, const void* y, 
                        unsigned char* rank_map);
 int gd_ens_verify_merge_host(const double* recs, long k, int M, double* rec_out, double* metrics);
 
+/* ------------------------------------------------------------------------------------------
+ * EOF analysis (eof.hip, csrc/eof_core.h): the pieces of an empirical-orthogonal-function / principal-component analysis
+ * of a (T, M) cube whose time axis is short (T <= GD_EOF_MAX_T) and whose space axis is long: validity and mean of every
+ * series, the T x T Gram matrix of the weighted anomalies, the projection of every series on K coefficient columns (EOFs,
+ * covariance maps) and the rank-K reconstruction.  The eigen-decomposition of the Gram matrix is the caller's (256 x 256
+ * doubles at most; gan_danet_amd/eof.py uses numpy.linalg.eigh).
+ * The layout is that of "Per-pixel time series": series m of a dense (T, M) array at x[t * M + m], storage fp32 (dtype 0)
+ * or fp64 (dtype 1), all arithmetic fp64.  mean: M doubles; valid: M bytes; weight: NULL or M doubles >= 0 (an area
+ * weight, for instance cos(lat)).  The WEIGHTED ANOMALY is
+ *   a[t, m] = sqrt(weight[m]) * ((double)x[t, m] - mean[m])   for valid m,   exactly 0 for invalid m
+ * (a select: the samples of an invalid series may be NaN).  The caller owns all memory, nothing is allocated, nothing waits
+ * for the device, no atomics: every result is bitwise reproducible.  Every entry has a host twin (`_host`, no GPU call,
+ * every pointer in HOST memory); prepare, project and reconstruct run the same operations in the same order on both sides
+ * (eof_core.h, every operation rounded on its own) and agree bit for bit.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_EOF_MAX_T 256 /* time steps of gd_eof_gram: 16 blocks of 16 rows, 136 blocks on and above the diagonal */
+#define GD_EOF_MAX_K 16  /* coefficient columns of one gd_eof_project / gd_eof_reconstruct call: K register accumulators */
+/* valid[m] = 1 iff the mask byte is nonzero (or mask is NULL), every sample of the series is finite, and the weight is
+ * finite and > 0 (or weight is NULL): a series with a gap is left out whole, the missing set of an EOF analysis is fixed
+ * in time.  mean[m] = (x[0, m] + x[1, m] + ... in ascending t, from +0.0) / T when center, else 0; 0 for an invalid
+ * series.  One thread per series. */
+int gd_eof_prepare(const void* x, int dtype, long T, long M, const unsigned char* mask, const double* weight, int center,
+                   double* mean, unsigned char* valid, void* stream);
+int gd_eof_prepare_host(const void* x, int dtype, long T, long M, const unsigned char* mask, const double* weight, int center,
+                        double* mean, unsigned char* valid);
+/* G (T, T) doubles: G[t, s] = sum over m of a[t, m] a[s, m]; no division.  2 <= T <= GD_EOF_MAX_T.
+ * On v_mfma_f64_16x16x4_f64: T is padded to 16 nb rows; a workgroup of 8 waves stages the anomalies of 32 series for all
+ * rows in LDS (fp64, rows 34 doubles apart so that the fragment reads are free of bank conflicts; padded rows, invalid
+ * series and series beyond M are zeros) and accumulates the nb (nb + 1) / 2 blocks of 16 x 16 on and above the diagonal,
+ * each wave a fixed contiguous run of them, a row fragment read once per 4 series and used by every block of the wave
+ * that touches its row block.  The series are split over at most 256 workgroups in runs of 32-series chunks (at least 8
+ * chunks per split; csrc/eof_core.h gd_eof_geom, a function of (T, M) alone); each writes one partial slab into ws
+ * (gd_eof_gram_ws_bytes), and a second launch adds the slabs in ascending order and writes both triangles from the
+ * upper one: G is exactly symmetric and two runs give the same bits.
+ * The host twin adds over m in ascending order and is NOT bit-equal to the device; with n valid series both satisfy
+ *   |G^[t, s] - G[t, s]| <= (n + 3) 2^-53 sum_m |a[t, m]| |a[s, m]|   (for any order of the sum).
+ * gd_eof_gram_ws_bytes is 0 for a shape that gd_eof_gram refuses. */
+size_t gd_eof_gram_ws_bytes(long T, long M);
+int gd_eof_gram(const void* x, int dtype, long T, long M, const double* mean, const unsigned char* valid, const double* weight,
+                double* G, void* ws, size_t ws_bytes, void* stream);
+int gd_eof_gram_host(const void* x, int dtype, long T, long M, const double* mean, const unsigned char* valid,
+                     const double* weight, double* G);
+/* coef (T, K) doubles, row t at coef[t * K]; out (K, M) doubles, planar:
+ *   out[k, m] = s_m * sum over t (ascending, from +0.0) of coef[t, k] * ((double)x[t, m] - mean[m]),
+ * s_m = sqrt(weight[m]) with use_weight (weight must be given), else 1; NaN for an invalid series.
+ * 1 <= K <= GD_EOF_MAX_K.  One thread per series with K register accumulators; the rows of coef are uniform across lanes.
+ * With coef = U Lambda^-1/2 (eigenvectors and eigenvalues of G) and use_weight these are the EOFs, of unit norm in the
+ * weighted space; with the standardised PCs divided by (T - ddof) and use_weight = 0, the covariance maps. */
+int gd_eof_project(const void* x, int dtype, long T, long M, const double* mean, const unsigned char* valid, const double* weight,
+                   int use_weight, const double* coef, int K, double* out, void* stream);
+int gd_eof_project_host(const void* x, int dtype, long T, long M, const double* mean, const unsigned char* valid,
+                        const double* weight, int use_weight, const double* coef, int K, double* out);
+/* eofs (K, M) doubles planar, pcs (T, K) doubles; out (T, M) in out_dtype (fp32 0 / fp64 1):
+ *   out[t, m] = mean[m] + (sum over k (ascending, from +0.0) of pcs[t, k] * eofs[k, m]) / sqrt(weight[m])
+ * (no division when weight is NULL), rounded once to out_dtype; NaN for an invalid series.  1 <= K <= GD_EOF_MAX_K. */
+int gd_eof_reconstruct(const double* eofs, const double* pcs, const double* mean, const unsigned char* valid, const double* weight,
+                       long T, long M, int K, void* out, int out_dtype, void* stream);
+int gd_eof_reconstruct_host(const double* eofs, const double* pcs, const double* mean, const unsigned char* valid,
+                            const double* weight, long T, long M, int K, void* out, int out_dtype);
+
 #ifdef __cplusplus
 }
 #endif
