@@ -28,6 +28,9 @@ from . import verification
 from .verification import EnsembleVerification, ensemble_scores
 from . import eof
 from .eof import EOFResult, eof_analysis
+from . import spectra
+from .spectra import (CrossSpectrum, Spectrum, cross_spectrum, effective_resolution, power_spectrum,
+                      spectral_ratio)
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

@@ -37,6 +37,8 @@ ENSV_M_COVER, ENSV_M_RELIABILITY, ENSV_M_TIED, ENSV_M_HIST, ENSV_METRICS = 6, 10
 ENSV_LEVELS = (0.5, 0.6826894921370859, 0.9, 0.95)   # the nominal levels of the four coverage counts
 EOF_MAX_T, EOF_MAX_K = 256, 16   # GD_EOF_MAX_T, GD_EOF_MAX_K
 EOF_CHUNK, EOF_SPLIT_MIN, EOF_SPLIT_MAX = 32, 8, 256   # GD_EOF_CHUNK, GD_EOF_SPLIT_MIN, GD_EOF_SPLIT_MAX (csrc/eof_core.h)
+SPEC_MAX_H, SPEC_MAX_W, SPEC_MAX_BINS = 1024, 2048, 1024   # GD_SPEC_MAX_H, GD_SPEC_MAX_W, GD_SPEC_MAX_BINS
+SPEC_DETREND = {"none": 0, "mean": 1, "plane": 2}          # GD_SPEC_DETREND_* (csrc/spectra_core.h)
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -236,6 +238,17 @@ SIGNATURES = {
     "gd_eof_project_host": (_i, [_p, _i, _l, _l, _p, _p, _p, _i, _p, _i, _p]),
     "gd_eof_reconstruct": (_i, [_p, _p, _p, _p, _p, _l, _l, _i, _p, _i, _p]),
     "gd_eof_reconstruct_host": (_i, [_p, _p, _p, _p, _p, _l, _l, _i, _p, _i]),
+    "gd_spec_twiddle_host": (_i, [_l, _p]),
+    "gd_spec_default_bins": (_i, [_l, _l, C.c_double, C.c_double]),
+    "gd_spec_bins_host": (_i, [_l, _l, C.c_double, C.c_double, _i, C.c_double, _p, _p, _p]),
+    "gd_spec_prepare": (_i, [_p, _i, _l, _l, _l, _p, _p, _p, _i, _p, _p, _p]),
+    "gd_spec_prepare_host": (_i, [_p, _i, _l, _l, _l, _p, _p, _p, _i, _p, _p]),
+    "gd_spec_power_ws_bytes": (_sz, [_l, _l, _l, _i]),
+    "gd_spec_power": (_i, [_p, _i, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    "gd_spec_power_host": (_i, [_p, _i, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "gd_spec_cross_ws_bytes": (_sz, [_l, _l, _l, _i]),
+    "gd_spec_cross": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
+    "gd_spec_cross_host": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

@@ -2299,3 +2299,207 @@ def eof_reconstruct_host(eofs, pcs, mean, valid, weight=None, dtype="float64"):
     L.check(lib().gd_eof_reconstruct_host(eofs.ctypes.data, pcs.ctypes.data, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), T, M, K,
                                           out.ctypes.data, int(out.dtype == np.float64)), "gd_eof_reconstruct_host")
     return out
+
+
+# ---- Spatial spectra (include/gandanet.h, "Spatial spectra"; spectra.hip) -----------------------------------------------------
+def spec_twiddle_host(N: int):
+    """cos and sin of 2 pi r / N, r = 0 .. N - 1, as one HOST array of 2 N doubles (octant reduction, within 1 ulp)"""
+    import numpy as np
+    tw = np.empty(2 * int(N))
+    L.check(lib().gd_spec_twiddle_host(int(N), tw.ctypes.data), "gd_spec_twiddle_host")
+    return tw
+
+
+def spec_default_bins(H: int, W: int, dy: float, dx: float) -> int:
+    return int(lib().gd_spec_default_bins(int(H), int(W), float(dy), float(dx)))
+
+
+def spec_bins_host(H: int, W: int, dy: float, dx: float, nbins: int, kmax: float = 0.0):
+    """the HOST bin table of an (H, W) grid of spacing (dy, dx): (bin (H, W // 2 + 1) int32, kcentre (nbins), count (nbins))"""
+    import numpy as np
+    H, W, nbins = int(H), int(W), int(nbins)
+    bins = np.empty((max(H, 0), max(W, 0) // 2 + 1), dtype=np.int32)
+    kc, count = np.empty(max(nbins, 0)), np.empty(max(nbins, 0), dtype=np.int64)
+    L.check(lib().gd_spec_bins_host(H, W, float(dy), float(dx), nbins, float(kmax), bins.ctypes.data, kc.ctypes.data, count.ctypes.data),
+            "gd_spec_bins_host")
+    return bins, kc, count
+
+
+def _spec_cube(x: Tensor, name: str) -> int:
+    dt = _filter_dtype(x, name)
+    if x.dim() != 3 or x.numel() == 0:
+        raise L.GandanetError(f"{name}: expected a dense, non-empty (T, H, W) tensor, got {tuple(x.shape)}")
+    return dt
+
+
+def _spec_vec(t: Optional[Tensor], n: int, name: str, dtype=torch.float64) -> Optional[Tensor]:
+    if t is None:
+        return None
+    _dense(t, name, dtype)
+    if t.numel() != n:
+        raise L.GandanetError(f"{name}: expected {n} entries, got {tuple(t.shape)}")
+    return t
+
+
+def _spec_out(t: Optional[Tensor], shape, like: Tensor, name: str) -> Tensor:
+    if t is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float64)
+    _dense(t, name, torch.float64)
+    if tuple(t.shape) != tuple(shape):
+        raise L.GandanetError(f"{name}: expected {tuple(shape)} float64, got {tuple(t.shape)}")
+    return t
+
+
+def spec_prepare(x: Tensor, mask: Optional[Tensor] = None, wy: Optional[Tensor] = None, wx: Optional[Tensor] = None,
+                 detrend: str = "mean", coef: Optional[Tensor] = None, S: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(coef (T, 3), S (T, 2)) fp64 of the fields of a dense fp32 / fp64 ``x`` (T, H, W): the detrend coefficients
+    (a, b, c) about the field's centre, and (sum of wy^2 wx^2, count) over the valid pixels.  ``mask``: H * W uint8 shared
+    by all fields; ``wy`` (H), ``wx`` (W): fp64 tapers.  No host sync."""
+    dt = _spec_cube(x, "spec_prepare input")
+    if detrend not in L.SPEC_DETREND:
+        raise L.GandanetError(f"spec_prepare: detrend is one of {sorted(L.SPEC_DETREND)}, got {detrend!r}")
+    T, H, W = x.shape
+    mask = _eval_mask(mask, H * W)
+    _spec_vec(wy, H, "spec_prepare wy")
+    _spec_vec(wx, W, "spec_prepare wx")
+    coef, S = _spec_out(coef, (T, 3), x, "spec_prepare coef"), _spec_out(S, (T, 2), x, "spec_prepare S")
+    L.check(lib().gd_spec_prepare(_ptr(x), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), L.SPEC_DETREND[detrend], _ptr(coef), _ptr(S),
+                                  _stream()), "gd_spec_prepare")
+    return coef, S
+
+
+def spec_power_ws_bytes(T: int, H: int, W: int, nbins: int) -> int:
+    return int(lib().gd_spec_power_ws_bytes(int(T), int(H), int(W), int(nbins)))
+
+
+def spec_cross_ws_bytes(T: int, H: int, W: int, nbins: int) -> int:
+    return int(lib().gd_spec_cross_ws_bytes(int(T), int(H), int(W), int(nbins)))
+
+
+def _spec_tables(x: Tensor, twid_h: Tensor, twid_w: Tensor, bins: Tensor, fn: str) -> int:
+    T, H, W = x.shape
+    _spec_vec(twid_h, 2 * H, fn + " twid_h")
+    _spec_vec(twid_w, 2 * W, fn + " twid_w")
+    _dense(bins, fn + " bins", torch.int32)
+    if tuple(bins.shape) != (H, W // 2 + 1):
+        raise L.GandanetError(f"{fn}: the bin table is ({H}, {W // 2 + 1}) int32, got {tuple(bins.shape)}")
+    return T
+
+
+def _spec_ws(ws: Optional[Tensor], nbytes: int, like: Tensor, fn: str) -> Tensor:
+    if ws is None:
+        ws = torch.empty(max(nbytes, 8), device=like.device, dtype=torch.uint8)
+    return _dense(ws, fn + " workspace", torch.uint8)
+
+
+def spec_power(x: Tensor, coef: Tensor, S: Tensor, twid_h: Tensor, twid_w: Tensor, bins: Tensor, nbins: int,
+               mask: Optional[Tensor] = None, wy: Optional[Tensor] = None, wx: Optional[Tensor] = None, power: Optional[Tensor] = None,
+               dropped: Optional[Tensor] = None, p2d: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(power (T, nbins), dropped (T)) fp64 of the fields of a dense fp32 / fp64 ``x`` (T, H, W) from the results of
+    ``spec_prepare`` and the device copies of the twiddle and bin tables; ``p2d`` (T, H, W // 2 + 1) fp64, when given,
+    receives the un-binned power.  Outputs and the uint8 workspace (spec_power_ws_bytes) are allocated unless given.  No
+    host sync."""
+    dt = _spec_cube(x, "spec_power input")
+    T, H, W = x.shape
+    _spec_tables(x, twid_h, twid_w, bins, "spec_power")
+    mask = _eval_mask(mask, H * W)
+    _spec_vec(wy, H, "spec_power wy")
+    _spec_vec(wx, W, "spec_power wx")
+    _spec_vec(coef, 3 * T, "spec_power coef")
+    _spec_vec(S, 2 * T, "spec_power S")
+    nbins = int(nbins)
+    power = _spec_out(power, (T, max(nbins, 0)), x, "spec_power power")
+    dropped = _spec_out(dropped, (T,), x, "spec_power dropped")
+    if p2d is not None:
+        _spec_out(p2d, (T, H, W // 2 + 1), x, "spec_power p2d")
+    ws = _spec_ws(ws, spec_power_ws_bytes(T, H, W, nbins), x, "spec_power")
+    L.check(lib().gd_spec_power(_ptr(x), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), _ptr(coef), _ptr(S), _ptr(twid_h), _ptr(twid_w),
+                                _ptr(bins), nbins, _ptr(power), _ptr(dropped), _ptr(p2d), _ptr(ws), ws.numel(), _stream()), "gd_spec_power")
+    return power, dropped
+
+
+def spec_cross(xa: Tensor, xb: Tensor, coef_a: Tensor, S_a: Tensor, coef_b: Tensor, S_b: Tensor, twid_h: Tensor, twid_w: Tensor,
+               bins: Tensor, nbins: int, mask: Optional[Tensor] = None, wy: Optional[Tensor] = None, wx: Optional[Tensor] = None,
+               out: Optional[Tensor] = None, dropped: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(out (4, T, nbins), dropped (T, 4)) fp64: the bin sums of P_aa, P_bb, co and quad of two dense cubes of one shape and
+    dtype.  No host sync."""
+    dt = _spec_cube(xa, "spec_cross input a")
+    if _spec_cube(xb, "spec_cross input b") != dt or xa.shape != xb.shape:
+        raise L.GandanetError(f"spec_cross: a {tuple(xa.shape)} {xa.dtype} vs b {tuple(xb.shape)} {xb.dtype}")
+    T, H, W = xa.shape
+    _spec_tables(xa, twid_h, twid_w, bins, "spec_cross")
+    mask = _eval_mask(mask, H * W)
+    _spec_vec(wy, H, "spec_cross wy")
+    _spec_vec(wx, W, "spec_cross wx")
+    for c, s in ((coef_a, S_a), (coef_b, S_b)):
+        _spec_vec(c, 3 * T, "spec_cross coef")
+        _spec_vec(s, 2 * T, "spec_cross S")
+    nbins = int(nbins)
+    out = _spec_out(out, (4, T, max(nbins, 0)), xa, "spec_cross out")
+    dropped = _spec_out(dropped, (T, 4), xa, "spec_cross dropped")
+    ws = _spec_ws(ws, spec_cross_ws_bytes(T, H, W, nbins), xa, "spec_cross")
+    L.check(lib().gd_spec_cross(_ptr(xa), _ptr(xb), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), _ptr(coef_a), _ptr(S_a), _ptr(coef_b),
+                                _ptr(S_b), _ptr(twid_h), _ptr(twid_w), _ptr(bins), nbins, _ptr(out), _ptr(dropped), _ptr(ws), ws.numel(),
+                                _stream()), "gd_spec_cross")
+    return out, dropped
+
+
+def _spec_host_args(x, mask, wy, wx, fn: str):
+    import numpy as np
+    x, dt = _host_f(x, fn)
+    if x.ndim != 3:
+        raise L.GandanetError(f"{fn}: expected a (T, H, W) array, got {x.shape}")
+    T, H, W = x.shape
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    wy = None if wy is None else np.ascontiguousarray(wy, dtype=np.float64).reshape(-1)
+    wx = None if wx is None else np.ascontiguousarray(wx, dtype=np.float64).reshape(-1)
+    if (mask is not None and mask.size != H * W) or (wy is not None and wy.size != H) or (wx is not None and wx.size != W):
+        raise L.GandanetError(f"{fn}: mask (H * W), wy (H) and wx (W) do not fit {x.shape}")
+    return x, dt, mask, wy, wx
+
+
+def spec_prepare_host(x, mask=None, wy=None, wx=None, detrend: str = "mean"):
+    """``spec_prepare`` on HOST arrays (plain C++ over the same arithmetic, no GPU): (coef (T, 3), S (T, 2))"""
+    import numpy as np
+    x, dt, mask, wy, wx = _spec_host_args(x, mask, wy, wx, "spec_prepare_host")
+    if detrend not in L.SPEC_DETREND:
+        raise L.GandanetError(f"spec_prepare_host: detrend is one of {sorted(L.SPEC_DETREND)}, got {detrend!r}")
+    T, H, W = x.shape
+    coef, S = np.empty((T, 3)), np.empty((T, 2))
+    L.check(lib().gd_spec_prepare_host(x.ctypes.data, dt, T, H, W, _np_ptr(mask), _np_ptr(wy), _np_ptr(wx), L.SPEC_DETREND[detrend],
+                                       coef.ctypes.data, S.ctypes.data), "gd_spec_prepare_host")
+    return coef, S
+
+
+def spec_power_host(x, coef, S, bins, nbins: int, mask=None, wy=None, wx=None, two_d: bool = False):
+    """``spec_power`` on HOST arrays: (power (T, nbins), dropped (T), p2d (T, H, W // 2 + 1) or None)"""
+    import numpy as np
+    x, dt, mask, wy, wx = _spec_host_args(x, mask, wy, wx, "spec_power_host")
+    T, H, W = x.shape
+    coef, S = np.ascontiguousarray(coef, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
+    bins = np.ascontiguousarray(bins, dtype=np.int32)
+    th, tw = spec_twiddle_host(H), spec_twiddle_host(W)
+    power, dropped = np.empty((T, nbins)), np.empty(T)
+    p2d = np.empty((T, H, W // 2 + 1)) if two_d else None
+    L.check(lib().gd_spec_power_host(x.ctypes.data, dt, T, H, W, _np_ptr(mask), _np_ptr(wy), _np_ptr(wx), coef.ctypes.data, S.ctypes.data,
+                                     th.ctypes.data, tw.ctypes.data, bins.ctypes.data, int(nbins), power.ctypes.data, dropped.ctypes.data,
+                                     _np_ptr(p2d)), "gd_spec_power_host")
+    return power, dropped, p2d
+
+
+def spec_cross_host(xa, xb, coef_a, S_a, coef_b, S_b, bins, nbins: int, mask=None, wy=None, wx=None):
+    """``spec_cross`` on HOST arrays: (out (4, T, nbins), dropped (T, 4))"""
+    import numpy as np
+    xa, dt, mask, wy, wx = _spec_host_args(xa, mask, wy, wx, "spec_cross_host")
+    xb, dtb = _host_f(xb, "spec_cross_host")
+    if dtb != dt or xb.shape != xa.shape:
+        raise L.GandanetError(f"spec_cross_host: a {xa.shape} {xa.dtype} vs b {xb.shape} {xb.dtype}")
+    T, H, W = xa.shape
+    ca, sa, cb, sb = (np.ascontiguousarray(v, dtype=np.float64) for v in (coef_a, S_a, coef_b, S_b))
+    bins = np.ascontiguousarray(bins, dtype=np.int32)
+    th, tw = spec_twiddle_host(H), spec_twiddle_host(W)
+    out, dropped = np.empty((4, T, nbins)), np.empty((T, 4))
+    L.check(lib().gd_spec_cross_host(xa.ctypes.data, xb.ctypes.data, dt, T, H, W, _np_ptr(mask), _np_ptr(wy), _np_ptr(wx), ca.ctypes.data,
+                                     sa.ctypes.data, cb.ctypes.data, sb.ctypes.data, th.ctypes.data, tw.ctypes.data, bins.ctypes.data,
+                                     int(nbins), out.ctypes.data, dropped.ctypes.data), "gd_spec_cross_host")
+    return out, dropped

@@ -1116,6 +1116,87 @@ int gd_eof_reconstruct(const double* eofs, const double* pcs, const double* mean
 int gd_eof_reconstruct_host(const double* eofs, const double* pcs, const double* mean, const unsigned char* valid,
                             const double* weight, long T, long M, int K, void* out, int out_dtype);
 
+/* ------------------------------------------------------------------------------------------
+ * Spatial spectra (spectra.hip, csrc/spectra_core.h): the radially binned spatial power spectrum of every field of a
+ * (T, H, W) cube, and the co- and quadrature spectra of two such cubes, by a 2-D DFT written as matrix products on
+ * v_mfma_f64_16x16x4_f64.  Storage fp32 (dtype 0) or fp64 (dtype 1), all arithmetic fp64.  No spectrum is stored (unless
+ * p2d is asked for), no N x N twiddle matrix, no atomics: the same input gives the same bits, and the result of field t
+ * depends on neither T nor the other fields.  The caller owns all memory, nothing waits for the device.  Every device
+ * entry has a host twin (`_host`, every pointer in HOST memory): plain O(H W (H + W)) loops over spectra_core.h, a
+ * separable two-stage sum over the same tables; twin and device differ in the order of their sums only.
+ *
+ * DEFINITIONS, for a field x (H, W); mask: NULL or H * W bytes shared by all fields; pixel (i, j) is VALID iff x is finite
+ * and its mask byte is nonzero.
+ *  1. detrend over the valid pixels: 0 none; 1 mean; 2 the least-squares plane.  With the centred coordinates
+ *     u = i - (H - 1) / 2, v = j - (W - 1) / 2 the three coefficients (a, b, c) describe a + b u + c v (a is the plane at
+ *     the field's centre; mean: b = c = 0; none: all 0).  A fit that does not determine a slope (one row, one column, a
+ *     line of pixels) leaves that slope 0.
+ *  2. taper: x'[i, j] = (x - (a + b u + c v)) * wy[i] * wx[j] for a valid pixel, exactly 0 for an invalid one.  wy (H) and
+ *     wx (W) doubles, NULL = all ones.
+ *  3. transform: Z[ky, kx] = sum_i sum_j x'[i, j] exp(-2 pi i (ky i / H + kx j / W)), ky = 0 .. H - 1, kx = 0 .. Kx - 1,
+ *     Kx = W / 2 + 1.  Hermitian weight of column kx: 1 for kx = 0 and for kx = W / 2 with W even, else 2.
+ *  4. normalise: P[ky, kx] = weight |Z|^2 / (H W S), S = sum over valid pixels of wy^2 wx^2.  PARSEVAL: the sum of P over
+ *     all (ky, kx) is sum x'^2 / S, the windowed variance of the valid pixels.
+ *  5. bin: an int32 table bin[ky * Kx + kx] in [-1, nbins), -1 = dropped.  power[b] is the sum of P over bin b; the power
+ *     of the dropped wavenumbers is returned apart, so Parseval stays checkable.
+ * A field with no valid pixel has S = 0, count 0, and NaN power.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_SPEC_MAX_H 1024
+#define GD_SPEC_MAX_W 2048
+#define GD_SPEC_MAX_BINS 1024
+/* tw: 2 N doubles, cos(2 pi r / N) for r = 0 .. N - 1, then sin.  The angle is reduced to k pi / 2 +- phi with
+ * 0 <= phi <= pi / 4 in integers, cos phi and sin phi are evaluated in extended precision and rounded once: every entry
+ * is within 1 ulp, and the entries at r = 0, N / 4, N / 2, 3 N / 4 are exactly 0 and +-1.  The kernels index the table by
+ * (i k) mod N in integer arithmetic.  1 <= N <= GD_SPEC_MAX_W. */
+int gd_spec_twiddle_host(long N, double* tw);
+/* The bin table.  With P = H dy and Q = W dx (the fp64 products), L = max(P, Q) and ky' = ky folded to (-H / 2, H / 2]:
+ *   k = hypot(ky' / P, kx / Q),   bin = floor(k L)   (uniform bins of width 1 / L),
+ * -1 when bin >= nbins, or when kmax > 0 and k > kmax (1 + 2^-40).  The comparison of (k L)^2 with the squared edges is
+ * made in integers whenever P / Q is a ratio of integers below 2^20 (equal domains, or dy = dx), else in extended
+ * precision (floor(sqrt(q)) in long double; exact unless q lies within 2^-63 of a squared edge).
+ * kcentre[b] = (b + 1/2) / L, count[b] = entries of the table equal to b.
+ * gd_spec_default_bins: floor(min(1 / (2 dy), 1 / (2 dx)) L) + 1, at most GD_SPEC_MAX_BINS (with kmax = that Nyquist
+ * wavenumber the bins run up to the smaller Nyquist wavenumber); 0 for bad arguments. */
+int gd_spec_default_bins(long H, long W, double dy, double dx);
+int gd_spec_bins_host(long H, long W, double dy, double dx, int nbins, double kmax, int* bin, double* kcentre, long* count);
+/* coef: 3 T doubles (a, b, c per field); S: 2 T doubles (S and the count of valid pixels per field).  One workgroup per
+ * field, every sum an ordered block reduction, the 3 x 3 solve (about the means) on the device; no host sync. */
+int gd_spec_prepare(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy, const double* wx,
+                    int detrend, double* coef, double* S, void* stream);
+int gd_spec_prepare_host(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy,
+                         const double* wx, int detrend, double* coef, double* S);
+/* power: T x nbins doubles; dropped: T doubles; p2d: NULL or T x H x Kx doubles, the un-binned P (for tests and 2-D plots).
+ * twid_h, twid_w: gd_spec_twiddle_host(H), (W) on the device; bin: the table above on the device.
+ * A workgroup of 4 waves owns one field and a tile of 8 kx = 16 real columns (Re, Im).  Stage 1, Y = x' [C_W | -S_W]:
+ * x' is built at the load and staged in LDS in chunks of 64 rows x 32 columns; the H x 16 result stays in LDS as fp64.
+ * Stage 2: per 16 ky two MFMAs per 4 rows of Y (cos and sin of the LDS copy of the H table) leave Re Z and Im Z in the
+ * accumulator; |Z|^2 is taken in registers, goes to an LDS tile of 64 ky x 8 kx, and thread t adds the entries whose bin
+ * is t (mod 256) in ascending (ky, kx) to its own registers.  One slab [nbins + 1] per workgroup goes to ws; a second
+ * launch adds the slabs of a field in ascending tile order and divides by H W S.  Rows and columns beyond H and W exist
+ * as zeros in LDS only; every global read is clamped.
+ * Refused: H or W < 1, H > GD_SPEC_MAX_H, W > GD_SPEC_MAX_W, T H W >= 2^31, nbins outside 1..GD_SPEC_MAX_BINS;
+ * gd_spec_power_ws_bytes (T * ceil(Kx / 8) * (nbins + 1) doubles, a function of the shape alone) is 0 for them. */
+size_t gd_spec_power_ws_bytes(long T, long H, long W, int nbins);
+int gd_spec_power(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy, const double* wx,
+                  const double* coef, const double* S, const double* twid_h, const double* twid_w, const int* bin, int nbins,
+                  double* power, double* dropped, double* p2d, void* ws, size_t ws_bytes, void* stream);
+int gd_spec_power_host(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy, const double* wx,
+                       const double* coef, const double* S, const double* twid_h, const double* twid_w, const int* bin, int nbins,
+                       double* power, double* dropped, double* p2d);
+/* Two cubes of one shape, each with its own coefficients and S.  out: 4 x T x nbins doubles -- the bin sums of P_aa, P_bb,
+ * weight Re(Z_a conj Z_b) / (H W sqrt(S_a S_b)) (co) and weight Im(Z_a conj Z_b) / (H W sqrt(S_a S_b)) (quad); dropped: T x 4
+ * doubles, the same four sums over the dropped wavenumbers.  For xa == xb quad is exactly 0 and P_aa == P_bb bit for bit.
+ * The kernel of gd_spec_power with tiles of 4 kx: the 16 real columns are (Re, Im) of a and of b.  NaN where either
+ * field has no valid pixel.  gd_spec_cross_ws_bytes: T * ceil(Kx / 4) * 4 * (nbins + 1) doubles. */
+size_t gd_spec_cross_ws_bytes(long T, long H, long W, int nbins);
+int gd_spec_cross(const void* xa, const void* xb, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy,
+                  const double* wx, const double* coef_a, const double* S_a, const double* coef_b, const double* S_b,
+                  const double* twid_h, const double* twid_w, const int* bin, int nbins, double* out, double* dropped, void* ws,
+                  size_t ws_bytes, void* stream);
+int gd_spec_cross_host(const void* xa, const void* xb, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy,
+                       const double* wx, const double* coef_a, const double* S_a, const double* coef_b, const double* S_b,
+                       const double* twid_h, const double* twid_w, const int* bin, int nbins, double* out, double* dropped);
+
 #ifdef __cplusplus
 }
 #endif
