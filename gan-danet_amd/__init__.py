@@ -31,6 +31,9 @@ from .eof import EOFResult, eof_analysis
 from . import spectra
 from .spectra import (CrossSpectrum, Spectrum, cross_spectrum, effective_resolution, power_spectrum,
                       spectral_ratio)
+from . import drought
+from .drought import (DSI_CLASSES, DroughtClimatology, DroughtEvents, climatology, compare_events, drought_area, drought_events,
+                      drought_index)
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

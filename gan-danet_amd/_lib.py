@@ -39,6 +39,10 @@ EOF_MAX_T, EOF_MAX_K = 256, 16   # GD_EOF_MAX_T, GD_EOF_MAX_K
 EOF_CHUNK, EOF_SPLIT_MIN, EOF_SPLIT_MAX = 32, 8, 256   # GD_EOF_CHUNK, GD_EOF_SPLIT_MIN, GD_EOF_SPLIT_MAX (csrc/eof_core.h)
 SPEC_MAX_H, SPEC_MAX_W, SPEC_MAX_BINS = 1024, 2048, 1024   # GD_SPEC_MAX_H, GD_SPEC_MAX_W, GD_SPEC_MAX_BINS
 SPEC_DETREND = {"none": 0, "mean": 1, "plane": 2}          # GD_SPEC_DETREND_* (csrc/spectra_core.h)
+DROUGHT_MAX_T, DROUGHT_MAX_PERIOD, DROUGHT_MAX_N = 2048, 366, 257   # GD_DROUGHT_MAX_T, GD_DROUGHT_MAX_PERIOD, GD_DROUGHT_MAX_N
+DROUGHT_ANOMALY, DROUGHT_STANDARDIZED = 0, 1   # GD_DROUGHT_ANOMALY, GD_DROUGHT_STANDARDIZED
+DROUGHT_EV_MAPS = ("n_valid", "n_dry", "n_events", "event_steps", "max_duration", "mean_duration", "max_severity", "total_severity",
+                   "peak", "longest_start", "worst_start", "last_run")   # GD_DROUGHT_EV_*: bit k of `which`
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -249,6 +253,16 @@ SIGNATURES = {
     "gd_spec_cross_ws_bytes": (_sz, [_l, _l, _l, _i]),
     "gd_spec_cross": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
     "gd_spec_cross_host": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
+    "gd_drought_clim": (_i, [_p, _i, _l, _l, _i, _i, _l, _l, _p, _p, _p]),
+    "gd_drought_clim_host": (_i, [_p, _i, _l, _l, _i, _i, _l, _l, _p, _p]),
+    "gd_drought_index": (_i, [_p, _i, _l, _l, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "gd_drought_index_host": (_i, [_p, _i, _l, _l, _p, _i, _i, _i, _i, _p, _p]),
+    "gd_drought_rank": (_i, [_p, _i, _l, _l, _i, _i, _l, _l, _p, _p, _i, _p, _p]),
+    "gd_drought_rank_host": (_i, [_p, _i, _l, _l, _i, _i, _l, _l, _p, _p, _i, _p]),
+    "gd_drought_events": (_i, [_p, _i, _l, _l, C.c_double, _i, _i, _p, _p, _p, _p]),
+    "gd_drought_events_host": (_i, [_p, _i, _l, _l, C.c_double, _i, _i, _p, _p, _p]),
+    "gd_drought_exceed": (_i, [_p, _i, _l, C.c_double, _p, _p]),
+    "gd_drought_exceed_host": (_i, [_p, _i, _l, C.c_double, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

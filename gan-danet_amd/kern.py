@@ -2503,3 +2503,169 @@ def spec_cross_host(xa, xb, coef_a, S_a, coef_b, S_b, bins, nbins: int, mask=Non
                                      sa.ctypes.data, cb.ctypes.data, sb.ctypes.data, th.ctypes.data, tw.ctypes.data, bins.ctypes.data,
                                      int(nbins), out.ctypes.data, dropped.ctypes.data), "gd_spec_cross_host")
     return out, dropped
+
+
+# ---- drought analysis (include/gandanet.h, "Drought analysis"; drought.hip) --------------------------------------------------
+def drought_which(maps) -> int:
+    """the ``which`` bit set of gd_drought_events for an iterable of map names (L.DROUGHT_EV_MAPS)"""
+    which = 0
+    for name in maps:
+        if name not in L.DROUGHT_EV_MAPS:
+            raise L.GandanetError(f"unknown drought event map {name!r}: expected one of {L.DROUGHT_EV_MAPS}")
+        which |= 1 << L.DROUGHT_EV_MAPS.index(name)
+    if which == 0:
+        raise L.GandanetError("no drought event map selected")
+    return which
+
+
+def _drought_out(out: Optional[Tensor], shape, like: Tensor, dtype, name: str) -> Tensor:
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=dtype)
+    _dense(out, name, dtype)
+    if tuple(out.shape) != tuple(shape):
+        raise L.GandanetError(f"{name}: expected a dense {tuple(shape)} tensor, got {tuple(out.shape)}")
+    return out
+
+
+def drought_clim(x: Tensor, period: int = 12, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask: Optional[Tensor] = None,
+                 out: Optional[Tensor] = None) -> Tensor:
+    """the (3, period, M) fp64 record (n, mean, M2 per slot) of the M series of a dense fp32 / fp64 ``x`` (T, M) over the
+    baseline steps [b0, b1); ``mask``: M uint8.  A new tensor unless ``out`` is given.  No host sync."""
+    dt = _series_2d(x, "drought_clim input")
+    T, M = x.shape
+    b1 = T if b1 is None else b1
+    out = _drought_out(out, (3, int(period), M), x, torch.float64, "drought climatology")
+    L.check(lib().gd_drought_clim(_ptr(x), dt, T, M, int(period), int(phase), int(b0), int(b1), _ptr(_eval_mask(mask, M)), _ptr(out),
+                                  _stream()), "gd_drought_clim")
+    return out
+
+
+def drought_index(x: Tensor, clim: Tensor, phase: int = 0, kind: int = L.DROUGHT_STANDARDIZED, ddof: int = 0,
+                  mask: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """the anomaly or standardised index of a dense fp32 / fp64 ``x`` (T, M) against ``clim`` (3, period, M) fp64, in the
+    dtype of ``x``"""
+    dt = _series_2d(x, "drought_index input")
+    T, M = x.shape
+    _dense(clim, "drought climatology", torch.float64)
+    if clim.dim() != 3 or clim.shape[0] != 3 or clim.shape[2] != M:
+        raise L.GandanetError(f"drought_index: the climatology is (3, period, {M}) float64, got {tuple(clim.shape)}")
+    out = _drought_out(out, (T, M), x, x.dtype, "drought index")
+    L.check(lib().gd_drought_index(_ptr(x), dt, T, M, _ptr(clim), clim.shape[1], int(phase), int(kind), int(ddof),
+                                   _ptr(_eval_mask(mask, M)), _ptr(out), _stream()), "gd_drought_index")
+    return out
+
+
+def drought_rank(x: Tensor, table: Tensor, period: int = 12, phase: int = 0, b0: int = 0, b1: Optional[int] = None,
+                 mask: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """the rank index of a dense fp32 / fp64 ``x`` (T, M) through ``table`` (nmax, nmax) or (nmax^2) fp64 on the device, in
+    the dtype of ``x``"""
+    dt = _series_2d(x, "drought_rank input")
+    T, M = x.shape
+    b1 = T if b1 is None else b1
+    _dense(table, "drought rank table", torch.float64)
+    nmax = math.isqrt(table.numel())
+    if nmax * nmax != table.numel() or nmax == 0:
+        raise L.GandanetError(f"drought_rank: the table holds nmax^2 doubles, got {table.numel()}")
+    out = _drought_out(out, (T, M), x, x.dtype, "drought rank index")
+    L.check(lib().gd_drought_rank(_ptr(x), dt, T, M, int(period), int(phase), int(b0), int(b1), _ptr(_eval_mask(mask, M)), _ptr(table),
+                                  nmax, _ptr(out), _stream()), "gd_drought_rank")
+    return out
+
+
+def drought_events(index: Tensor, threshold: float, min_duration: int = 3, maps=L.DROUGHT_EV_MAPS, mask: Optional[Tensor] = None,
+                   want_steps: bool = False, out: Optional[Tensor] = None, in_event: Optional[Tensor] = None):
+    """(maps (len(set(maps)), M) fp64 in the order of L.DROUGHT_EV_MAPS, in_event (T, M) uint8 or None) of a dense fp32 /
+    fp64 ``index`` (T, M)"""
+    dt = _series_2d(index, "drought_events input")
+    T, M = index.shape
+    which = drought_which(maps)
+    out = _drought_out(out, (bin(which).count("1"), M), index, torch.float64, "drought event maps")
+    if want_steps or in_event is not None:
+        in_event = _drought_out(in_event, (T, M), index, torch.uint8, "drought in_event")
+    L.check(lib().gd_drought_events(_ptr(index), dt, T, M, float(threshold), int(min_duration), which, _ptr(_eval_mask(mask, M)),
+                                    _ptr(out), _ptr(in_event), _stream()), "gd_drought_events")
+    return out, in_event
+
+
+def drought_exceed(index: Tensor, threshold: float, out: Optional[Tensor] = None) -> Tensor:
+    """1 where ``index`` <= ``threshold``, 0 where not, NaN where NaN, in the dtype of the dense fp32 / fp64 ``index``"""
+    dt = _filter_dtype(index, "drought_exceed input")
+    if index.numel() == 0:
+        raise L.GandanetError("drought_exceed: empty tensor")
+    out = _drought_out(out, index.shape, index, index.dtype, "drought indicator")
+    L.check(lib().gd_drought_exceed(_ptr(index), dt, index.numel(), float(threshold), _ptr(out), _stream()), "gd_drought_exceed")
+    return out
+
+
+def _drought_host_args(x, mask, fn: str):
+    import numpy as np
+    x, dt = _host_f(x, fn)
+    if x.ndim != 2:
+        raise L.GandanetError(f"{fn}: expected a (T, M) array, got {x.shape}")
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    if mask is not None and mask.size != x.shape[1]:
+        raise L.GandanetError(f"{fn}: {mask.size} mask entries for {x.shape[1]} series")
+    return x, dt, mask
+
+
+def drought_clim_host(x, period: int = 12, phase: int = 0, b0: int = 0, b1=None, mask=None):
+    """``drought_clim`` on HOST arrays (plain C++ loops over the same per-series code, no GPU): the (3, period, M) record"""
+    import numpy as np
+    x, dt, mask = _drought_host_args(x, mask, "drought_clim_host")
+    T, M = x.shape
+    out = np.empty((3, max(int(period), 0), M))
+    L.check(lib().gd_drought_clim_host(x.ctypes.data, dt, T, M, int(period), int(phase), int(b0), int(T if b1 is None else b1),
+                                       _np_ptr(mask), out.ctypes.data), "gd_drought_clim_host")
+    return out
+
+
+def drought_index_host(x, clim, phase: int = 0, kind: int = L.DROUGHT_STANDARDIZED, ddof: int = 0, mask=None):
+    """``drought_index`` on HOST arrays"""
+    import numpy as np
+    x, dt, mask = _drought_host_args(x, mask, "drought_index_host")
+    T, M = x.shape
+    clim = np.ascontiguousarray(clim, dtype=np.float64)
+    if clim.ndim != 3 or clim.shape[0] != 3 or clim.shape[2] != M:
+        raise L.GandanetError(f"drought_index_host: the climatology is (3, period, {M}), got {clim.shape}")
+    out = np.empty_like(x)
+    L.check(lib().gd_drought_index_host(x.ctypes.data, dt, T, M, clim.ctypes.data, clim.shape[1], int(phase), int(kind), int(ddof),
+                                        _np_ptr(mask), out.ctypes.data), "gd_drought_index_host")
+    return out
+
+
+def drought_rank_host(x, table, period: int = 12, phase: int = 0, b0: int = 0, b1=None, mask=None):
+    """``drought_rank`` on HOST arrays"""
+    import numpy as np
+    x, dt, mask = _drought_host_args(x, mask, "drought_rank_host")
+    T, M = x.shape
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+    nmax = math.isqrt(table.size)
+    if nmax * nmax != table.size or nmax == 0:
+        raise L.GandanetError(f"drought_rank_host: the table holds nmax^2 doubles, got {table.size}")
+    out = np.empty_like(x)
+    L.check(lib().gd_drought_rank_host(x.ctypes.data, dt, T, M, int(period), int(phase), int(b0), int(T if b1 is None else b1),
+                                       _np_ptr(mask), table.ctypes.data, nmax, out.ctypes.data), "gd_drought_rank_host")
+    return out
+
+
+def drought_events_host(index, threshold: float, min_duration: int = 3, maps=L.DROUGHT_EV_MAPS, mask=None, want_steps: bool = False):
+    """``drought_events`` on HOST arrays: (dict name -> (M) array, in_event (T, M) uint8 or None)"""
+    import numpy as np
+    x, dt, mask = _drought_host_args(index, mask, "drought_events_host")
+    T, M = x.shape
+    which = drought_which(maps)
+    names = [nm for nm in L.DROUGHT_EV_MAPS if which >> L.DROUGHT_EV_MAPS.index(nm) & 1]
+    out = np.empty((len(names), M))
+    steps = np.empty((T, M), dtype=np.uint8) if want_steps else None
+    L.check(lib().gd_drought_events_host(x.ctypes.data, dt, T, M, float(threshold), int(min_duration), which, _np_ptr(mask),
+                                         out.ctypes.data, _np_ptr(steps)), "gd_drought_events_host")
+    return dict(zip(names, out)), steps
+
+
+def drought_exceed_host(index, threshold: float):
+    """``drought_exceed`` on a HOST array"""
+    import numpy as np
+    x, dt = _host_f(index, "drought_exceed_host")
+    out = np.empty_like(x)
+    L.check(lib().gd_drought_exceed_host(x.ctypes.data, dt, x.size, float(threshold), out.ctypes.data), "gd_drought_exceed_host")
+    return out

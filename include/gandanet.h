@@ -1197,6 +1197,82 @@ int gd_spec_cross_host(const void* xa, const void* xb, int dtype, long T, long H
                        const double* wx, const double* coef_a, const double* S_a, const double* coef_b, const double* S_b,
                        const double* twid_h, const double* twid_w, const int* bin, int nbins, double* out, double* dropped);
 
+/* ------------------------------------------------------------------------------------------
+ * Drought analysis (drought.hip, csrc/drought_core.h): where, when, how long and how severe were the droughts of a TWSA
+ * cube -- the calendar climatology of every pixel, the water storage deficit (Thomas et al. 2014) and the standardised
+ * GRACE-DSI (Zhao et al. 2017) against it, a non-parametric rank index, the events of run theory with their maps, and the
+ * indicator cube whose zonal means (gd_zone_mean) are drought-area series.
+ * The layout is that of "Per-pixel time series": series m of a dense (T, M) array at x[t * M + m], storage fp32 (dtype 0)
+ * or fp64 (dtype 1), 1 <= T <= GD_DROUGHT_MAX_T, all arithmetic fp64 with every operation rounded on its own.  mask: NULL,
+ * or M bytes, 0 = leave the series out (NaN in its outputs, 0 in its counts).  One thread owns a series and walks it in
+ * time order; no LDS, no atomics, no workspace, nothing allocated; a series' result depends on the series and the
+ * parameters alone.  Every *_host twin takes the same arguments in HOST memory, makes no GPU call, runs the same
+ * per-series code (csrc/drought_core.h) and agrees bit for bit.  Every argument is checked before any launch.
+ *
+ * Calendar: step t belongs to slot s = (t + phase) mod period, 1 <= period <= GD_DROUGHT_MAX_PERIOD, 0 <= phase < period.
+ * Baseline: the steps [b0, b1), 0 <= b0 < b1 <= T.
+ *
+ * gd_drought_clim: clim (3, period, M) doubles -- n, mean, M2 (the sum of squared deviations from the mean) of slot s of
+ * series m at clim[(j * period + s) * M + m], j = 0, 1, 2 -- over the baseline steps of the slot that are not NaN, in time
+ * order, by the recurrence of gd_series_push: d = v - mean, mean += d * (1 / (n + 1)), M2 += d * d * (n * (1 / (n + 1))),
+ * d against the mean before the sample.  A slot without a sample has n = 0 and NaN mean and M2.  The slots are walked in
+ * an outer loop (t = first(s); t += period): three accumulators in registers, every baseline element read once.
+ *
+ * gd_drought_index: out (T, M) in the dtype of x, rounded once.  GD_DROUGHT_ANOMALY: x - mean_s.  GD_DROUGHT_STANDARDIZED:
+ * (x - mean_s) / sqrt(M2_s / (n_s - ddof)), ddof 0 or 1; NaN where n_s - ddof <= 0 or M2_s == 0.  A NaN sample or an empty
+ * slot gives NaN.
+ *
+ * gd_drought_rank: for the sample v = x[t] of slot s let B be the baseline samples of the slot that are not NaN, and v
+ * itself when t lies outside the baseline; n = |B|, k = 2 #{b in B: b < v} + #{b in B: b == v}, so the midrank of v in B is
+ * (k + 1) / 2 and 1 <= k <= 2 n - 1.  out[t] = table[(n - 1)^2 + (k - 1)] rounded to the dtype of x; NaN for a NaN sample.
+ * table: nmax^2 doubles built by the caller (a plotting position, or its normal quantile for an SPI-style index), nmax <=
+ * GD_DROUGHT_MAX_N; refused where ceil((b1 - b0) / period) + 1 > nmax.  Nothing transcendental runs on the device.  The
+ * O(n^2) comparisons of a slot are one thread's; the baseline samples are re-read from cache for every sample.
+ *
+ * gd_drought_events: a step is dry when v <= threshold (never for NaN, which ends a run).  An event is a maximal run of
+ * consecutive dry steps of length >= min_duration (>= 1); its severity is the sum of (threshold - v) over its steps in time
+ * order.  maps: the planes selected by the bits of `which` (bit k = map k below), in ascending k, map j of series m at
+ * maps[j * M + m]:
+ *   n_valid, n_dry: the steps that are not NaN / that are dry;  n_events;  event_steps: the steps inside events;
+ *   max_duration;  mean_duration = event_steps / n_events, NaN without events;
+ *   max_severity, total_severity (the events' severities added in time order), both 0 without events;
+ *   peak: the smallest v inside events, NaN without events;
+ *   longest_start, worst_start: the first step of the first longest event / of the first event of largest severity, -1
+ *   without events;  last_run: the length of the run still open at step T - 1, whatever min_duration is, 0 if none.
+ * A masked series has 0 in n_valid, n_dry, n_events, event_steps, max_duration and last_run and NaN elsewhere.
+ * in_event: NULL, or (T, M) bytes, all written: 1 on the steps of events, else 0 (a thread writes 0 as it goes and
+ * back-fills its own column when a run qualifies).
+ *
+ * gd_drought_exceed: out[i] = 1 where index[i] <= threshold, 0 where not, NaN where index[i] is NaN, n elements in the
+ * dtype of the input: the cube whose gd_zone_mean is the (weighted) share of a zone's valid pixels in drought.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_DROUGHT_MAX_T 2048
+#define GD_DROUGHT_MAX_PERIOD 366
+#define GD_DROUGHT_MAX_N 257
+enum { GD_DROUGHT_ANOMALY = 0, GD_DROUGHT_STANDARDIZED = 1 };
+enum { GD_DROUGHT_EV_N_VALID = 0, GD_DROUGHT_EV_N_DRY = 1, GD_DROUGHT_EV_N_EVENTS = 2, GD_DROUGHT_EV_EVENT_STEPS = 3,
+       GD_DROUGHT_EV_MAX_DURATION = 4, GD_DROUGHT_EV_MEAN_DURATION = 5, GD_DROUGHT_EV_MAX_SEVERITY = 6,
+       GD_DROUGHT_EV_TOTAL_SEVERITY = 7, GD_DROUGHT_EV_PEAK = 8, GD_DROUGHT_EV_LONGEST_START = 9,
+       GD_DROUGHT_EV_WORST_START = 10, GD_DROUGHT_EV_LAST_RUN = 11, GD_DROUGHT_EV_MAPS = 12 };
+int gd_drought_clim(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
+                    const unsigned char* mask, double* clim, void* stream);
+int gd_drought_clim_host(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
+                         const unsigned char* mask, double* clim);
+int gd_drought_index(const void* x, int dtype, long T, long M, const double* clim, int period, int phase, int kind, int ddof,
+                     const unsigned char* mask, void* out, void* stream);
+int gd_drought_index_host(const void* x, int dtype, long T, long M, const double* clim, int period, int phase, int kind,
+                          int ddof, const unsigned char* mask, void* out);
+int gd_drought_rank(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
+                    const unsigned char* mask, const double* table, int nmax, void* out, void* stream);
+int gd_drought_rank_host(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
+                         const unsigned char* mask, const double* table, int nmax, void* out);
+int gd_drought_events(const void* index, int dtype, long T, long M, double threshold, int min_duration, int which,
+                      const unsigned char* mask, double* maps, unsigned char* in_event, void* stream);
+int gd_drought_events_host(const void* index, int dtype, long T, long M, double threshold, int min_duration, int which,
+                           const unsigned char* mask, double* maps, unsigned char* in_event);
+int gd_drought_exceed(const void* index, int dtype, long n, double threshold, void* out, void* stream);
+int gd_drought_exceed_host(const void* index, int dtype, long n, double threshold, void* out);
+
 #ifdef __cplusplus
 }
 #endif
