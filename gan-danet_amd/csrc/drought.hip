@@ -8,7 +8,7 @@
 // series and the parameters.  No LDS, no atomics, no workspace.  The climatology, index and rank kernels take the slots in
 // an outer loop (t = first(s); t += period), which keeps a slot's accumulators, mean and deviation in registers; the rank
 // kernel re-reads the baseline samples of a slot once per sample of that slot (they come from cache).
-// From elem_util.h: gd_dtype_ok, gd_elem_aligned, gd_aligned, gd_stream_grid, GD_S.
+// From elem_util.h: gd_dtype_ok, gd_elem_aligned, gd_aligned, gd_stream_grid, gd_with_dtype, gd_for_items, GD_S.
 #include "elem_util.h"
 #include "drought_core.h"
 
@@ -16,104 +16,109 @@ namespace {
 
 constexpr int DR_THREADS = 256;
 
-template <typename T>
-__global__ __launch_bounds__(DR_THREADS) void drought_clim_kernel(const T* __restrict__ x, long M, int period, int phase, long b0, long b1,
-                                                                  const unsigned char* __restrict__ mask, double* __restrict__ rec) {
-    const long m = (long)blockIdx.x * DR_THREADS + threadIdx.x;
-    if (m >= M) return;
-    gd_drought_clim_one(x + m, M, period, phase, b0, b1, !mask || mask[m] != 0, rec + m);
-}
+// one Body per entry (gd_for_items): operator() is the per-series call of the device kernel and of the host twin alike
+template <typename T> struct ClimBody {
+    const T* x;
+    long M, b0, b1;
+    int period, phase;
+    const unsigned char* mask;
+    double* rec;
+    __host__ __device__ void operator()(long m) const {
+        gd_drought_clim_one(x + m, M, period, phase, b0, b1, !mask || mask[m] != 0, rec + m);
+    }
+};
 
-template <typename T>
-__global__ __launch_bounds__(DR_THREADS) void drought_index_kernel(const T* __restrict__ x, long Tn, long M, const double* __restrict__ rec,
-                                                                   int period, int phase, int kind, int ddof,
-                                                                   const unsigned char* __restrict__ mask, T* __restrict__ out) {
-    const long m = (long)blockIdx.x * DR_THREADS + threadIdx.x;
-    if (m >= M) return;
-    gd_drought_index_one(x + m, Tn, M, rec + m, period, phase, kind, ddof, !mask || mask[m] != 0, out + m);
-}
+template <typename T> struct IndexBody {
+    const T* x;
+    long Tn, M;
+    const double* rec;
+    int period, phase, kind, ddof;
+    const unsigned char* mask;
+    T* out;
+    __host__ __device__ void operator()(long m) const {
+        gd_drought_index_one(x + m, Tn, M, rec + m, period, phase, kind, ddof, !mask || mask[m] != 0, out + m);
+    }
+};
 
-template <typename T>
-__global__ __launch_bounds__(DR_THREADS) void drought_rank_kernel(const T* __restrict__ x, long Tn, long M, int period, int phase, long b0,
-                                                                  long b1, const unsigned char* __restrict__ mask,
-                                                                  const double* __restrict__ table, T* __restrict__ out) {
-    const long m = (long)blockIdx.x * DR_THREADS + threadIdx.x;
-    if (m >= M) return;
-    gd_drought_rank_one(x + m, Tn, M, period, phase, b0, b1, !mask || mask[m] != 0, table, out + m);
-}
+template <typename T> struct RankBody {
+    const T* x;
+    long Tn, M, b0, b1;
+    int period, phase;
+    const unsigned char* mask;
+    const double* table;
+    T* out;
+    __host__ __device__ void operator()(long m) const {
+        gd_drought_rank_one(x + m, Tn, M, period, phase, b0, b1, !mask || mask[m] != 0, table, out + m);
+    }
+};
 
-template <typename T>
-__global__ __launch_bounds__(DR_THREADS) void drought_events_kernel(const T* __restrict__ x, long Tn, long M, double threshold,
-                                                                    int min_duration, int which, const unsigned char* __restrict__ mask,
-                                                                    double* __restrict__ maps, unsigned char* __restrict__ in_event) {
-    const long m = (long)blockIdx.x * DR_THREADS + threadIdx.x;
-    if (m >= M) return;
-    double o[GD_DROUGHT_EV_MAPS];
-    gd_drought_events_one(x + m, Tn, M, threshold, min_duration, !mask || mask[m] != 0, o, in_event ? in_event + m : in_event);
-    gd_drought_events_put(o, which, M, maps + m);
-}
+template <typename T> struct EventsBody {
+    const T* x;
+    long Tn, M;
+    double threshold;
+    int min_duration, which;
+    const unsigned char* mask;
+    double* maps;
+    unsigned char* in_event;
+    __host__ __device__ void operator()(long m) const {
+        double o[GD_DROUGHT_EV_MAPS];
+        gd_drought_events_one(x + m, Tn, M, threshold, min_duration, !mask || mask[m] != 0, o, in_event ? in_event + m : in_event);
+        gd_drought_events_put(o, which, M, maps + m);
+    }
+};
 
+// exceed keeps a kernel of its own: the __restrict__ of kernel arguments lets the fp32 loop be unrolled with its loads ahead
+// of its stores, which a Body's members do not (12 instead of 25 VGPRs, and 14 % slower on the (181, 440, 900) cube)
 template <typename T>
 __global__ __launch_bounds__(DR_THREADS) void drought_exceed_kernel(const T* __restrict__ x, long n, double threshold, T* __restrict__ out) {
     for (long i = (long)blockIdx.x * DR_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * DR_THREADS)
         out[i] = gd_drought_exceed_one(x[i], threshold);
 }
 
-// one entry per (dtype, host or device): the host twins are the loops over m of the same per-series functions
-template <typename T>
-static void clim_go(bool host, const T* x, long M, int period, int phase, long b0, long b1, const unsigned char* mask, double* rec,
-                    hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m) gd_drought_clim_one(x + m, M, period, phase, b0, b1, !mask || mask[m] != 0, rec + m);
-        return;
-    }
-    hipLaunchKernelGGL(drought_clim_kernel<T>, dim3(gd_cdiv(M, DR_THREADS)), dim3(DR_THREADS), 0, st, x, M, period, phase, b0, b1, mask, rec);
+// one function per entry, called by the device entry (host = false) and by its host twin (host = true, st unused)
+void clim_run(bool host, hipStream_t st, const void* x, int dtype, long M, int period, int phase, long b0, long b1,
+              const unsigned char* mask, double* clim) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        gd_for_items<DR_THREADS>(host, M, st, ClimBody<T>{(const T*)x, M, b0, b1, period, phase, mask, clim});
+    });
 }
 
-template <typename T>
-static void index_go(bool host, const T* x, long Tn, long M, const double* rec, int period, int phase, int kind, int ddof,
-                     const unsigned char* mask, T* out, hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m)
-            gd_drought_index_one(x + m, Tn, M, rec + m, period, phase, kind, ddof, !mask || mask[m] != 0, out + m);
-        return;
-    }
-    hipLaunchKernelGGL(drought_index_kernel<T>, dim3(gd_cdiv(M, DR_THREADS)), dim3(DR_THREADS), 0, st, x, Tn, M, rec, period, phase, kind,
-                       ddof, mask, out);
+void index_run(bool host, hipStream_t st, const void* x, int dtype, long Tn, long M, const double* clim, int period, int phase, int kind,
+               int ddof, const unsigned char* mask, void* out) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        gd_for_items<DR_THREADS>(host, M, st, IndexBody<T>{(const T*)x, Tn, M, clim, period, phase, kind, ddof, mask, (T*)out});
+    });
 }
 
-template <typename T>
-static void rank_go(bool host, const T* x, long Tn, long M, int period, int phase, long b0, long b1, const unsigned char* mask,
-                    const double* table, T* out, hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m) gd_drought_rank_one(x + m, Tn, M, period, phase, b0, b1, !mask || mask[m] != 0, table, out + m);
-        return;
-    }
-    hipLaunchKernelGGL(drought_rank_kernel<T>, dim3(gd_cdiv(M, DR_THREADS)), dim3(DR_THREADS), 0, st, x, Tn, M, period, phase, b0, b1, mask,
-                       table, out);
+void rank_run(bool host, hipStream_t st, const void* x, int dtype, long Tn, long M, int period, int phase, long b0, long b1,
+              const unsigned char* mask, const double* table, void* out) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        gd_for_items<DR_THREADS>(host, M, st, RankBody<T>{(const T*)x, Tn, M, b0, b1, period, phase, mask, table, (T*)out});
+    });
 }
 
-template <typename T>
-static void events_go(bool host, const T* x, long Tn, long M, double threshold, int min_duration, int which, const unsigned char* mask,
-                      double* maps, unsigned char* in_event, hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m) {
-            double o[GD_DROUGHT_EV_MAPS];
-            gd_drought_events_one(x + m, Tn, M, threshold, min_duration, !mask || mask[m] != 0, o, in_event ? in_event + m : in_event);
-            gd_drought_events_put(o, which, M, maps + m);
+void events_run(bool host, hipStream_t st, const void* index, int dtype, long Tn, long M, double threshold, int min_duration, int which,
+                const unsigned char* mask, double* maps, unsigned char* in_event) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        gd_for_items<DR_THREADS>(host, M, st, EventsBody<T>{(const T*)index, Tn, M, threshold, min_duration, which, mask, maps, in_event});
+    });
+}
+
+void exceed_run(bool host, hipStream_t st, const void* index, int dtype, long n, double threshold, void* out) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        const T* x = (const T*)index;
+        T* o = (T*)out;
+        if (host) {
+            for (long i = 0; i < n; ++i) o[i] = gd_drought_exceed_one(x[i], threshold);
+            return;
         }
-        return;
-    }
-    hipLaunchKernelGGL(drought_events_kernel<T>, dim3(gd_cdiv(M, DR_THREADS)), dim3(DR_THREADS), 0, st, x, Tn, M, threshold, min_duration,
-                       which, mask, maps, in_event);
-}
-
-template <typename T> static void exceed_go(bool host, const T* x, long n, double threshold, T* out, hipStream_t st) {
-    if (host) {
-        for (long i = 0; i < n; ++i) out[i] = gd_drought_exceed_one(x[i], threshold);
-        return;
-    }
-    hipLaunchKernelGGL(drought_exceed_kernel<T>, dim3(gd_stream_grid(n, DR_THREADS, 1L << 16)), dim3(DR_THREADS), 0, st, x, n, threshold, out);
+        hipLaunchKernelGGL(drought_exceed_kernel<T>, dim3(gd_stream_grid(n, DR_THREADS, 1L << 16)), dim3(DR_THREADS), 0, st, x, n, threshold, o);
+    });
 }
 
 }  // namespace
@@ -140,8 +145,7 @@ template <typename T> static void exceed_go(bool host, const T* x, long n, doubl
 extern "C" int gd_drought_clim(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
                                const unsigned char* mask, double* clim, void* stream) {
     DROUGHT_CLIM_CHECKS("gd_drought_clim");
-    if (dtype == GD_FILTER_F64) clim_go(false, (const double*)x, M, period, phase, b0, b1, mask, clim, GD_S);
-    else clim_go(false, (const float*)x, M, period, phase, b0, b1, mask, clim, GD_S);
+    clim_run(false, GD_S, x, dtype, M, period, phase, b0, b1, mask, clim);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -149,8 +153,7 @@ extern "C" int gd_drought_clim(const void* x, int dtype, long T, long M, int per
 extern "C" int gd_drought_clim_host(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
                                     const unsigned char* mask, double* clim) {
     DROUGHT_CLIM_CHECKS("gd_drought_clim_host");
-    if (dtype == GD_FILTER_F64) clim_go(true, (const double*)x, M, period, phase, b0, b1, mask, clim, nullptr);
-    else clim_go(true, (const float*)x, M, period, phase, b0, b1, mask, clim, nullptr);
+    clim_run(true, nullptr, x, dtype, M, period, phase, b0, b1, mask, clim);
     return 0;
 }
 
@@ -165,8 +168,7 @@ extern "C" int gd_drought_clim_host(const void* x, int dtype, long T, long M, in
 extern "C" int gd_drought_index(const void* x, int dtype, long T, long M, const double* clim, int period, int phase, int kind, int ddof,
                                 const unsigned char* mask, void* out, void* stream) {
     DROUGHT_INDEX_CHECKS("gd_drought_index");
-    if (dtype == GD_FILTER_F64) index_go(false, (const double*)x, T, M, clim, period, phase, kind, ddof, mask, (double*)out, GD_S);
-    else index_go(false, (const float*)x, T, M, clim, period, phase, kind, ddof, mask, (float*)out, GD_S);
+    index_run(false, GD_S, x, dtype, T, M, clim, period, phase, kind, ddof, mask, out);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -174,8 +176,7 @@ extern "C" int gd_drought_index(const void* x, int dtype, long T, long M, const 
 extern "C" int gd_drought_index_host(const void* x, int dtype, long T, long M, const double* clim, int period, int phase, int kind,
                                      int ddof, const unsigned char* mask, void* out) {
     DROUGHT_INDEX_CHECKS("gd_drought_index_host");
-    if (dtype == GD_FILTER_F64) index_go(true, (const double*)x, T, M, clim, period, phase, kind, ddof, mask, (double*)out, nullptr);
-    else index_go(true, (const float*)x, T, M, clim, period, phase, kind, ddof, mask, (float*)out, nullptr);
+    index_run(true, nullptr, x, dtype, T, M, clim, period, phase, kind, ddof, mask, out);
     return 0;
 }
 
@@ -191,8 +192,7 @@ extern "C" int gd_drought_index_host(const void* x, int dtype, long T, long M, c
 extern "C" int gd_drought_rank(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
                                const unsigned char* mask, const double* table, int nmax, void* out, void* stream) {
     DROUGHT_RANK_CHECKS("gd_drought_rank");
-    if (dtype == GD_FILTER_F64) rank_go(false, (const double*)x, T, M, period, phase, b0, b1, mask, table, (double*)out, GD_S);
-    else rank_go(false, (const float*)x, T, M, period, phase, b0, b1, mask, table, (float*)out, GD_S);
+    rank_run(false, GD_S, x, dtype, T, M, period, phase, b0, b1, mask, table, out);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -200,8 +200,7 @@ extern "C" int gd_drought_rank(const void* x, int dtype, long T, long M, int per
 extern "C" int gd_drought_rank_host(const void* x, int dtype, long T, long M, int period, int phase, long b0, long b1,
                                     const unsigned char* mask, const double* table, int nmax, void* out) {
     DROUGHT_RANK_CHECKS("gd_drought_rank_host");
-    if (dtype == GD_FILTER_F64) rank_go(true, (const double*)x, T, M, period, phase, b0, b1, mask, table, (double*)out, nullptr);
-    else rank_go(true, (const float*)x, T, M, period, phase, b0, b1, mask, table, (float*)out, nullptr);
+    rank_run(true, nullptr, x, dtype, T, M, period, phase, b0, b1, mask, table, out);
     return 0;
 }
 
@@ -216,8 +215,7 @@ extern "C" int gd_drought_rank_host(const void* x, int dtype, long T, long M, in
 extern "C" int gd_drought_events(const void* index, int dtype, long T, long M, double threshold, int min_duration, int which,
                                  const unsigned char* mask, double* maps, unsigned char* in_event, void* stream) {
     DROUGHT_EVENTS_CHECKS("gd_drought_events");
-    if (dtype == GD_FILTER_F64) events_go(false, (const double*)index, T, M, threshold, min_duration, which, mask, maps, in_event, GD_S);
-    else events_go(false, (const float*)index, T, M, threshold, min_duration, which, mask, maps, in_event, GD_S);
+    events_run(false, GD_S, index, dtype, T, M, threshold, min_duration, which, mask, maps, in_event);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -225,8 +223,7 @@ extern "C" int gd_drought_events(const void* index, int dtype, long T, long M, d
 extern "C" int gd_drought_events_host(const void* index, int dtype, long T, long M, double threshold, int min_duration, int which,
                                       const unsigned char* mask, double* maps, unsigned char* in_event) {
     DROUGHT_EVENTS_CHECKS("gd_drought_events_host");
-    if (dtype == GD_FILTER_F64) events_go(true, (const double*)index, T, M, threshold, min_duration, which, mask, maps, in_event, nullptr);
-    else events_go(true, (const float*)index, T, M, threshold, min_duration, which, mask, maps, in_event, nullptr);
+    events_run(true, nullptr, index, dtype, T, M, threshold, min_duration, which, mask, maps, in_event);
     return 0;
 }
 
@@ -239,15 +236,13 @@ extern "C" int gd_drought_events_host(const void* index, int dtype, long T, long
 
 extern "C" int gd_drought_exceed(const void* index, int dtype, long n, double threshold, void* out, void* stream) {
     DROUGHT_EXCEED_CHECKS("gd_drought_exceed");
-    if (dtype == GD_FILTER_F64) exceed_go(false, (const double*)index, n, threshold, (double*)out, GD_S);
-    else exceed_go(false, (const float*)index, n, threshold, (float*)out, GD_S);
+    exceed_run(false, GD_S, index, dtype, n, threshold, out);
     GD_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int gd_drought_exceed_host(const void* index, int dtype, long n, double threshold, void* out) {
     DROUGHT_EXCEED_CHECKS("gd_drought_exceed_host");
-    if (dtype == GD_FILTER_F64) exceed_go(true, (const double*)index, n, threshold, (double*)out, nullptr);
-    else exceed_go(true, (const float*)index, n, threshold, (float*)out, nullptr);
+    exceed_run(true, nullptr, index, dtype, n, threshold, out);
     return 0;
 }

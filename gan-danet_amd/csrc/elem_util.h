@@ -1,6 +1,8 @@
-// Shared host and device plumbing of the analysis kernels (evalstats, gradguard, filters, spline, prepare, basins, stl):
-// the fp32 / fp64 dtype tag and its alignment checks, 16-byte vector access with a scalar head and tail, launch-grid
-// sizing, and the fixed-order fp64 reductions.  The training-path kernels do not include this file.
+// Shared host and device plumbing of the analysis kernels (evalstats, gradguard, filters, spline, prepare, basins, stl,
+// series, trend, ensverify, eof, spectra, drought): the fp32 / fp64 dtype tag, its alignment checks and its dispatch
+// (gd_with_dtype: stl, series, trend, ensverify, eof, spectra, drought), 16-byte vector access with a scalar head and tail, launch-grid
+// sizing, the one-thread-per-item launcher with its host twin (gd_for_items: series, eof, drought), and the fixed-order fp64
+// reductions.  The training-path kernels do not include this file.
 #pragma once
 #include "common.h"
 #include "../../include/gandanet.h"
@@ -10,6 +12,12 @@ static inline bool gd_dtype_ok(int d) { return d == GD_FILTER_F32 || d == GD_FIL
 static inline bool gd_aligned(const void* p, int bytes) { return ((uintptr_t)p % bytes) == 0; }
 static inline bool gd_elem_aligned(const void* p, int dtype) { return gd_aligned(p, dtype ? 8 : 4); }
 #define GD_S ((hipStream_t)stream)   // inside an entry point: its `void* stream` argument as the HIP stream
+
+// f(T{}) with T the element type of the tag (host only): gd_with_dtype(dtype, [&](auto zero) { using T = decltype(zero); ... })
+template <class F> static inline auto gd_with_dtype(int dtype, F&& f) {
+    if (dtype == GD_FILTER_F64) return f(double{});
+    return f(float{});
+}
 
 // elements of T from `p` up to the next 16-byte boundary (p is element aligned)
 template <typename T> __host__ __device__ inline long gd_head_of(const T* p) {
@@ -58,6 +66,28 @@ static inline int gd_plane_gx(long planes, long hw, int elems_per_block) {
     cap = cap < 1 ? 1 : cap;
     gx = gx > cap ? cap : gx;
     return (int)(gx < 1 ? 1 : (gx > 64 ? 64 : gx));
+}
+
+// ---- one thread per item --------------------------------------------------------------------------------------------------
+// body(i) for every i in [0, n): `Body` is a plain struct of an entry's arguments whose __host__ __device__ operator()(long)
+// holds the one per-item call, so the device kernel and the host twin (host = true: a loop on the calling thread, `st` is
+// not used) unpack the arguments in the same line.  CAP = 0: gd_cdiv(n, THREADS) workgroups, a thread per item; CAP > 0: a
+// grid-stride loop on gd_stream_grid(n, THREADS, CAP) workgroups.
+template <int THREADS, long CAP, class Body> __global__ __launch_bounds__(THREADS) void gd_item_kernel(long n, Body body) {
+    const long i0 = (long)blockIdx.x * THREADS + threadIdx.x;
+    if constexpr (CAP > 0) {
+        for (long i = i0; i < n; i += (long)gridDim.x * THREADS) body(i);
+    } else {
+        if (i0 < n) body(i0);
+    }
+}
+template <int THREADS, long CAP = 0, class Body> static inline void gd_for_items(bool host, long n, hipStream_t st, Body body) {
+    if (host) {
+        for (long i = 0; i < n; ++i) body(i);
+        return;
+    }
+    const int grid = CAP > 0 ? gd_stream_grid(n, THREADS, CAP) : gd_cdiv(n, THREADS);
+    hipLaunchKernelGGL((gd_item_kernel<THREADS, CAP, Body>), dim3(grid), dim3(THREADS), 0, st, n, body);
 }
 
 // ---- fp64 reductions in a fixed order ------------------------------------------------------------------------------------

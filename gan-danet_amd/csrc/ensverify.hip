@@ -238,8 +238,10 @@ extern "C" int gd_ens_verify(const void* x, int M, long member_stride, const voi
     }
     const GdEnsvGrid g = gd_ensv_grid(planes, hw);
     const int fair = (flags & GD_ENSV_FAIR) ? 1 : 0;
-    if (f64) ensv_launch<double>(x, M, member_stride, y, planes, hw, mask, scale, fair, crps_map, err_map, spread_map, rank_map, (double*)ws, g, GD_S);
-    else ensv_launch<float>(x, M, member_stride, y, planes, hw, mask, scale, fair, crps_map, err_map, spread_map, rank_map, (double*)ws, g, GD_S);
+    gd_with_dtype(f64 ? GD_FILTER_F64 : GD_FILTER_F32, [&](auto zero) {
+        ensv_launch<decltype(zero)>(x, M, member_stride, y, planes, hw, mask, scale, fair, crps_map, err_map, spread_map, rank_map, (double*)ws,
+                                    g, GD_S);
+    });
     hipLaunchKernelGGL(ens_verify_final_kernel, dim3(1), dim3(64), 0, GD_S, (const double*)ws, g.gx * g.gy, rec);
     GD_LAUNCH_CHECK();
     return 0;
@@ -254,12 +256,11 @@ extern "C" int gd_ens_verify_host(const void* x, int M, long member_stride, cons
         planes = 1;
     }
     const bool fair = (flags & GD_ENSV_FAIR) != 0;
-    if (f64)
-        ensv_host((const double*)x, M, member_stride, (const double*)y, planes, hw, mask, scale, fair, rec, (double*)crps_map,
-                  (double*)err_map, (double*)spread_map, rank_map);
-    else
-        ensv_host((const float*)x, M, member_stride, (const float*)y, planes, hw, mask, scale, fair, rec, (float*)crps_map, (float*)err_map,
-                  (float*)spread_map, rank_map);
+    gd_with_dtype(f64 ? GD_FILTER_F64 : GD_FILTER_F32, [&](auto zero) {
+        using E = decltype(zero);
+        ensv_host((const E*)x, M, member_stride, (const E*)y, planes, hw, mask, scale, fair, rec, (E*)crps_map, (E*)err_map, (E*)spread_map,
+                  rank_map);
+    });
     return 0;
 }
 

@@ -16,6 +16,7 @@
 // chunk's samples are loaded into registers ahead of the MFMAs of the current one.  A workgroup owns a contiguous run of
 // chunks (gd_eof_geom) and writes its accumulators as one slab [nblk][4][64]; a second launch adds the slabs in ascending
 // order and writes both triangles of G from the upper one.  No atomics; the geometry depends on (T, M) alone.
+#include <type_traits>
 #include <vector>
 
 #include "elem_util.h"
@@ -204,92 +205,82 @@ static void gram_host(const T* x, long Tn, long M, const double* mean, const uns
 }
 
 // ---- prepare -------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(EOF_THREADS) void eof_prepare_kernel(const T* __restrict__ x, long Tn, long M,
-                                                                  const unsigned char* __restrict__ mask,
-                                                                  const double* __restrict__ weight, int center, double* __restrict__ mean,
-                                                                  unsigned char* __restrict__ valid) {
-    const long m = (long)blockIdx.x * EOF_THREADS + threadIdx.x;
-    if (m >= M) return;
-    gd_eof_prepare_one(x + m, Tn, M, !mask || mask[m] != 0, weight != nullptr, weight ? weight[m] : 1.0, center, mean + m, valid + m);
-}
-
-template <typename T>
-static void prepare_go(bool host, const T* x, long Tn, long M, const unsigned char* mask, const double* weight, int center, double* mean,
-                       unsigned char* valid, hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m)
-            gd_eof_prepare_one(x + m, Tn, M, !mask || mask[m] != 0, weight != nullptr, weight ? weight[m] : 1.0, center, mean + m, valid + m);
-        return;
+// One Body per entry (gd_for_items): operator() is the per-series call of the device kernel and of the host twin alike.
+// Each *_run is called by the device entry (host = false) and by its host twin (host = true, st unused).
+template <typename T> struct PrepareBody {
+    const T* x;
+    long Tn, M;
+    const unsigned char* mask;
+    const double* weight;
+    int center;
+    double* mean;
+    unsigned char* valid;
+    __host__ __device__ void operator()(long m) const {
+        gd_eof_prepare_one(x + m, Tn, M, !mask || mask[m] != 0, weight != nullptr, weight ? weight[m] : 1.0, center, mean + m, valid + m);
     }
-    hipLaunchKernelGGL(eof_prepare_kernel<T>, dim3(gd_cdiv(M, EOF_THREADS)), dim3(EOF_THREADS), 0, st, x, Tn, M, mask, weight, center, mean,
-                       valid);
+};
+
+void prepare_run(bool host, hipStream_t st, const void* x, int dtype, long Tn, long M, const unsigned char* mask, const double* weight,
+                 int center, double* mean, unsigned char* valid) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        gd_for_items<EOF_THREADS>(host, M, st, PrepareBody<T>{(const T*)x, Tn, M, mask, weight, center, mean, valid});
+    });
 }
 
 // ---- project -------------------------------------------------------------------------------------------------------------
-template <typename T, int KC>
-__global__ __launch_bounds__(EOF_THREADS) void eof_project_kernel(const T* __restrict__ x, long Tn, long M, const double* __restrict__ mean,
-                                                                  const unsigned char* __restrict__ valid,
-                                                                  const double* __restrict__ weight, const double* __restrict__ coef, int K,
-                                                                  double* __restrict__ out) {
-    const long m = (long)blockIdx.x * EOF_THREADS + threadIdx.x;
-    if (m >= M) return;
-    gd_eof_project_one<T, KC>(x + m, Tn, M, mean[m], valid[m] != 0, weight ? sqrt(weight[m]) : 1.0, coef, K, out, m);
-}
-
-template <typename T, int KC>
-static void project_go(bool host, const T* x, long Tn, long M, const double* mean, const unsigned char* valid, const double* weight,
-                       const double* coef, int K, double* out, hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m)
-            gd_eof_project_one<T, KC>(x + m, Tn, M, mean[m], valid[m] != 0, weight ? sqrt(weight[m]) : 1.0, coef, K, out, m);
-        return;
-    }
-    hipLaunchKernelGGL((eof_project_kernel<T, KC>), dim3(gd_cdiv(M, EOF_THREADS)), dim3(EOF_THREADS), 0, st, x, Tn, M, mean, valid, weight,
-                       coef, K, out);
-}
-
-// K accumulators in registers: the instance with 1, 4 or 16 of them that holds K
-template <typename T>
-static void project_dispatch(bool host, const T* x, long Tn, long M, const double* mean, const unsigned char* valid, const double* weight,
-                             const double* coef, int K, double* out, hipStream_t st) {
-    if (K <= 1) project_go<T, 1>(host, x, Tn, M, mean, valid, weight, coef, K, out, st);
-    else if (K <= 4) project_go<T, 4>(host, x, Tn, M, mean, valid, weight, coef, K, out, st);
-    else project_go<T, 16>(host, x, Tn, M, mean, valid, weight, coef, K, out, st);
+// K accumulators in registers: f(KC) for the instance with KC = 1, 4 or 16 of them that holds K
+template <class F> void with_kc(int K, F&& f) {
+    if (K <= 1) f(std::integral_constant<int, 1>{});
+    else if (K <= 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 16>{});
     static_assert(GD_EOF_MAX_K == 16, "the widest instance holds GD_EOF_MAX_K");
 }
 
-// ---- reconstruct ---------------------------------------------------------------------------------------------------------
-template <typename O, int KC>
-__global__ __launch_bounds__(EOF_THREADS) void eof_reconstruct_kernel(const double* __restrict__ eofs, const double* __restrict__ pcs,
-                                                                      const double* __restrict__ mean,
-                                                                      const unsigned char* __restrict__ valid,
-                                                                      const double* __restrict__ weight, long Tn, long M, int K,
-                                                                      O* __restrict__ out) {
-    const long m = (long)blockIdx.x * EOF_THREADS + threadIdx.x;
-    if (m >= M) return;
-    gd_eof_reconstruct_one<O, KC>(eofs, pcs, mean[m], valid[m] != 0, weight != nullptr, weight ? sqrt(weight[m]) : 1.0, Tn, M, K, out, m);
-}
-
-template <typename O, int KC>
-static void reconstruct_go(bool host, const double* eofs, const double* pcs, const double* mean, const unsigned char* valid,
-                           const double* weight, long Tn, long M, int K, O* out, hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m)
-            gd_eof_reconstruct_one<O, KC>(eofs, pcs, mean[m], valid[m] != 0, weight != nullptr, weight ? sqrt(weight[m]) : 1.0, Tn, M, K, out,
-                                          m);
-        return;
+template <typename T, int KC> struct ProjectBody {
+    const T* x;
+    long Tn, M;
+    const double* mean;
+    const unsigned char* valid;
+    const double *weight, *coef;
+    int K;
+    double* out;
+    __host__ __device__ void operator()(long m) const {
+        gd_eof_project_one<T, KC>(x + m, Tn, M, mean[m], valid[m] != 0, weight ? sqrt(weight[m]) : 1.0, coef, K, out, m);
     }
-    hipLaunchKernelGGL((eof_reconstruct_kernel<O, KC>), dim3(gd_cdiv(M, EOF_THREADS)), dim3(EOF_THREADS), 0, st, eofs, pcs, mean, valid,
-                       weight, Tn, M, K, out);
+};
+
+void project_run(bool host, hipStream_t st, const void* x, int dtype, long Tn, long M, const double* mean, const unsigned char* valid,
+                 const double* weight, const double* coef, int K, double* out) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        with_kc(K, [&](auto kc) {
+            gd_for_items<EOF_THREADS>(host, M, st, ProjectBody<T, decltype(kc)::value>{(const T*)x, Tn, M, mean, valid, weight, coef, K, out});
+        });
+    });
 }
 
-template <typename O>
-static void reconstruct_dispatch(bool host, const double* eofs, const double* pcs, const double* mean, const unsigned char* valid,
-                                 const double* weight, long Tn, long M, int K, O* out, hipStream_t st) {
-    if (K <= 1) reconstruct_go<O, 1>(host, eofs, pcs, mean, valid, weight, Tn, M, K, out, st);
-    else if (K <= 4) reconstruct_go<O, 4>(host, eofs, pcs, mean, valid, weight, Tn, M, K, out, st);
-    else reconstruct_go<O, 16>(host, eofs, pcs, mean, valid, weight, Tn, M, K, out, st);
+// ---- reconstruct ---------------------------------------------------------------------------------------------------------
+template <typename O, int KC> struct ReconstructBody {
+    const double *eofs, *pcs, *mean;
+    const unsigned char* valid;
+    const double* weight;
+    long Tn, M;
+    int K;
+    O* out;
+    __host__ __device__ void operator()(long m) const {
+        gd_eof_reconstruct_one<O, KC>(eofs, pcs, mean[m], valid[m] != 0, weight != nullptr, weight ? sqrt(weight[m]) : 1.0, Tn, M, K, out, m);
+    }
+};
+
+void reconstruct_run(bool host, hipStream_t st, const double* eofs, const double* pcs, const double* mean, const unsigned char* valid,
+                     const double* weight, long Tn, long M, int K, void* out, int out_dtype) {
+    gd_with_dtype(out_dtype, [&](auto zero) {
+        using O = decltype(zero);
+        with_kc(K, [&](auto kc) {
+            gd_for_items<EOF_THREADS>(host, M, st, ReconstructBody<O, decltype(kc)::value>{eofs, pcs, mean, valid, weight, Tn, M, K, (O*)out});
+        });
+    });
 }
 
 }  // namespace
@@ -309,8 +300,7 @@ static void reconstruct_dispatch(bool host, const double* eofs, const double* pc
 extern "C" int gd_eof_prepare(const void* x, int dtype, long T, long M, const unsigned char* mask, const double* weight, int center,
                               double* mean, unsigned char* valid, void* stream) {
     EOF_PREPARE_CHECKS("gd_eof_prepare");
-    if (dtype == GD_FILTER_F64) prepare_go(false, (const double*)x, T, M, mask, weight, center, mean, valid, GD_S);
-    else prepare_go(false, (const float*)x, T, M, mask, weight, center, mean, valid, GD_S);
+    prepare_run(false, GD_S, x, dtype, T, M, mask, weight, center, mean, valid);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -318,8 +308,7 @@ extern "C" int gd_eof_prepare(const void* x, int dtype, long T, long M, const un
 extern "C" int gd_eof_prepare_host(const void* x, int dtype, long T, long M, const unsigned char* mask, const double* weight, int center,
                                    double* mean, unsigned char* valid) {
     EOF_PREPARE_CHECKS("gd_eof_prepare_host");
-    if (dtype == GD_FILTER_F64) prepare_go(true, (const double*)x, T, M, mask, weight, center, mean, valid, nullptr);
-    else prepare_go(true, (const float*)x, T, M, mask, weight, center, mean, valid, nullptr);
+    prepare_run(true, nullptr, x, dtype, T, M, mask, weight, center, mean, valid);
     return 0;
 }
 
@@ -341,8 +330,7 @@ extern "C" int gd_eof_gram(const void* x, int dtype, long T, long M, const doubl
     EOF_GRAM_CHECKS("gd_eof_gram");
     GD_CHECK_ARG(ws && gd_aligned(ws, 8) && ws_bytes >= gd_eof_gram_ws_bytes(T, M), "gd_eof_gram: workspace missing, misaligned or too small");
     const GdEofGeom g = gd_eof_geom(T, M);
-    if (dtype == GD_FILTER_F64) gram_dispatch((const double*)x, (int)T, M, mean, valid, weight, g, (double*)ws, GD_S);
-    else gram_dispatch((const float*)x, (int)T, M, mean, valid, weight, g, (double*)ws, GD_S);
+    gd_with_dtype(dtype, [&](auto zero) { gram_dispatch((const decltype(zero)*)x, (int)T, M, mean, valid, weight, g, (double*)ws, GD_S); });
     GD_LAUNCH_CHECK();
     hipLaunchKernelGGL(eof_gram_reduce_kernel, dim3(gd_cdiv((long)g.nblk * 256, 256)), dim3(256), 0, GD_S, (const double*)ws, g.splits, g.nb,
                        (int)T, G);
@@ -353,8 +341,7 @@ extern "C" int gd_eof_gram(const void* x, int dtype, long T, long M, const doubl
 extern "C" int gd_eof_gram_host(const void* x, int dtype, long T, long M, const double* mean, const unsigned char* valid,
                                 const double* weight, double* G) {
     EOF_GRAM_CHECKS("gd_eof_gram_host");
-    if (dtype == GD_FILTER_F64) gram_host((const double*)x, T, M, mean, valid, weight, G);
-    else gram_host((const float*)x, T, M, mean, valid, weight, G);
+    gd_with_dtype(dtype, [&](auto zero) { gram_host((const decltype(zero)*)x, T, M, mean, valid, weight, G); });
     return 0;
 }
 
@@ -370,9 +357,7 @@ extern "C" int gd_eof_gram_host(const void* x, int dtype, long T, long M, const 
 extern "C" int gd_eof_project(const void* x, int dtype, long T, long M, const double* mean, const unsigned char* valid,
                               const double* weight, int use_weight, const double* coef, int K, double* out, void* stream) {
     EOF_PROJECT_CHECKS("gd_eof_project");
-    const double* w = use_weight ? weight : nullptr;
-    if (dtype == GD_FILTER_F64) project_dispatch(false, (const double*)x, T, M, mean, valid, w, coef, K, out, GD_S);
-    else project_dispatch(false, (const float*)x, T, M, mean, valid, w, coef, K, out, GD_S);
+    project_run(false, GD_S, x, dtype, T, M, mean, valid, use_weight ? weight : nullptr, coef, K, out);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -380,9 +365,7 @@ extern "C" int gd_eof_project(const void* x, int dtype, long T, long M, const do
 extern "C" int gd_eof_project_host(const void* x, int dtype, long T, long M, const double* mean, const unsigned char* valid,
                                    const double* weight, int use_weight, const double* coef, int K, double* out) {
     EOF_PROJECT_CHECKS("gd_eof_project_host");
-    const double* w = use_weight ? weight : nullptr;
-    if (dtype == GD_FILTER_F64) project_dispatch(true, (const double*)x, T, M, mean, valid, w, coef, K, out, nullptr);
-    else project_dispatch(true, (const float*)x, T, M, mean, valid, w, coef, K, out, nullptr);
+    project_run(true, nullptr, x, dtype, T, M, mean, valid, use_weight ? weight : nullptr, coef, K, out);
     return 0;
 }
 
@@ -399,8 +382,7 @@ extern "C" int gd_eof_project_host(const void* x, int dtype, long T, long M, con
 extern "C" int gd_eof_reconstruct(const double* eofs, const double* pcs, const double* mean, const unsigned char* valid,
                                   const double* weight, long T, long M, int K, void* out, int out_dtype, void* stream) {
     EOF_RECONSTRUCT_CHECKS("gd_eof_reconstruct");
-    if (out_dtype == GD_FILTER_F64) reconstruct_dispatch(false, eofs, pcs, mean, valid, weight, T, M, K, (double*)out, GD_S);
-    else reconstruct_dispatch(false, eofs, pcs, mean, valid, weight, T, M, K, (float*)out, GD_S);
+    reconstruct_run(false, GD_S, eofs, pcs, mean, valid, weight, T, M, K, out, out_dtype);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -408,7 +390,6 @@ extern "C" int gd_eof_reconstruct(const double* eofs, const double* pcs, const d
 extern "C" int gd_eof_reconstruct_host(const double* eofs, const double* pcs, const double* mean, const unsigned char* valid,
                                        const double* weight, long T, long M, int K, void* out, int out_dtype) {
     EOF_RECONSTRUCT_CHECKS("gd_eof_reconstruct_host");
-    if (out_dtype == GD_FILTER_F64) reconstruct_dispatch(true, eofs, pcs, mean, valid, weight, T, M, K, (double*)out, nullptr);
-    else reconstruct_dispatch(true, eofs, pcs, mean, valid, weight, T, M, K, (float*)out, nullptr);
+    reconstruct_run(true, nullptr, eofs, pcs, mean, valid, weight, T, M, K, out, out_dtype);
     return 0;
 }

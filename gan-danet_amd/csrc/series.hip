@@ -7,7 +7,8 @@
 // walks t in ascending order: lanes read neighbouring columns of a row, so every time step is one coalesced row read, and
 // T is never split -- a series' result depends on nothing but the series.  No LDS, no atomics, no workspace.  The basis
 // rows of the fit are the same for every lane: they are read at a wave-uniform address and come through the scalar cache.
-// From elem_util.h: gd_dtype_ok, gd_elem_aligned, gd_aligned, gd_head_of, gd_vec16, gd_stream_grid, GD_S.
+// From elem_util.h: gd_dtype_ok, gd_elem_aligned, gd_aligned, gd_head_of, gd_vec16, gd_with_dtype, gd_for_items,
+// GD_S.
 #include "elem_util.h"
 #include "series_core.h"
 
@@ -115,11 +116,14 @@ __host__ __device__ inline void skill_one(const double* rec, long M, long m, int
     }
 }
 
-__global__ __launch_bounds__(SR_THREADS) void series_skill_kernel(const double* __restrict__ rec, long M, int ddof, int which,
-                                                                  double* __restrict__ out) {
-    const long m = (long)blockIdx.x * SR_THREADS + threadIdx.x;
-    if (m < M) skill_one(rec, M, m, ddof, which, out);
-}
+// One Body per entry (gd_for_items): operator() is the per-item call of the device kernel and of the host twin alike.
+struct SkillBody {
+    const double* rec;
+    long M;
+    int ddof, which;
+    double* out;
+    __host__ __device__ void operator()(long m) const { skill_one(rec, M, m, ddof, which, out); }
+};
 
 // ---- least squares -------------------------------------------------------------------------------------------------------
 template <typename T, int P> __host__ __device__ inline void lstsq_one(const T* __restrict__ x, long Tn, long M, long m,
@@ -146,42 +150,32 @@ template <typename T, int P> __host__ __device__ inline void lstsq_one(const T* 
     if (n_out) n_out[m] = s.n;
 }
 
-template <typename T, int P>
-__global__ __launch_bounds__(SR_THREADS) void series_lstsq_kernel(const T* __restrict__ x, long Tn, long M, const double* __restrict__ basis,
-                                                                  double* __restrict__ coef, double* __restrict__ rss,
-                                                                  double* __restrict__ n_out) {
-    const long m = (long)blockIdx.x * SR_THREADS + threadIdx.x;
-    if (m < M) lstsq_one<T, P>(x, Tn, M, m, basis, coef, rss, n_out);
-}
+template <typename T, int P> struct LstsqBody {
+    const T* x;
+    long Tn, M;
+    const double* basis;
+    double *coef, *rss, *n_out;
+    __host__ __device__ void operator()(long m) const { lstsq_one<T, P>(x, Tn, M, m, basis, coef, rss, n_out); }
+};
 
-template <typename T, int P>
-static void lstsq_go(bool host, const T* x, long Tn, long M, const double* basis, double* coef, double* rss, double* n_out, hipStream_t st) {
-    if (host) {
-        for (long m = 0; m < M; ++m) lstsq_one<T, P>(x, Tn, M, m, basis, coef, rss, n_out);
-        return;
-    }
-    hipLaunchKernelGGL((series_lstsq_kernel<T, P>), dim3(gd_cdiv(M, SR_THREADS)), dim3(SR_THREADS), 0, st, x, Tn, M, basis, coef, rss, n_out);
-}
-
-template <typename T>
-static void lstsq_dispatch(bool host, const T* x, long Tn, long M, const double* basis, int P, double* coef, double* rss, double* n_out,
-                           hipStream_t st) {
-    switch (P) {
-#define LSQ_CASE(p) case p: lstsq_go<T, p>(host, x, Tn, M, basis, coef, rss, n_out, st); break
-        LSQ_CASE(1); LSQ_CASE(2); LSQ_CASE(3); LSQ_CASE(4); LSQ_CASE(5); LSQ_CASE(6); LSQ_CASE(7); LSQ_CASE(8);
+// called by the device entry (host = false) and by its host twin (host = true, st unused)
+void lstsq_run(bool host, hipStream_t st, const void* x, int dtype, long Tn, long M, const double* basis, int P, double* coef, double* rss,
+               double* n_out) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        switch (P) {
+#define LSQ_CASE(p) case p: gd_for_items<SR_THREADS>(host, M, st, LstsqBody<T, p>{(const T*)x, Tn, M, basis, coef, rss, n_out}); break
+            LSQ_CASE(1); LSQ_CASE(2); LSQ_CASE(3); LSQ_CASE(4); LSQ_CASE(5); LSQ_CASE(6); LSQ_CASE(7); LSQ_CASE(8);
 #undef LSQ_CASE
-    }
+        }
+    });
     static_assert(GD_LSTSQ_MAX_P == 8, "one case per P");
 }
 
 // ---- amplitude, phase, slope, rms residual -------------------------------------------------------------------------------
-__global__ __launch_bounds__(SR_THREADS) void harmonic_finalize_kernel(const double* __restrict__ coef, long M, int K, int has_trend,
-                                                                       double tau_scale, const double* __restrict__ rss,
-                                                                       const double* __restrict__ n, double* __restrict__ amp,
-                                                                       double* __restrict__ phase, double* __restrict__ slope,
-                                                                       double* __restrict__ rms) {
-    const long m = (long)blockIdx.x * SR_THREADS + threadIdx.x;
-    if (m >= M) return;
+__host__ __device__ inline void harmonic_one(const double* __restrict__ coef, long M, long m, int K, int has_trend, double tau_scale,
+                                             const double* __restrict__ rss, const double* __restrict__ n, double* __restrict__ amp,
+                                             double* __restrict__ phase, double* __restrict__ slope, double* __restrict__ rms) {
     for (int k = 0; k < K; ++k) {
         const double c = coef[(1 + has_trend + 2 * k) * M + m], s = coef[(2 + has_trend + 2 * k) * M + m];
         if (amp) amp[k * M + m] = hypot(c, s);
@@ -191,15 +185,29 @@ __global__ __launch_bounds__(SR_THREADS) void harmonic_finalize_kernel(const dou
     if (rms) rms[m] = sqrt(rss[m] / n[m]);
 }
 
+struct HarmonicBody {
+    const double* coef;
+    long M;
+    int K, has_trend;
+    double tau_scale;
+    const double *rss, *n;
+    double *amp, *phase, *slope, *rms;
+    __host__ __device__ void operator()(long m) const { harmonic_one(coef, M, m, K, has_trend, tau_scale, rss, n, amp, phase, slope, rms); }
+};
+
 // ---- block mean ----------------------------------------------------------------------------------------------------------
 // one thread per output element, neighbouring threads neighbouring blocks of a row: a wave reads fx * 64 consecutive
 // elements of each of the fy rows
-template <typename T>
-__global__ __launch_bounds__(SR_THREADS) void block_mean_kernel(const T* __restrict__ x, long total, long H, long W, int fy, int fx,
-                                                                const double* __restrict__ weights, int min_count, T* __restrict__ out,
-                                                                int* __restrict__ count) {
-    const long Ho = H / fy, Wo = W / fx;
-    for (long i = (long)blockIdx.x * SR_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * SR_THREADS) {
+template <typename T> struct BlockMeanBody {
+    const T* x;
+    long H, W;
+    int fy, fx;
+    const double* weights;
+    int min_count;
+    T* out;
+    int* count;
+    __host__ __device__ void operator()(long i) const {
+        const long Ho = H / fy, Wo = W / fx;
         const long ox = i % Wo, oy = (i / Wo) % Ho, pl = i / (Wo * Ho);
         const long off = oy * fy * W + ox * fx;
         int cnt;
@@ -207,20 +215,14 @@ __global__ __launch_bounds__(SR_THREADS) void block_mean_kernel(const T* __restr
         out[i] = (T)v;
         if (count) count[i] = cnt;
     }
-}
+};
 
-template <typename T>
-static void block_mean_host(const T* x, long total, long H, long W, int fy, int fx, const double* weights, int min_count, T* out,
-                            int* count) {
-    const long Ho = H / fy, Wo = W / fx;
-    for (long i = 0; i < total; ++i) {
-        const long ox = i % Wo, oy = (i / Wo) % Ho, pl = i / (Wo * Ho);
-        const long off = oy * fy * W + ox * fx;
-        int cnt;
-        const double v = gd_block_mean_one(x + pl * H * W + off, weights ? weights + off : weights, W, fy, fx, min_count, &cnt);
-        out[i] = (T)v;
-        if (count) count[i] = cnt;
-    }
+void block_mean_run(bool host, hipStream_t st, const void* x, int dtype, long total, long H, long W, int fy, int fx, const double* weights,
+                    int min_count, void* out, int* count) {
+    gd_with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        gd_for_items<SR_THREADS, 1L << 20>(host, total, st, BlockMeanBody<T>{(const T*)x, H, W, fy, fx, weights, min_count, (T*)out, count});
+    });
 }
 
 }  // namespace
@@ -239,13 +241,11 @@ extern "C" int gd_series_stats(const void* pred, const void* truth, int dtype, l
                                double* rec, int accumulate, void* stream) {
     SERIES_STATS_CHECKS("gd_series_stats");
     const bool skip = (flags & GD_EVAL_SKIP_NAN) != 0;
-    if (dtype == GD_FILTER_F64) {
-        if (skip) series_stats_launch<double, true>((const double*)pred, (const double*)truth, T, M, mask, rec, accumulate, GD_S);
-        else series_stats_launch<double, false>((const double*)pred, (const double*)truth, T, M, mask, rec, accumulate, GD_S);
-    } else {
-        if (skip) series_stats_launch<float, true>((const float*)pred, (const float*)truth, T, M, mask, rec, accumulate, GD_S);
-        else series_stats_launch<float, false>((const float*)pred, (const float*)truth, T, M, mask, rec, accumulate, GD_S);
-    }
+    gd_with_dtype(dtype, [&](auto zero) {
+        using E = decltype(zero);
+        if (skip) series_stats_launch<E, true>((const E*)pred, (const E*)truth, T, M, mask, rec, accumulate, GD_S);
+        else series_stats_launch<E, false>((const E*)pred, (const E*)truth, T, M, mask, rec, accumulate, GD_S);
+    });
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -254,8 +254,10 @@ extern "C" int gd_series_stats_host(const void* pred, const void* truth, int dty
                                     int flags, double* rec, int accumulate) {
     SERIES_STATS_CHECKS("gd_series_stats_host");
     const bool skip = (flags & GD_EVAL_SKIP_NAN) != 0;
-    if (dtype == GD_FILTER_F64) series_stats_host((const double*)pred, (const double*)truth, T, M, mask, skip, rec, accumulate);
-    else series_stats_host((const float*)pred, (const float*)truth, T, M, mask, skip, rec, accumulate);
+    gd_with_dtype(dtype, [&](auto zero) {
+        using E = decltype(zero);
+        series_stats_host((const E*)pred, (const E*)truth, T, M, mask, skip, rec, accumulate);
+    });
     return 0;
 }
 
@@ -268,14 +270,14 @@ extern "C" int gd_series_stats_host(const void* pred, const void* truth, int dty
 
 extern "C" int gd_series_skill(const double* rec, long M, int ddof, int which, double* out, void* stream) {
     SERIES_SKILL_CHECKS("gd_series_skill");
-    hipLaunchKernelGGL(series_skill_kernel, dim3(gd_cdiv(M, SR_THREADS)), dim3(SR_THREADS), 0, GD_S, rec, M, ddof, which, out);
+    gd_for_items<SR_THREADS>(false, M, GD_S, SkillBody{rec, M, ddof, which, out});
     GD_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int gd_series_skill_host(const double* rec, long M, int ddof, int which, double* out) {
     SERIES_SKILL_CHECKS("gd_series_skill_host");
-    for (long m = 0; m < M; ++m) skill_one(rec, M, m, ddof, which, out);
+    gd_for_items<SR_THREADS>(true, M, nullptr, SkillBody{rec, M, ddof, which, out});
     return 0;
 }
 
@@ -292,8 +294,7 @@ extern "C" int gd_series_skill_host(const double* rec, long M, int ddof, int whi
 extern "C" int gd_series_lstsq(const void* x, int dtype, long T, long M, const double* basis, int P, double* coef, double* rss,
                                double* n_out, void* stream) {
     SERIES_LSTSQ_CHECKS("gd_series_lstsq");
-    if (dtype == GD_FILTER_F64) lstsq_dispatch(false, (const double*)x, T, M, basis, P, coef, rss, n_out, GD_S);
-    else lstsq_dispatch(false, (const float*)x, T, M, basis, P, coef, rss, n_out, GD_S);
+    lstsq_run(false, GD_S, x, dtype, T, M, basis, P, coef, rss, n_out);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -301,8 +302,7 @@ extern "C" int gd_series_lstsq(const void* x, int dtype, long T, long M, const d
 extern "C" int gd_series_lstsq_host(const void* x, int dtype, long T, long M, const double* basis, int P, double* coef, double* rss,
                                     double* n_out) {
     SERIES_LSTSQ_CHECKS("gd_series_lstsq_host");
-    if (dtype == GD_FILTER_F64) lstsq_dispatch(true, (const double*)x, T, M, basis, P, coef, rss, n_out, nullptr);
-    else lstsq_dispatch(true, (const float*)x, T, M, basis, P, coef, rss, n_out, nullptr);
+    lstsq_run(true, nullptr, x, dtype, T, M, basis, P, coef, rss, n_out);
     return 0;
 }
 
@@ -318,8 +318,7 @@ extern "C" int gd_harmonic_finalize(const double* coef, int P, long M, int K, in
     GD_CHECK_ARG(gd_aligned(coef, 8) && gd_aligned(rss, 8) && gd_aligned(n, 8) && gd_aligned(amp, 8) && gd_aligned(phase, 8) &&
                      gd_aligned(slope, 8) && gd_aligned(rms, 8),
                  "gd_harmonic_finalize: pointer not element aligned");
-    hipLaunchKernelGGL(harmonic_finalize_kernel, dim3(gd_cdiv(M, SR_THREADS)), dim3(SR_THREADS), 0, GD_S, coef, M, K, has_trend, tau_scale,
-                       rss, n, amp, phase, slope, rms);
+    gd_for_items<SR_THREADS>(false, M, GD_S, HarmonicBody{coef, M, K, has_trend, tau_scale, rss, n, amp, phase, slope, rms});
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -339,13 +338,7 @@ extern "C" int gd_harmonic_finalize(const double* coef, int P, long M, int K, in
 extern "C" int gd_block_mean(const void* x, int dtype, long planes, long H, long W, int fy, int fx, const double* weights,
                              int min_count, void* out, int* count, void* stream) {
     BLOCK_MEAN_CHECKS("gd_block_mean");
-    const dim3 grid(gd_stream_grid(total, SR_THREADS, 1L << 20)), blk(SR_THREADS);
-    if (dtype == GD_FILTER_F64)
-        hipLaunchKernelGGL(block_mean_kernel<double>, grid, blk, 0, GD_S, (const double*)x, total, H, W, fy, fx, weights, min_count,
-                           (double*)out, count);
-    else
-        hipLaunchKernelGGL(block_mean_kernel<float>, grid, blk, 0, GD_S, (const float*)x, total, H, W, fy, fx, weights, min_count,
-                           (float*)out, count);
+    block_mean_run(false, GD_S, x, dtype, total, H, W, fy, fx, weights, min_count, out, count);
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -353,7 +346,6 @@ extern "C" int gd_block_mean(const void* x, int dtype, long planes, long H, long
 extern "C" int gd_block_mean_host(const void* x, int dtype, long planes, long H, long W, int fy, int fx, const double* weights,
                                   int min_count, void* out, int* count) {
     BLOCK_MEAN_CHECKS("gd_block_mean_host");
-    if (dtype == GD_FILTER_F64) block_mean_host((const double*)x, total, H, W, fy, fx, weights, min_count, (double*)out, count);
-    else block_mean_host((const float*)x, total, H, W, fy, fx, weights, min_count, (float*)out, count);
+    block_mean_run(true, nullptr, x, dtype, total, H, W, fy, fx, weights, min_count, out, count);
     return 0;
 }

@@ -574,12 +574,11 @@ extern "C" int gd_spec_bins_host(long H, long W, double dy, double dx, int nbins
 extern "C" int gd_spec_prepare(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy,
                                const double* wx, int detrend, double* coef, double* S, void* stream) {
     SPEC_PREPARE_CHECKS("gd_spec_prepare");
-    if (dtype == GD_FILTER_F64)
-        hipLaunchKernelGGL(spec_prepare_kernel<double>, dim3((unsigned)T), dim3(SPEC_THREADS), 0, GD_S, (const double*)x, (int)H, (int)W, mask, wy,
-                           wx, detrend, coef, S);
-    else
-        hipLaunchKernelGGL(spec_prepare_kernel<float>, dim3((unsigned)T), dim3(SPEC_THREADS), 0, GD_S, (const float*)x, (int)H, (int)W, mask, wy,
-                           wx, detrend, coef, S);
+    gd_with_dtype(dtype, [&](auto zero) {
+        using E = decltype(zero);
+        hipLaunchKernelGGL(spec_prepare_kernel<E>, dim3((unsigned)T), dim3(SPEC_THREADS), 0, GD_S, (const E*)x, (int)H, (int)W, mask, wy, wx,
+                           detrend, coef, S);
+    });
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -587,8 +586,7 @@ extern "C" int gd_spec_prepare(const void* x, int dtype, long T, long H, long W,
 extern "C" int gd_spec_prepare_host(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* wy,
                                     const double* wx, int detrend, double* coef, double* S) {
     SPEC_PREPARE_CHECKS("gd_spec_prepare_host");
-    if (dtype == GD_FILTER_F64) prepare_host((const double*)x, T, (int)H, (int)W, mask, wy, wx, detrend, coef, S);
-    else prepare_host((const float*)x, T, (int)H, (int)W, mask, wy, wx, detrend, coef, S);
+    gd_with_dtype(dtype, [&](auto zero) { prepare_host((const decltype(zero)*)x, T, (int)H, (int)W, mask, wy, wx, detrend, coef, S); });
     return 0;
 }
 
@@ -618,9 +616,9 @@ extern "C" int gd_spec_power(const void* x, int dtype, long T, long H, long W, c
     GD_CHECK_ARG(ws && gd_aligned(ws, 8) && ws_bytes >= gd_spec_power_ws_bytes(T, H, W, nbins),
                  "gd_spec_power: workspace missing, misaligned or too small");
     const SpecField f{x, coef, S};
-    const int rc = dtype == GD_FILTER_F64
-                       ? dft_launch<double, 1>(f, f, (int)T, (int)H, (int)W, mask, wy, wx, twid_h, twid_w, bin, nbins, p2d, (double*)ws, GD_S)
-                       : dft_launch<float, 1>(f, f, (int)T, (int)H, (int)W, mask, wy, wx, twid_h, twid_w, bin, nbins, p2d, (double*)ws, GD_S);
+    const int rc = gd_with_dtype(dtype, [&](auto zero) {
+        return dft_launch<decltype(zero), 1>(f, f, (int)T, (int)H, (int)W, mask, wy, wx, twid_h, twid_w, bin, nbins, p2d, (double*)ws, GD_S);
+    });
     if (rc) return rc;
     GD_LAUNCH_CHECK();
     hipLaunchKernelGGL(spec_reduce_kernel<1>, dim3(gd_cdiv(T * (nbins + 1), 256)), dim3(256), 0, GD_S, (const double*)ws, (int)T,
@@ -633,9 +631,9 @@ extern "C" int gd_spec_power_host(const void* x, int dtype, long T, long H, long
                                   const double* wx, const double* coef, const double* S, const double* twid_h, const double* twid_w,
                                   const int* bin, int nbins, double* power, double* dropped, double* p2d) {
     SPEC_POWER_CHECKS("gd_spec_power_host");
-    if (dtype == GD_FILTER_F64)
-        power_host((const double*)x, T, (int)H, (int)W, mask, wy, wx, coef, S, twid_h, twid_w, bin, nbins, power, dropped, p2d);
-    else power_host((const float*)x, T, (int)H, (int)W, mask, wy, wx, coef, S, twid_h, twid_w, bin, nbins, power, dropped, p2d);
+    gd_with_dtype(dtype, [&](auto zero) {
+        power_host((const decltype(zero)*)x, T, (int)H, (int)W, mask, wy, wx, coef, S, twid_h, twid_w, bin, nbins, power, dropped, p2d);
+    });
     return 0;
 }
 
@@ -657,9 +655,9 @@ extern "C" int gd_spec_cross(const void* xa, const void* xb, int dtype, long T, 
     GD_CHECK_ARG(ws && gd_aligned(ws, 8) && ws_bytes >= gd_spec_cross_ws_bytes(T, H, W, nbins),
                  "gd_spec_cross: workspace missing, misaligned or too small");
     const SpecField fa{xa, coef_a, S_a}, fb{xb, coef_b, S_b};
-    const int rc = dtype == GD_FILTER_F64
-                       ? dft_launch<double, 2>(fa, fb, (int)T, (int)H, (int)W, mask, wy, wx, twid_h, twid_w, bin, nbins, nullptr, (double*)ws, GD_S)
-                       : dft_launch<float, 2>(fa, fb, (int)T, (int)H, (int)W, mask, wy, wx, twid_h, twid_w, bin, nbins, nullptr, (double*)ws, GD_S);
+    const int rc = gd_with_dtype(dtype, [&](auto zero) {
+        return dft_launch<decltype(zero), 2>(fa, fb, (int)T, (int)H, (int)W, mask, wy, wx, twid_h, twid_w, bin, nbins, nullptr, (double*)ws, GD_S);
+    });
     if (rc) return rc;
     GD_LAUNCH_CHECK();
     hipLaunchKernelGGL(spec_reduce_kernel<4>, dim3(gd_cdiv(T * 4 * (nbins + 1), 256)), dim3(256), 0, GD_S, (const double*)ws, (int)T,
@@ -673,11 +671,9 @@ extern "C" int gd_spec_cross_host(const void* xa, const void* xb, int dtype, lon
                                   const double* S_b, const double* twid_h, const double* twid_w, const int* bin, int nbins, double* out,
                                   double* dropped) {
     SPEC_CROSS_CHECKS("gd_spec_cross_host");
-    if (dtype == GD_FILTER_F64)
-        cross_host((const double*)xa, (const double*)xb, T, (int)H, (int)W, mask, wy, wx, coef_a, S_a, coef_b, S_b, twid_h, twid_w, bin, nbins,
-                   out, dropped);
-    else
-        cross_host((const float*)xa, (const float*)xb, T, (int)H, (int)W, mask, wy, wx, coef_a, S_a, coef_b, S_b, twid_h, twid_w, bin, nbins, out,
-                   dropped);
+    gd_with_dtype(dtype, [&](auto zero) {
+        using E = decltype(zero);
+        cross_host((const E*)xa, (const E*)xb, T, (int)H, (int)W, mask, wy, wx, coef_a, S_a, coef_b, S_b, twid_h, twid_w, bin, nbins, out, dropped);
+    });
     return 0;
 }

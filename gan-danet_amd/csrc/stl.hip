@@ -144,11 +144,10 @@ extern "C" int gd_stl_decompose(const void* x, int dtype, long T, long M, int pe
                                 void* seasonal_out, void* resid_out, void* weights_out, void* stream) {
     STL_CHECKS("gd_stl_decompose");
     static_assert(gd_stl_work_doubles(GD_STL_MAX_T, GD_STL_MAX_T / 2, 1) * 8 <= STL_LDS_MAX, "one series at the cap must fit the LDS");
-    if (dtype == GD_FILTER_F64)
-        return stl_launch((const double*)x, M, P, (double*)trend_out, (double*)seasonal_out, (double*)resid_out, (double*)weights_out,
-                          GD_S);
-    return stl_launch((const float*)x, M, P, (float*)trend_out, (float*)seasonal_out, (float*)resid_out, (float*)weights_out,
-                      GD_S);
+    return gd_with_dtype(dtype, [&](auto zero) {
+        using E = decltype(zero);
+        return stl_launch((const E*)x, M, P, (E*)trend_out, (E*)seasonal_out, (E*)resid_out, (E*)weights_out, GD_S);
+    });
 }
 
 // Host only, no GPU call: the same fit (stl_core.h) in plain loops, series after series, every pointer in HOST memory.
@@ -156,9 +155,9 @@ extern "C" int gd_stl_decompose_host(const void* x, int dtype, long T, long M, i
                                      int seasonal_deg, int trend_deg, int low_pass_deg, int inner_iter, int outer_iter, void* trend_out,
                                      void* seasonal_out, void* resid_out, void* weights_out) {
     STL_CHECKS("gd_stl_decompose_host");
-    if (dtype == GD_FILTER_F64)
-        stl_host((const double*)x, M, P, (double*)trend_out, (double*)seasonal_out, (double*)resid_out, (double*)weights_out);
-    else
-        stl_host((const float*)x, M, P, (float*)trend_out, (float*)seasonal_out, (float*)resid_out, (float*)weights_out);
+    gd_with_dtype(dtype, [&](auto zero) {
+        using E = decltype(zero);
+        stl_host((const E*)x, M, P, (E*)trend_out, (E*)seasonal_out, (E*)resid_out, (E*)weights_out);
+    });
     return 0;
 }

@@ -440,8 +440,7 @@ static void trend_host_one(const T* x, long Tn, long M, long m, const double* ti
 extern "C" int gd_trend_test(const void* x, int dtype, long T, long M, const double* times, int period, const unsigned char* mask,
                              int flags, double zq, double* out, void* stream) {
     TREND_CHECKS("gd_trend_test");
-    if (dtype == GD_FILTER_F64) trend_launch((const double*)x, T, M, times, period, mask, flags, zq, out, GD_S);
-    else trend_launch((const float*)x, T, M, times, period, mask, flags, zq, out, GD_S);
+    gd_with_dtype(dtype, [&](auto zero) { trend_launch((const decltype(zero)*)x, T, M, times, period, mask, flags, zq, out, GD_S); });
     GD_LAUNCH_CHECK();
     return 0;
 }
@@ -452,10 +451,11 @@ extern "C" int gd_trend_test_host(const void* x, int dtype, long T, long M, cons
     for (long k = 0; k < T; ++k)
         GD_CHECK_ARG(times[k] - times[k] == 0.0 && (k == 0 || times[k] > times[k - 1]),
                      "gd_trend_test_host: times are not finite and strictly increasing");
-    for (long m = 0; m < M; ++m) {
-        if (mask && mask[m] == 0) trend_put_empty(out, M, m, flags, 0);
-        else if (dtype == GD_FILTER_F64) trend_host_one((const double*)x, T, M, m, times, period, flags, zq, out);
-        else trend_host_one((const float*)x, T, M, m, times, period, flags, zq, out);
-    }
+    gd_with_dtype(dtype, [&](auto zero) {
+        for (long m = 0; m < M; ++m) {
+            if (mask && mask[m] == 0) trend_put_empty(out, M, m, flags, 0);
+            else trend_host_one((const decltype(zero)*)x, T, M, m, times, period, flags, zq, out);
+        }
+    });
     return 0;
 }

@@ -1788,6 +1788,66 @@ def zone_mean(x: Tensor, bits: Tensor, zones: int, weights: Optional[Tensor] = N
     return mean, count
 
 
+# ---- argument helpers of the analysis wrappers below (stl .. drought) ----------------------------------------------------------
+def _vec(t: Optional[Tensor], n: int, name: str, dtype=torch.float64) -> Optional[Tensor]:
+    """an optional dense device vector of ``n`` entries (any shape) of ``dtype``"""
+    if t is None:
+        return None
+    _dense(t, name, dtype)
+    if t.numel() != n:
+        raise L.GandanetError(f"{name}: expected {n} entries, got {tuple(t.shape)}")
+    return t
+
+
+def _out(out: Optional[Tensor], shape, like: Tensor, dtype, name: str) -> Tensor:
+    """the dense output of ``shape`` and ``dtype``: ``out`` when one is given, else a new tensor on the device of ``like``"""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=dtype)
+    _dense(out, name, dtype)
+    if tuple(out.shape) != tuple(shape):
+        raise L.GandanetError(f"{name}: expected a dense {tuple(shape)} {dtype} tensor, got {tuple(out.shape)}")
+    return out
+
+
+def _ws(ws: Optional[Tensor], nbytes: int, like: Tensor, name: str) -> Tensor:
+    """the dense uint8 workspace: ``ws`` when one is given (the C entry checks its size), else a new one of ``nbytes``"""
+    if ws is None:
+        ws = torch.empty(max(nbytes, 8), device=like.device, dtype=torch.uint8)
+    return _dense(ws, name + " workspace", torch.uint8)
+
+
+def _which(names, table, what: str) -> int:
+    """the ``which`` bit set of an iterable of map ``names`` out of ``table``"""
+    which = 0
+    for name in names:
+        if name not in table:
+            raise L.GandanetError(f"unknown {what} map {name!r}: expected one of {table}")
+        which |= 1 << table.index(name)
+    if which == 0:
+        raise L.GandanetError(f"no {what} map selected")
+    return which
+
+
+def _which_names(which: int, table) -> list:
+    """the names of ``table`` that the bit set ``which`` selects, in the order of ``table``"""
+    return [nm for k, nm in enumerate(table) if which >> k & 1]
+
+
+def _np_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _host_vec(a, n: Optional[int], name: str, dtype="float64"):
+    """an optional flat HOST vector: None, or a contiguous 1-D ``dtype`` array, of ``n`` entries where ``n`` is given"""
+    import numpy as np
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+    if n is not None and a.size != n:
+        raise L.GandanetError(f"{name}: expected {n} entries, got {a.size}")
+    return a
+
+
 # ---- STL decomposition (include/gandanet.h, "STL decomposition"; stl.hip) ------------------------------------------------------
 def _stl_args(p: dict):
     return [int(p[k]) for k in ("period", "seasonal", "trend", "low_pass", "seasonal_deg", "trend_deg", "low_pass_deg", "inner_iter",
@@ -1824,14 +1884,7 @@ def stl_decompose_host(x, p: dict):
 # ---- per-pixel time series (include/gandanet.h, "Per-pixel time series"; series.hip) -----------------------------------------
 def skill_which(metrics) -> int:
     """the ``which`` bit set of gd_series_skill for an iterable of map names (L.SKILL_MAPS)"""
-    which = 0
-    for name in metrics:
-        if name not in L.SKILL_MAPS:
-            raise L.GandanetError(f"unknown skill map {name!r}: expected one of {L.SKILL_MAPS}")
-        which |= 1 << L.SKILL_MAPS.index(name)
-    if which == 0:
-        raise L.GandanetError("no skill map selected")
-    return which
+    return _which(metrics, L.SKILL_MAPS, "skill")
 
 
 def _series_2d(x: Tensor, name: str) -> int:
@@ -1945,8 +1998,8 @@ def series_stats_host(pred, truth, mask=None, skip_nan: bool = True, rec=None):
     T, M = pred.shape
     acc = rec is not None
     rec = np.ascontiguousarray(rec, dtype=np.float64).copy() if acc else np.empty((8, M))
-    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-    L.check(lib().gd_series_stats_host(pred.ctypes.data, truth.ctypes.data, dt, T, M, None if mask is None else mask.ctypes.data,
+    mask = _host_vec(mask, None, "series_stats_host mask", "uint8")
+    L.check(lib().gd_series_stats_host(pred.ctypes.data, truth.ctypes.data, dt, T, M, _np_ptr(mask),
                                        L.EVAL_SKIP_NAN if skip_nan else 0, rec.ctypes.data, int(acc)), "gd_series_stats_host")
     return rec
 
@@ -1956,7 +2009,7 @@ def series_skill_host(rec, metrics, ddof: int = 0):
     import numpy as np
     rec = np.ascontiguousarray(rec, dtype=np.float64)
     which = skill_which(metrics)
-    names = [nm for nm in L.SKILL_MAPS if which >> L.SKILL_MAPS.index(nm) & 1]
+    names = _which_names(which, L.SKILL_MAPS)
     out = np.empty((len(names), rec.shape[1]))
     L.check(lib().gd_series_skill_host(rec.ctypes.data, rec.shape[1], int(ddof), which, out.ctypes.data), "gd_series_skill_host")
     return dict(zip(names, out))
@@ -1980,11 +2033,11 @@ def block_mean_host(x, fy: int, fx: int, weights=None, min_count: int = 1):
     import numpy as np
     x, dt = _host_f(x, "block_mean_host")
     H, W = x.shape[-2:]
-    weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    weights = _host_vec(weights, None, "block_mean_host weights")
     planes = math.prod(x.shape[:-2])
     shape = tuple(x.shape[:-2]) + (H // max(fy, 1), W // max(fx, 1))
     out, count = np.empty(shape, dtype=x.dtype), np.empty(shape, dtype=np.int32)
-    L.check(lib().gd_block_mean_host(x.ctypes.data, dt, planes, H, W, int(fy), int(fx), None if weights is None else weights.ctypes.data,
+    L.check(lib().gd_block_mean_host(x.ctypes.data, dt, planes, H, W, int(fy), int(fx), _np_ptr(weights),
                                      int(min_count), out.ctypes.data, count.ctypes.data), "gd_block_mean_host")
     return out, count
 
@@ -2005,11 +2058,7 @@ def trend_test(x: Tensor, times: Tensor, period: int = 0, mask: Optional[Tensor]
     _dense(times, "trend_test times", torch.float64)
     if times.dim() != 1 or times.shape[0] != T:
         raise L.GandanetError(f"trend_test: {tuple(times.shape)} times for {T} samples")
-    if out is None:
-        out = torch.empty((len(L.TREND_MAPS), M), device=x.device, dtype=torch.float64)
-    _dense(out, "trend_test output", torch.float64)
-    if tuple(out.shape) != (len(L.TREND_MAPS), M):
-        raise L.GandanetError(f"trend_test: the output is ({len(L.TREND_MAPS)}, {M}) float64, got {tuple(out.shape)}")
+    out = _out(out, (len(L.TREND_MAPS), M), x, torch.float64, "trend_test output")
     mask = _eval_mask(mask, M)
     L.check(lib().gd_trend_test(_ptr(x), dt, T, M, _ptr(times), int(period), _ptr(mask), int(flags), float(zq), _ptr(out), _stream()),
             "gd_trend_test")
@@ -2024,12 +2073,10 @@ def trend_test_host(x, times, period: int = 0, mask=None, flags: int = L.TREND_C
     if x.ndim != 2:
         raise L.GandanetError(f"trend_test_host: expected a (T, M) array, got {x.shape}")
     T, M = x.shape
-    times = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
-    if times.size != T:
-        raise L.GandanetError(f"trend_test_host: {times.size} times for {T} samples")
+    times = _host_vec(times, T, "trend_test_host times")
     out = np.empty((len(L.TREND_MAPS), M)) if out is None else out
-    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-    L.check(lib().gd_trend_test_host(x.ctypes.data, dt, T, M, times.ctypes.data, int(period), None if mask is None else mask.ctypes.data,
+    mask = _host_vec(mask, None, "trend_test_host mask", "uint8")
+    L.check(lib().gd_trend_test_host(x.ctypes.data, dt, T, M, _np_ptr(times), int(period), _np_ptr(mask),
                                      int(flags), float(zq), out.ctypes.data), "gd_trend_test_host")
     return out
 
@@ -2097,7 +2144,7 @@ def ens_verify_host(x, truth, mask=None, scale: float = 1.0, fair: bool = False,
     truth = np.ascontiguousarray(truth, dtype=x.dtype)
     if truth.size != n:
         raise L.GandanetError(f"ens_verify_host: members of {n} elements against a truth of {truth.size}")
-    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    mask = _host_vec(mask, None, "ens_verify_host mask", "uint8")
     hw = n if mask is None else mask.size
     if hw <= 0 or n % hw:
         raise L.GandanetError(f"ens_verify_host: a mask of {hw} entries does not tile {truth.shape}")
@@ -2107,7 +2154,7 @@ def ens_verify_host(x, truth, mask=None, scale: float = 1.0, fair: bool = False,
         out = {"crps": np.empty(truth.shape, x.dtype), "err": np.empty(truth.shape, x.dtype), "spread": np.empty(truth.shape, x.dtype),
                "rank": np.empty(truth.shape, np.uint8)}
     ptr = lambda k: out[k].ctypes.data if maps else None
-    L.check(lib().gd_ens_verify_host(x.ctypes.data, M, stride, truth.ctypes.data, n // hw, hw, None if mask is None else mask.ctypes.data,
+    L.check(lib().gd_ens_verify_host(x.ctypes.data, M, stride, truth.ctypes.data, n // hw, hw, _np_ptr(mask),
                                      float(scale), ens_verify_flags(x.dtype == np.float64, fair), rec.ctypes.data, ptr("crps"), ptr("err"),
                                      ptr("spread"), ptr("rank")), "gd_ens_verify_host")
     return rec, out
@@ -2133,24 +2180,15 @@ def ens_verify_merge_host(records, M: int) -> Tuple[list, dict]:
 
 
 # ---- EOF analysis (include/gandanet.h, "EOF analysis"; eof.hip) ---------------------------------------------------------------
-def _eof_vec(t: Optional[Tensor], M: int, name: str, dtype=torch.float64) -> Optional[Tensor]:
-    if t is None:
-        return None
-    _dense(t, name, dtype)
-    if t.numel() != M:
-        raise L.GandanetError(f"{name}: expected {M} entries (one per series), got {tuple(t.shape)}")
-    return t
-
-
 def eof_prepare(x: Tensor, mask: Optional[Tensor] = None, weight: Optional[Tensor] = None, center: bool = True,
                 mean: Optional[Tensor] = None, valid: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """(mean (M) fp64, valid (M) uint8) of the M series of a dense fp32 / fp64 ``x`` (T, M); ``mask``: M uint8; ``weight``:
     M fp64; ``mean`` and ``valid`` may be dense views to write into.  No host sync."""
     dt = _series_2d(x, "eof_prepare input")
     T, M = x.shape
-    mask, weight = _eval_mask(mask, M), _eof_vec(weight, M, "eof_prepare weight")
-    mean = torch.empty(M, device=x.device, dtype=torch.float64) if mean is None else _eof_vec(mean, M, "eof_prepare mean")
-    valid = torch.empty(M, device=x.device, dtype=torch.uint8) if valid is None else _eof_vec(valid, M, "eof_prepare valid", torch.uint8)
+    mask, weight = _eval_mask(mask, M), _vec(weight, M, "eof_prepare weight")
+    mean = torch.empty(M, device=x.device, dtype=torch.float64) if mean is None else _vec(mean, M, "eof_prepare mean")
+    valid = torch.empty(M, device=x.device, dtype=torch.uint8) if valid is None else _vec(valid, M, "eof_prepare valid", torch.uint8)
     L.check(lib().gd_eof_prepare(_ptr(x), dt, T, M, _ptr(mask), _ptr(weight), int(bool(center)), _ptr(mean), _ptr(valid), _stream()),
             "gd_eof_prepare")
     return mean, valid
@@ -2166,18 +2204,15 @@ def eof_gram(x: Tensor, mean: Tensor, valid: Tensor, weight: Optional[Tensor] = 
     ``out`` and the uint8 workspace ``ws`` (eof_gram_ws_bytes) are allocated unless given.  No host sync."""
     dt = _series_2d(x, "eof_gram input")
     T, M = x.shape
-    _eof_vec(mean, M, "eof_gram mean")
-    _eof_vec(valid, M, "eof_gram valid", torch.uint8)
-    _eof_vec(weight, M, "eof_gram weight")
+    _vec(mean, M, "eof_gram mean")
+    _vec(valid, M, "eof_gram valid", torch.uint8)
+    _vec(weight, M, "eof_gram weight")
     if out is None:
         out = torch.empty((T, T), device=x.device, dtype=torch.float64)
     _dense(out, "eof_gram output", torch.float64)
     if out.numel() != T * T:
         raise L.GandanetError(f"eof_gram: the output is ({T}, {T}) float64, got {tuple(out.shape)}")
-    nbytes = eof_gram_ws_bytes(T, M)
-    if ws is None:
-        ws = torch.empty(max(nbytes, 8), device=x.device, dtype=torch.uint8)
-    _dense(ws, "eof_gram workspace", torch.uint8)
+    ws = _ws(ws, eof_gram_ws_bytes(T, M), x, "eof_gram")
     L.check(lib().gd_eof_gram(_ptr(x), dt, T, M, _ptr(mean), _ptr(valid), _ptr(weight), _ptr(out), _ptr(ws), ws.numel(), _stream()),
             "gd_eof_gram")
     return out
@@ -2189,18 +2224,14 @@ def eof_project(x: Tensor, mean: Tensor, valid: Tensor, coef: Tensor, weight: Op
     1 <= K <= L.EOF_MAX_K; ``out`` may be a dense (K, M) view to write into.  No host sync."""
     dt = _series_2d(x, "eof_project input")
     T, M = x.shape
-    _eof_vec(mean, M, "eof_project mean")
-    _eof_vec(valid, M, "eof_project valid", torch.uint8)
-    _eof_vec(weight, M, "eof_project weight")
+    _vec(mean, M, "eof_project mean")
+    _vec(valid, M, "eof_project valid", torch.uint8)
+    _vec(weight, M, "eof_project weight")
     _dense(coef, "eof_project coefficients", torch.float64)
     if coef.dim() != 2 or coef.shape[0] != T or not 1 <= coef.shape[1] <= L.EOF_MAX_K:
         raise L.GandanetError(f"eof_project: the coefficients are ({T}, K) float64 with 1 <= K <= {L.EOF_MAX_K}, got {tuple(coef.shape)}")
     K = coef.shape[1]
-    if out is None:
-        out = torch.empty((K, M), device=x.device, dtype=torch.float64)
-    _dense(out, "eof_project output", torch.float64)
-    if tuple(out.shape) != (K, M):
-        raise L.GandanetError(f"eof_project: the output is ({K}, {M}) float64, got {tuple(out.shape)}")
+    out = _out(out, (K, M), x, torch.float64, "eof_project output")
     L.check(lib().gd_eof_project(_ptr(x), dt, T, M, _ptr(mean), _ptr(valid), _ptr(weight), int(bool(use_weight)), _ptr(coef), K, _ptr(out),
                                  _stream()), "gd_eof_project")
     return out
@@ -2219,35 +2250,21 @@ def eof_reconstruct(eofs: Tensor, pcs: Tensor, mean: Tensor, valid: Tensor, weig
     if dtype not in (torch.float32, torch.float64):
         raise L.GandanetError(f"eof_reconstruct: the output is float32 or float64, got {dtype}")
     (K, M), T = eofs.shape, pcs.shape[0]
-    _eof_vec(mean, M, "eof_reconstruct mean")
-    _eof_vec(valid, M, "eof_reconstruct valid", torch.uint8)
-    _eof_vec(weight, M, "eof_reconstruct weight")
-    if out is None:
-        out = torch.empty((T, M), device=eofs.device, dtype=dtype)
-    _dense(out, "eof_reconstruct output", dtype)
-    if tuple(out.shape) != (T, M):
-        raise L.GandanetError(f"eof_reconstruct: the output is ({T}, {M}) {dtype}, got {tuple(out.shape)}")
+    _vec(mean, M, "eof_reconstruct mean")
+    _vec(valid, M, "eof_reconstruct valid", torch.uint8)
+    _vec(weight, M, "eof_reconstruct weight")
+    out = _out(out, (T, M), eofs, dtype, "eof_reconstruct output")
     L.check(lib().gd_eof_reconstruct(_ptr(eofs), _ptr(pcs), _ptr(mean), _ptr(valid), _ptr(weight), T, M, K, _ptr(out),
                                      int(dtype == torch.float64), _stream()), "gd_eof_reconstruct")
     return out
 
 
-def _np_ptr(a):
-    return None if a is None else a.ctypes.data
-
-
 def _eof_host_args(x, mean, valid, weight, fn: str):
-    import numpy as np
     x, dt = _host_f(x, fn)
     if x.ndim != 2:
         raise L.GandanetError(f"{fn}: expected a (T, M) array, got {x.shape}")
     M = x.shape[1]
-    mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
-    valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
-    weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
-    if mean.size != M or valid.size != M or (weight is not None and weight.size != M):
-        raise L.GandanetError(f"{fn}: mean, valid and weight hold one entry per series ({M})")
-    return x, dt, mean, valid, weight
+    return x, dt, _host_vec(mean, M, fn + " mean"), _host_vec(valid, M, fn + " valid", "uint8"), _host_vec(weight, M, fn + " weight")
 
 
 def eof_prepare_host(x, mask=None, weight=None, center: bool = True):
@@ -2255,8 +2272,7 @@ def eof_prepare_host(x, mask=None, weight=None, center: bool = True):
     import numpy as np
     x, dt = _host_f(x, "eof_prepare_host")
     T, M = x.shape
-    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
-    weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+    mask, weight = _host_vec(mask, None, "eof_prepare_host mask", "uint8"), _host_vec(weight, None, "eof_prepare_host weight")
     mean, valid = np.empty(M), np.empty(M, dtype=np.uint8)
     L.check(lib().gd_eof_prepare_host(x.ctypes.data, dt, T, M, _np_ptr(mask), _np_ptr(weight), int(bool(center)), mean.ctypes.data,
                                       valid.ctypes.data), "gd_eof_prepare_host")
@@ -2292,9 +2308,8 @@ def eof_reconstruct_host(eofs, pcs, mean, valid, weight=None, dtype="float64"):
     import numpy as np
     eofs, pcs = np.ascontiguousarray(eofs, dtype=np.float64), np.ascontiguousarray(pcs, dtype=np.float64)
     (K, M), T = eofs.shape, pcs.shape[0]
-    mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
-    valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
-    weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+    mean, valid = _host_vec(mean, None, "eof_reconstruct_host mean"), _host_vec(valid, None, "eof_reconstruct_host valid", "uint8")
+    weight = _host_vec(weight, None, "eof_reconstruct_host weight")
     out = np.empty((T, M), dtype=np.dtype(dtype))
     L.check(lib().gd_eof_reconstruct_host(eofs.ctypes.data, pcs.ctypes.data, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), T, M, K,
                                           out.ctypes.data, int(out.dtype == np.float64)), "gd_eof_reconstruct_host")
@@ -2332,24 +2347,6 @@ def _spec_cube(x: Tensor, name: str) -> int:
     return dt
 
 
-def _spec_vec(t: Optional[Tensor], n: int, name: str, dtype=torch.float64) -> Optional[Tensor]:
-    if t is None:
-        return None
-    _dense(t, name, dtype)
-    if t.numel() != n:
-        raise L.GandanetError(f"{name}: expected {n} entries, got {tuple(t.shape)}")
-    return t
-
-
-def _spec_out(t: Optional[Tensor], shape, like: Tensor, name: str) -> Tensor:
-    if t is None:
-        return torch.empty(shape, device=like.device, dtype=torch.float64)
-    _dense(t, name, torch.float64)
-    if tuple(t.shape) != tuple(shape):
-        raise L.GandanetError(f"{name}: expected {tuple(shape)} float64, got {tuple(t.shape)}")
-    return t
-
-
 def spec_prepare(x: Tensor, mask: Optional[Tensor] = None, wy: Optional[Tensor] = None, wx: Optional[Tensor] = None,
                  detrend: str = "mean", coef: Optional[Tensor] = None, S: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """(coef (T, 3), S (T, 2)) fp64 of the fields of a dense fp32 / fp64 ``x`` (T, H, W): the detrend coefficients
@@ -2360,9 +2357,9 @@ def spec_prepare(x: Tensor, mask: Optional[Tensor] = None, wy: Optional[Tensor] 
         raise L.GandanetError(f"spec_prepare: detrend is one of {sorted(L.SPEC_DETREND)}, got {detrend!r}")
     T, H, W = x.shape
     mask = _eval_mask(mask, H * W)
-    _spec_vec(wy, H, "spec_prepare wy")
-    _spec_vec(wx, W, "spec_prepare wx")
-    coef, S = _spec_out(coef, (T, 3), x, "spec_prepare coef"), _spec_out(S, (T, 2), x, "spec_prepare S")
+    _vec(wy, H, "spec_prepare wy")
+    _vec(wx, W, "spec_prepare wx")
+    coef, S = _out(coef, (T, 3), x, torch.float64, "spec_prepare coef"), _out(S, (T, 2), x, torch.float64, "spec_prepare S")
     L.check(lib().gd_spec_prepare(_ptr(x), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), L.SPEC_DETREND[detrend], _ptr(coef), _ptr(S),
                                   _stream()), "gd_spec_prepare")
     return coef, S
@@ -2378,18 +2375,12 @@ def spec_cross_ws_bytes(T: int, H: int, W: int, nbins: int) -> int:
 
 def _spec_tables(x: Tensor, twid_h: Tensor, twid_w: Tensor, bins: Tensor, fn: str) -> int:
     T, H, W = x.shape
-    _spec_vec(twid_h, 2 * H, fn + " twid_h")
-    _spec_vec(twid_w, 2 * W, fn + " twid_w")
+    _vec(twid_h, 2 * H, fn + " twid_h")
+    _vec(twid_w, 2 * W, fn + " twid_w")
     _dense(bins, fn + " bins", torch.int32)
     if tuple(bins.shape) != (H, W // 2 + 1):
         raise L.GandanetError(f"{fn}: the bin table is ({H}, {W // 2 + 1}) int32, got {tuple(bins.shape)}")
     return T
-
-
-def _spec_ws(ws: Optional[Tensor], nbytes: int, like: Tensor, fn: str) -> Tensor:
-    if ws is None:
-        ws = torch.empty(max(nbytes, 8), device=like.device, dtype=torch.uint8)
-    return _dense(ws, fn + " workspace", torch.uint8)
 
 
 def spec_power(x: Tensor, coef: Tensor, S: Tensor, twid_h: Tensor, twid_w: Tensor, bins: Tensor, nbins: int,
@@ -2403,16 +2394,16 @@ def spec_power(x: Tensor, coef: Tensor, S: Tensor, twid_h: Tensor, twid_w: Tenso
     T, H, W = x.shape
     _spec_tables(x, twid_h, twid_w, bins, "spec_power")
     mask = _eval_mask(mask, H * W)
-    _spec_vec(wy, H, "spec_power wy")
-    _spec_vec(wx, W, "spec_power wx")
-    _spec_vec(coef, 3 * T, "spec_power coef")
-    _spec_vec(S, 2 * T, "spec_power S")
+    _vec(wy, H, "spec_power wy")
+    _vec(wx, W, "spec_power wx")
+    _vec(coef, 3 * T, "spec_power coef")
+    _vec(S, 2 * T, "spec_power S")
     nbins = int(nbins)
-    power = _spec_out(power, (T, max(nbins, 0)), x, "spec_power power")
-    dropped = _spec_out(dropped, (T,), x, "spec_power dropped")
+    power = _out(power, (T, max(nbins, 0)), x, torch.float64, "spec_power power")
+    dropped = _out(dropped, (T,), x, torch.float64, "spec_power dropped")
     if p2d is not None:
-        _spec_out(p2d, (T, H, W // 2 + 1), x, "spec_power p2d")
-    ws = _spec_ws(ws, spec_power_ws_bytes(T, H, W, nbins), x, "spec_power")
+        _out(p2d, (T, H, W // 2 + 1), x, torch.float64, "spec_power p2d")
+    ws = _ws(ws, spec_power_ws_bytes(T, H, W, nbins), x, "spec_power")
     L.check(lib().gd_spec_power(_ptr(x), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), _ptr(coef), _ptr(S), _ptr(twid_h), _ptr(twid_w),
                                 _ptr(bins), nbins, _ptr(power), _ptr(dropped), _ptr(p2d), _ptr(ws), ws.numel(), _stream()), "gd_spec_power")
     return power, dropped
@@ -2429,15 +2420,15 @@ def spec_cross(xa: Tensor, xb: Tensor, coef_a: Tensor, S_a: Tensor, coef_b: Tens
     T, H, W = xa.shape
     _spec_tables(xa, twid_h, twid_w, bins, "spec_cross")
     mask = _eval_mask(mask, H * W)
-    _spec_vec(wy, H, "spec_cross wy")
-    _spec_vec(wx, W, "spec_cross wx")
+    _vec(wy, H, "spec_cross wy")
+    _vec(wx, W, "spec_cross wx")
     for c, s in ((coef_a, S_a), (coef_b, S_b)):
-        _spec_vec(c, 3 * T, "spec_cross coef")
-        _spec_vec(s, 2 * T, "spec_cross S")
+        _vec(c, 3 * T, "spec_cross coef")
+        _vec(s, 2 * T, "spec_cross S")
     nbins = int(nbins)
-    out = _spec_out(out, (4, T, max(nbins, 0)), xa, "spec_cross out")
-    dropped = _spec_out(dropped, (T, 4), xa, "spec_cross dropped")
-    ws = _spec_ws(ws, spec_cross_ws_bytes(T, H, W, nbins), xa, "spec_cross")
+    out = _out(out, (4, T, max(nbins, 0)), xa, torch.float64, "spec_cross out")
+    dropped = _out(dropped, (T, 4), xa, torch.float64, "spec_cross dropped")
+    ws = _ws(ws, spec_cross_ws_bytes(T, H, W, nbins), xa, "spec_cross")
     L.check(lib().gd_spec_cross(_ptr(xa), _ptr(xb), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), _ptr(coef_a), _ptr(S_a), _ptr(coef_b),
                                 _ptr(S_b), _ptr(twid_h), _ptr(twid_w), _ptr(bins), nbins, _ptr(out), _ptr(dropped), _ptr(ws), ws.numel(),
                                 _stream()), "gd_spec_cross")
@@ -2445,17 +2436,11 @@ def spec_cross(xa: Tensor, xb: Tensor, coef_a: Tensor, S_a: Tensor, coef_b: Tens
 
 
 def _spec_host_args(x, mask, wy, wx, fn: str):
-    import numpy as np
     x, dt = _host_f(x, fn)
     if x.ndim != 3:
         raise L.GandanetError(f"{fn}: expected a (T, H, W) array, got {x.shape}")
     T, H, W = x.shape
-    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
-    wy = None if wy is None else np.ascontiguousarray(wy, dtype=np.float64).reshape(-1)
-    wx = None if wx is None else np.ascontiguousarray(wx, dtype=np.float64).reshape(-1)
-    if (mask is not None and mask.size != H * W) or (wy is not None and wy.size != H) or (wx is not None and wx.size != W):
-        raise L.GandanetError(f"{fn}: mask (H * W), wy (H) and wx (W) do not fit {x.shape}")
-    return x, dt, mask, wy, wx
+    return x, dt, _host_vec(mask, H * W, fn + " mask", "uint8"), _host_vec(wy, H, fn + " wy"), _host_vec(wx, W, fn + " wx")
 
 
 def spec_prepare_host(x, mask=None, wy=None, wx=None, detrend: str = "mean"):
@@ -2508,23 +2493,7 @@ def spec_cross_host(xa, xb, coef_a, S_a, coef_b, S_b, bins, nbins: int, mask=Non
 # ---- drought analysis (include/gandanet.h, "Drought analysis"; drought.hip) --------------------------------------------------
 def drought_which(maps) -> int:
     """the ``which`` bit set of gd_drought_events for an iterable of map names (L.DROUGHT_EV_MAPS)"""
-    which = 0
-    for name in maps:
-        if name not in L.DROUGHT_EV_MAPS:
-            raise L.GandanetError(f"unknown drought event map {name!r}: expected one of {L.DROUGHT_EV_MAPS}")
-        which |= 1 << L.DROUGHT_EV_MAPS.index(name)
-    if which == 0:
-        raise L.GandanetError("no drought event map selected")
-    return which
-
-
-def _drought_out(out: Optional[Tensor], shape, like: Tensor, dtype, name: str) -> Tensor:
-    if out is None:
-        return torch.empty(shape, device=like.device, dtype=dtype)
-    _dense(out, name, dtype)
-    if tuple(out.shape) != tuple(shape):
-        raise L.GandanetError(f"{name}: expected a dense {tuple(shape)} tensor, got {tuple(out.shape)}")
-    return out
+    return _which(maps, L.DROUGHT_EV_MAPS, "drought event")
 
 
 def drought_clim(x: Tensor, period: int = 12, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask: Optional[Tensor] = None,
@@ -2534,7 +2503,7 @@ def drought_clim(x: Tensor, period: int = 12, phase: int = 0, b0: int = 0, b1: O
     dt = _series_2d(x, "drought_clim input")
     T, M = x.shape
     b1 = T if b1 is None else b1
-    out = _drought_out(out, (3, int(period), M), x, torch.float64, "drought climatology")
+    out = _out(out, (3, int(period), M), x, torch.float64, "drought climatology")
     L.check(lib().gd_drought_clim(_ptr(x), dt, T, M, int(period), int(phase), int(b0), int(b1), _ptr(_eval_mask(mask, M)), _ptr(out),
                                   _stream()), "gd_drought_clim")
     return out
@@ -2549,7 +2518,7 @@ def drought_index(x: Tensor, clim: Tensor, phase: int = 0, kind: int = L.DROUGHT
     _dense(clim, "drought climatology", torch.float64)
     if clim.dim() != 3 or clim.shape[0] != 3 or clim.shape[2] != M:
         raise L.GandanetError(f"drought_index: the climatology is (3, period, {M}) float64, got {tuple(clim.shape)}")
-    out = _drought_out(out, (T, M), x, x.dtype, "drought index")
+    out = _out(out, (T, M), x, x.dtype, "drought index")
     L.check(lib().gd_drought_index(_ptr(x), dt, T, M, _ptr(clim), clim.shape[1], int(phase), int(kind), int(ddof),
                                    _ptr(_eval_mask(mask, M)), _ptr(out), _stream()), "gd_drought_index")
     return out
@@ -2566,7 +2535,7 @@ def drought_rank(x: Tensor, table: Tensor, period: int = 12, phase: int = 0, b0:
     nmax = math.isqrt(table.numel())
     if nmax * nmax != table.numel() or nmax == 0:
         raise L.GandanetError(f"drought_rank: the table holds nmax^2 doubles, got {table.numel()}")
-    out = _drought_out(out, (T, M), x, x.dtype, "drought rank index")
+    out = _out(out, (T, M), x, x.dtype, "drought rank index")
     L.check(lib().gd_drought_rank(_ptr(x), dt, T, M, int(period), int(phase), int(b0), int(b1), _ptr(_eval_mask(mask, M)), _ptr(table),
                                   nmax, _ptr(out), _stream()), "gd_drought_rank")
     return out
@@ -2579,9 +2548,9 @@ def drought_events(index: Tensor, threshold: float, min_duration: int = 3, maps=
     dt = _series_2d(index, "drought_events input")
     T, M = index.shape
     which = drought_which(maps)
-    out = _drought_out(out, (bin(which).count("1"), M), index, torch.float64, "drought event maps")
+    out = _out(out, (bin(which).count("1"), M), index, torch.float64, "drought event maps")
     if want_steps or in_event is not None:
-        in_event = _drought_out(in_event, (T, M), index, torch.uint8, "drought in_event")
+        in_event = _out(in_event, (T, M), index, torch.uint8, "drought in_event")
     L.check(lib().gd_drought_events(_ptr(index), dt, T, M, float(threshold), int(min_duration), which, _ptr(_eval_mask(mask, M)),
                                     _ptr(out), _ptr(in_event), _stream()), "gd_drought_events")
     return out, in_event
@@ -2592,20 +2561,16 @@ def drought_exceed(index: Tensor, threshold: float, out: Optional[Tensor] = None
     dt = _filter_dtype(index, "drought_exceed input")
     if index.numel() == 0:
         raise L.GandanetError("drought_exceed: empty tensor")
-    out = _drought_out(out, index.shape, index, index.dtype, "drought indicator")
+    out = _out(out, index.shape, index, index.dtype, "drought indicator")
     L.check(lib().gd_drought_exceed(_ptr(index), dt, index.numel(), float(threshold), _ptr(out), _stream()), "gd_drought_exceed")
     return out
 
 
 def _drought_host_args(x, mask, fn: str):
-    import numpy as np
     x, dt = _host_f(x, fn)
     if x.ndim != 2:
         raise L.GandanetError(f"{fn}: expected a (T, M) array, got {x.shape}")
-    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
-    if mask is not None and mask.size != x.shape[1]:
-        raise L.GandanetError(f"{fn}: {mask.size} mask entries for {x.shape[1]} series")
-    return x, dt, mask
+    return x, dt, _host_vec(mask, x.shape[1], fn + " mask", "uint8")
 
 
 def drought_clim_host(x, period: int = 12, phase: int = 0, b0: int = 0, b1=None, mask=None):
@@ -2654,7 +2619,7 @@ def drought_events_host(index, threshold: float, min_duration: int = 3, maps=L.D
     x, dt, mask = _drought_host_args(index, mask, "drought_events_host")
     T, M = x.shape
     which = drought_which(maps)
-    names = [nm for nm in L.DROUGHT_EV_MAPS if which >> L.DROUGHT_EV_MAPS.index(nm) & 1]
+    names = _which_names(which, L.DROUGHT_EV_MAPS)
     out = np.empty((len(names), M))
     steps = np.empty((T, M), dtype=np.uint8) if want_steps else None
     L.check(lib().gd_drought_events_host(x.ctypes.data, dt, T, M, float(threshold), int(min_duration), which, _np_ptr(mask),

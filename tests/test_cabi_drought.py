@@ -212,3 +212,47 @@ def test_cpu_and_bad_arguments_are_refused():
             call()
     t = D.rank_table("percentile", 3)
     assert t[0] == (1 - 0.44) / 1.12 and t[(3 - 1) ** 2 + 4] == (3 - 0.44) / 3.12 and D.rank_table("empirical", 1)[0] == 0.0
+
+
+@pytest.mark.parametrize("M", [1, 255, 256, 257])
+def test_host_twin_launcher_edges(M):
+    """the host side of the per-item launcher, T = 5, period 2: every host twin writes through the C entry into the middle of
+    a buffer of sentinels, leaves the sentinels alone, and a column's bits are those of the 257-series cube (the device
+    side of the same sizes: tests/test_gpu_drought.py::test_launcher_edges)"""
+    from gan_danet_amd import drought as D
+    from gan_danet_amd import kern as K
+    L, lib = _lib()
+    T, period, pad = 5, 2, 64
+    nmax = U.nmax_of(T, period, None)
+    table = np.ascontiguousarray(D.rank_table("empirical", nmax)).reshape(-1)
+
+    def guarded(n, dtype):
+        return np.full(n + 2 * pad, 7, dtype=dtype)
+
+    def middle(buf, n, shape):
+        assert np.all(buf[:pad] == 7) and np.all(buf[pad + n:] == 7), "written outside the output"
+        return buf[pad:pad + n].reshape(shape)
+
+    for dtype in (np.float64, np.float32):
+        wide, x = U.series(T, 257, dtype), U.series(T, M, dtype)
+        dt, ptr = int(dtype == np.float64), lambda b: b[pad:].ctypes.data
+        cb = guarded(3 * period * M, np.float64)
+        L.check(lib.gd_drought_clim_host(x.ctypes.data, dt, T, M, period, 0, 0, T, None, ptr(cb)), "gd_drought_clim_host")
+        clim = middle(cb, 3 * period * M, (3, period, M))
+        assert np.array_equal(clim, K.drought_clim_host(wide, period)[..., :M], equal_nan=True)
+        ib, rb, xb = guarded(T * M, dtype), guarded(T * M, dtype), guarded(T * M, dtype)
+        L.check(lib.gd_drought_index_host(x.ctypes.data, dt, T, M, clim.ctypes.data, period, 0, 1, 0, None, ptr(ib)), "gd_drought_index_host")
+        L.check(lib.gd_drought_rank_host(x.ctypes.data, dt, T, M, period, 0, 0, T, None, table.ctypes.data, nmax, ptr(rb)),
+                "gd_drought_rank_host")
+        L.check(lib.gd_drought_exceed_host(x.ctypes.data, dt, T * M, U.THRESHOLD, ptr(xb)), "gd_drought_exceed_host")
+        wclim = K.drought_clim_host(wide, period)
+        assert np.array_equal(middle(ib, T * M, (T, M)), K.drought_index_host(wide, wclim)[:, :M], equal_nan=True)
+        assert np.array_equal(middle(rb, T * M, (T, M)), K.drought_rank_host(wide, table, period)[:, :M], equal_nan=True)
+        assert np.array_equal(middle(xb, T * M, (T, M)), K.drought_exceed_host(wide, U.THRESHOLD)[:, :M], equal_nan=True)
+        mb, sb = guarded(len(U.EV_MAPS) * M, np.float64), guarded(T * M, np.uint8)
+        which = K.drought_which(U.EV_MAPS)
+        L.check(lib.gd_drought_events_host(x.ctypes.data, dt, T, M, U.THRESHOLD, 2, which, None, ptr(mb), ptr(sb)), "gd_drought_events_host")
+        maps, steps = K.drought_events_host(wide, U.THRESHOLD, 2, want_steps=True)
+        got = middle(mb, len(U.EV_MAPS) * M, (len(U.EV_MAPS), M))
+        assert all(np.array_equal(got[k], maps[nm][:M], equal_nan=True) for k, nm in enumerate(U.EV_MAPS))
+        assert np.array_equal(middle(sb, T * M, (T, M)), steps[:, :M])

@@ -181,3 +181,46 @@ def test_project_and_reconstruct_host(dtype):
                 assert got.dtype == od and np.isnan(got[:, ~ok]).all() and np.all(np.abs(got - want)[:, ok] <= bound[:, ok])
                 worst_r = max(worst_r, float((np.abs(got - want)[:, ok] / np.maximum(bound[:, ok], 1e-300)).max()))
     print(f"{np.dtype(dtype).name}: project_host at most {worst_p:.3f} of its bound, reconstruct_host {worst_r:.3f}")
+
+
+@pytest.mark.parametrize("M", [1, 255, 256, 257])
+def test_host_twin_launcher_edges(M):
+    """the host side of the per-item launcher, T = 5: gd_eof_prepare_host, gd_eof_project_host and gd_eof_reconstruct_host
+    write through the C entries into the middle of buffers of sentinels, leave the sentinels alone, and a column's bits are
+    those the wrappers give on the 257-series cube (the device side: tests/test_gpu_eof.py::test_launcher_edges)"""
+    from gan_danet_amd import kern as K
+    L, lib = _lib()
+    T, kk, pad = 5, 4, 64
+
+    def guarded(n, dtype):
+        return np.full(n + 2 * pad, 7, dtype=dtype)
+
+    def ptr(buf):
+        return buf[pad:].ctypes.data
+
+    def middle(buf, n, shape):
+        assert np.all(buf[:pad] == 7) and np.all(buf[pad + n:] == 7), "written outside the output"
+        return buf[pad:pad + n].reshape(shape)
+
+    rng = np.random.default_rng(7)
+    coef, eofs_w, pcs = rng.standard_normal((T, kk)), rng.standard_normal((kk, 257)), rng.standard_normal((T, kk))
+    w_wide = U.coslat_weights(257)
+    for dtype in (np.float64, np.float32):
+        wide = U.cube(T, 257, dtype)
+        wide[::2, 0] = np.nan                                            # a series with gaps, present at every M
+        x, w, eofs = np.ascontiguousarray(wide[:, :M]), np.ascontiguousarray(w_wide[:M]), np.ascontiguousarray(eofs_w[:, :M])
+        dt = int(dtype == np.float64)
+        mean_w, valid_w = K.eof_prepare_host(wide, None, w_wide, True)
+        mb, vb = guarded(M, np.float64), guarded(M, np.uint8)
+        L.check(lib.gd_eof_prepare_host(x.ctypes.data, dt, T, M, None, w.ctypes.data, 1, ptr(mb), ptr(vb)), "gd_eof_prepare_host")
+        mean, valid = middle(mb, M, (M,)).copy(), middle(vb, M, (M,)).copy()
+        assert np.array_equal(mean, mean_w[:M], equal_nan=True) and np.array_equal(valid, valid_w[:M])
+        pb = guarded(kk * M, np.float64)
+        L.check(lib.gd_eof_project_host(x.ctypes.data, dt, T, M, mean.ctypes.data, valid.ctypes.data, w.ctypes.data, 1, coef.ctypes.data, kk,
+                                        ptr(pb)), "gd_eof_project_host")
+        assert np.array_equal(middle(pb, kk * M, (kk, M)), K.eof_project_host(wide, mean_w, valid_w, coef, w_wide, True)[:, :M], equal_nan=True)
+        rb = guarded(T * M, dtype)
+        L.check(lib.gd_eof_reconstruct_host(eofs.ctypes.data, pcs.ctypes.data, mean.ctypes.data, valid.ctypes.data, w.ctypes.data, T, M, kk,
+                                            ptr(rb), dt), "gd_eof_reconstruct_host")
+        want = K.eof_reconstruct_host(eofs_w, pcs, mean_w, valid_w, w_wide, dtype)[:, :M]
+        assert np.array_equal(middle(rb, T * M, (T, M)), want, equal_nan=True)

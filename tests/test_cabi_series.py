@@ -215,3 +215,50 @@ def test_cpu_and_bad_tensors_are_refused():
     with pytest.raises(L.GandanetError):
         K.skill_which([])
     assert K.skill_which(U.MAPS) == 0xfff and K.skill_which(["cc", "n"]) == 0x101
+
+
+@pytest.mark.parametrize("M", [1, 255, 256, 257])
+def test_host_twin_launcher_edges(M):
+    """the host side of the per-item launcher, T = 5: gd_series_lstsq_host, gd_series_skill_host and gd_block_mean_host write
+    through the C entries into the middle of buffers of sentinels, leave the sentinels alone, and a column's (a block's)
+    bits are those the wrappers give on the 257-series input (the device side: tests/test_gpu_series.py::test_launcher_edges)"""
+    from gan_danet_amd import kern as K
+    L, lib = _lib()
+    T, P, pad = 5, 2, 64
+
+    def guarded(n, dtype=np.float64):
+        return np.full(n + 2 * pad, 7, dtype=dtype)
+
+    def ptr(buf):
+        return buf[pad:].ctypes.data
+
+    def middle(buf, n, shape):
+        assert np.all(buf[:pad] == 7) and np.all(buf[pad + n:] == 7), "written outside the output"
+        return buf[pad:pad + n].reshape(shape)
+
+    for dtype in (np.float64, np.float32):
+        dt = int(dtype == np.float64)
+        yw, a = U.fit_series(P, T, 257, dtype)
+        y = np.ascontiguousarray(yw[:, :M])
+        cb, rb, nb = guarded(P * M), guarded(M), guarded(M)
+        L.check(lib.gd_series_lstsq_host(y.ctypes.data, dt, T, M, a.ctypes.data, P, ptr(cb), ptr(rb), ptr(nb)), "gd_series_lstsq_host")
+        coef, rss, n = K.series_lstsq_host(yw, a)
+        assert np.array_equal(middle(cb, P * M, (P, M)), coef[:, :M], equal_nan=True)
+        assert np.array_equal(middle(rb, M, (M,)), rss[:M], equal_nan=True) and np.array_equal(middle(nb, M, (M,)), n[:M])
+
+        pw, tw = U.pair(T, 257, dtype)
+        recw = K.series_stats_host(pw, tw)
+        rec = np.ascontiguousarray(recw[:, :M])
+        names = L.SKILL_MAPS
+        sb = guarded(len(names) * M)
+        L.check(lib.gd_series_skill_host(rec.ctypes.data, M, 0, K.skill_which(names), ptr(sb)), "gd_series_skill_host")
+        want = K.series_skill_host(recw, names)
+        got = middle(sb, len(names) * M, (len(names), M))
+        assert all(np.array_equal(got[k], want[nm][:M], equal_nan=True) for k, nm in enumerate(names))
+
+        xw = U.block_case((1, 2, 2 * 257), dtype)
+        x = np.ascontiguousarray(xw[:, :, :2 * M])
+        ob, kb = guarded(M, dtype), guarded(M, np.int32)
+        L.check(lib.gd_block_mean_host(x.ctypes.data, dt, 1, 2, 2 * M, 2, 2, None, 1, ptr(ob), ptr(kb)), "gd_block_mean_host")
+        hm, hc = K.block_mean_host(xw, 2, 2)
+        assert np.array_equal(middle(ob, M, (1, 1, M)), hm[..., :M], equal_nan=True) and np.array_equal(middle(kb, M, (1, 1, M)), hc[..., :M])

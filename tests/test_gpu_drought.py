@@ -251,3 +251,30 @@ def test_compare_events_by_hand():
     assert r2.hits.shape == (1, 3) and r2.hits.dtype == torch.int64 and r2.false_alarms.tolist() == [[0, 2, 0]]
     with pytest.raises(D.L.GandanetError):
         D.compare_events(_dev(a), _dev(b[:3]))
+
+
+@pytest.mark.parametrize("M", [255, 256])
+def test_launcher_edges(M):
+    """every entry with T = 5, period 2 at the series counts on either side of a whole 256-thread workgroup (1 and 257 are
+    in U.MS): guarded outputs (the sentinels around them stay intact), bit for bit the host twins"""
+    from gan_danet_amd import drought as D
+    case = (5, 2, 0, None)
+    tables = {"empirical": D.rank_table("empirical", U.nmax_of(5, 2, None))}
+    for dtype in (np.float64, np.float32):
+        x = U.series(5, M, dtype)
+        _same(_device(x, _dev(x), case, tables, durations=(2,)), _host(x, case, tables, durations=(2,)), f"M={M} T=5 period 2")
+
+
+def test_exceed_grid_stride_beyond_the_cap():
+    """gd_drought_exceed with more elements than its capped grid has threads (65536 workgroups of 256): n = 2^24 + 257
+    fp32, so the first 257 threads take a second element; guarded output, bit for bit the host twin.  This is
+    drought_exceed_kernel, which kept a kernel of its own; the grid-stride form of gd_item_kernel (gd_block_mean, capped at
+    2^20 workgroups) would need more than 2^28 outputs for a second trip, which does not fit a test, so that step of the
+    shared launcher is run by no test (tests/test_gpu_series.py::test_launcher_edges covers its first trip)"""
+    from gan_danet_amd import kern as K
+    n = (1 << 24) + 257
+    x = np.random.default_rng(5).standard_normal(n).astype(np.float32)
+    x[::1001] = np.nan
+    g = Guarded((n,), torch.float32)
+    K.drought_exceed(_dev(x), U.THRESHOLD, out=g.out)
+    assert np.array_equal(g.get(), K.drought_exceed_host(x, U.THRESHOLD), equal_nan=True)

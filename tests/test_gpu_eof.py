@@ -277,3 +277,35 @@ def test_eof_analysis_gaps_masks_and_errors():
     with pytest.raises(GandanetError, match="GPU tensor"):
         E.eof_analysis(torch.zeros(4, 4))
     print(f"eof_analysis with gaps and masks: at most {worst:.3f} of the bounds")
+
+
+@pytest.mark.parametrize("M", [255, 256])
+def test_launcher_edges(M):
+    """prepare, project and reconstruct with T = 5 at the series counts on either side of a whole 256-thread workgroup (1 and
+    257 are in test_prepare_project_reconstruct_equal_their_twins): outputs in the middle of sentinel buffers, the
+    sentinels intact, bit for bit the host twins"""
+    from gan_danet_amd import kern as K
+    T, kk = 5, 4
+    x = U.cube(T, M, np.float32)
+    x[::2, 3] = np.nan
+    w = U.coslat_weights(M)
+    rng = np.random.default_rng(M)
+    mbuf = torch.full((M + 16,), SENTINEL, device="cuda", dtype=torch.float64)
+    vbuf = torch.full((M + 32,), 0xA5, device="cuda", dtype=torch.uint8)
+    K.eof_prepare(_dev(x), None, _dev(w), True, mean=mbuf[8:8 + M], valid=vbuf[16:16 + M])
+    mb, vb = mbuf.cpu().numpy(), vbuf.cpu().numpy()
+    assert np.all(mb[:8] == SENTINEL) and np.all(mb[8 + M:] == SENTINEL) and np.all(vb[:16] == 0xA5) and np.all(vb[16 + M:] == 0xA5)
+    mean, valid = K.eof_prepare_host(x, None, w, True)
+    assert np.array_equal(mb[8:8 + M], mean, equal_nan=True) and np.array_equal(vb[16:16 + M], valid)
+    coef = rng.standard_normal((T, kk))
+    buf = torch.full((kk * M + 16,), SENTINEL, device="cuda", dtype=torch.float64)
+    K.eof_project(_dev(x), _dev(mean), _dev(valid), _dev(coef), _dev(w), True, out=buf[8:8 + kk * M].view(kk, M))
+    b = buf.cpu().numpy()
+    assert np.all(b[:8] == SENTINEL) and np.all(b[8 + kk * M:] == SENTINEL)
+    assert np.array_equal(b[8:8 + kk * M].reshape(kk, M), K.eof_project_host(x, mean, valid, coef, w, True), equal_nan=True)
+    eofs, pcs = rng.standard_normal((kk, M)), rng.standard_normal((T, kk))
+    rbuf = torch.full((T * M + 16,), SENTINEL, device="cuda", dtype=torch.float32)
+    K.eof_reconstruct(_dev(eofs), _dev(pcs), _dev(mean), _dev(valid), _dev(w), torch.float32, out=rbuf[8:8 + T * M].view(T, M))
+    rb = rbuf.cpu().numpy()
+    assert np.all(rb[:8] == SENTINEL) and np.all(rb[8 + T * M:] == SENTINEL)
+    assert np.array_equal(rb[8:8 + T * M].reshape(T, M), K.eof_reconstruct_host(eofs, pcs, mean, valid, w, np.float32), equal_nan=True)

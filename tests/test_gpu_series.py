@@ -225,3 +225,57 @@ def test_block_mean_errors_and_consistency():
         assert torch.equal(TS.coarsen(_dev(fine), (5, 5)), _dev(coarse))
         assert torch.all(maps["rmse"] == 0) and torch.all(maps["cc"] == 1) and torch.all(maps["n"] == 24) and torch.all(maps["nse"] == 1)
         assert maps["cc"].shape == (6, 9)
+
+
+def _guarded(n, dtype=torch.float64):
+    """(buffer of sentinels, its middle ``n`` elements)"""
+    buf = torch.full((n + 128,), -7.0, device="cuda", dtype=dtype)
+    return buf, buf[64:64 + n]
+
+
+def _middle(buf, n):
+    host = buf.cpu().numpy()
+    assert np.all(host[:64] == -7) and np.all(host[64 + n:] == -7), "written outside the output"
+    return host[64:64 + n]
+
+
+@pytest.mark.parametrize("M", [1, 255, 256, 257])
+def test_launcher_edges(M):
+    """the one-thread-per-item launcher around its 256-thread workgroup, T = 5: lstsq, skill, harmonic_finalize and
+    block_mean write into the middle of sentinel buffers through the C entries; the sentinels stay, and the outputs are
+    bit for bit those of the host twins (harmonic_finalize has none: its slope is exact and amp / phase are within the
+    8 ulp of test_harmonic_fit_known_answer)"""
+    from gan_danet_amd import _lib as L
+    from gan_danet_amd import kern as K
+    lib, st, T, P = K.lib(), K._stream(), 5, 2
+    y, a = U.fit_series(P, T, M, np.float32)
+    bufs, yd, ad = [_guarded(n) for n in (P * M, M, M)], _dev(y), _dev(a)      # inputs stay referenced until their results are read
+    L.check(lib.gd_series_lstsq(yd.data_ptr(), L.FILTER_F32, T, M, ad.data_ptr(), P, *[v.data_ptr() for _, v in bufs], st), "gd_series_lstsq")
+    for (buf, v), host in zip(bufs, K.series_lstsq_host(y, a)):
+        assert np.array_equal(_middle(buf, v.numel()), host.reshape(-1), equal_nan=True), M
+
+    p, t = U.pair(T, M)
+    rec = K.series_stats_host(p, t)
+    names = L.SKILL_MAPS
+    (buf, v), recd = _guarded(len(names) * M), _dev(rec)
+    L.check(lib.gd_series_skill(recd.data_ptr(), M, 0, K.skill_which(names), v.data_ptr(), st), "gd_series_skill")
+    host = K.series_skill_host(rec, names)
+    assert np.array_equal(_middle(buf, v.numel()), np.stack([host[nm] for nm in names]).reshape(-1), equal_nan=True), M
+
+    rng = np.random.default_rng(M)
+    coef, rss, n = rng.standard_normal((4, M)), rng.random(M), np.full(M, 5.0)
+    bufs, ins = [_guarded(M) for _ in range(4)], [_dev(coef), _dev(rss), _dev(n)]
+    L.check(lib.gd_harmonic_finalize(ins[0].data_ptr(), 4, M, 1, 1, 0.5, ins[1].data_ptr(), ins[2].data_ptr(), *[v.data_ptr() for _, v in bufs],
+                                     st), "gd_harmonic_finalize")
+    amp, phase, slope, rms = (_middle(buf, M) for buf, _ in bufs)
+    assert np.array_equal(slope, coef[1] * 0.5)
+    assert U.ulps(amp, np.hypot(coef[2], coef[3])).max() <= 8 and U.ulps(phase, np.arctan2(coef[3], coef[2])).max() <= 8
+    assert U.ulps(rms, np.sqrt(rss / n)).max() <= 8
+
+    for dtype, td in ((np.float64, torch.float64), (np.float32, torch.float32)):
+        x = U.block_case((1, 2, 2 * M), dtype)
+        (buf, v), (cbuf, c), xd = _guarded(M, td), _guarded(M, torch.int32), _dev(x)
+        L.check(lib.gd_block_mean(xd.data_ptr(), int(dtype == np.float64), 1, 2, 2 * M, 2, 2, None, 1, v.data_ptr(), c.data_ptr(), st),
+                "gd_block_mean")
+        hm, hc = K.block_mean_host(x, 2, 2)
+        assert np.array_equal(_middle(buf, M), hm.reshape(-1), equal_nan=True) and np.array_equal(_middle(cbuf, M), hc.reshape(-1)), M
