@@ -34,6 +34,8 @@ from .spectra import (CrossSpectrum, Spectrum, cross_spectrum, effective_resolut
 from . import drought
 from .drought import (DSI_CLASSES, DroughtClimatology, DroughtEvents, climatology, compare_events, drought_area, drought_events,
                       drought_index)
+from . import clusters
+from .clusters import DroughtClusters, drought_clusters, label_components, structure_word
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

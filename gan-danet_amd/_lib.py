@@ -43,6 +43,12 @@ DROUGHT_MAX_T, DROUGHT_MAX_PERIOD, DROUGHT_MAX_N = 2048, 366, 257   # GD_DROUGHT
 DROUGHT_ANOMALY, DROUGHT_STANDARDIZED = 0, 1   # GD_DROUGHT_ANOMALY, GD_DROUGHT_STANDARDIZED
 DROUGHT_EV_MAPS = ("n_valid", "n_dry", "n_events", "event_steps", "max_duration", "mean_duration", "max_severity", "total_severity",
                    "peak", "longest_start", "worst_start", "last_run")   # GD_DROUGHT_EV_*: bit k of `which`
+CCL_TILE_T, CCL_TILE_H, CCL_TILE_W = 4, 8, 32   # GD_CCL_TILE_T, GD_CCL_TILE_H, GD_CCL_TILE_W
+CCL_U8, CCL_STRUCT_BITS = 2, 13   # GD_CCL_U8 (the dtype tag of a uint8 cube), GD_CCL_STRUCT_BITS
+CCL_NO_TILES, CCL_SEVERITY = 1, 1   # GD_CCL_NO_TILES (gd_ccl_label flags), GD_CCL_SEVERITY (gd_ccl_tracks flags)
+CCL_BOUNDS = ("n", "t0", "t1", "h0", "h1", "w0", "w1")   # GD_CCL_B_*: column k of the bounds table
+CCL_TRACK = ("count", "area", "severity", "sum_h", "sum_w", "min")   # GD_CCL_TR_*: column k of a track record
+CCL_TOTALS = ("volume", "severity", "peak_area", "peak_area_step", "peak", "centroid_t", "centroid_h", "centroid_w")   # GD_CCL_TO_*
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -263,6 +269,21 @@ SIGNATURES = {
     "gd_drought_events_host": (_i, [_p, _i, _l, _l, C.c_double, _i, _i, _p, _p, _p]),
     "gd_drought_exceed": (_i, [_p, _i, _l, C.c_double, _p, _p]),
     "gd_drought_exceed_host": (_i, [_p, _i, _l, C.c_double, _p]),
+    "gd_ccl_ws_bytes": (_sz, [_l]),
+    "gd_ccl_label": (_i, [_p, _i, _l, _l, _l, C.c_double, _p, _i, _i, _p, _p]),
+    "gd_ccl_label_host": (_i, [_p, _i, _l, _l, _l, C.c_double, _p, _i, _i, _p]),
+    "gd_ccl_filter": (_i, [_p, _l, _i, _p, _sz, _p]),
+    "gd_ccl_filter_host": (_i, [_p, _l, _i]),
+    "gd_ccl_relabel": (_i, [_p, _l, _p, _p, _p, _sz, _p]),
+    "gd_ccl_relabel_host": (_i, [_p, _l, _p, _p]),
+    "gd_ccl_bounds": (_i, [_p, _l, _l, _l, _i, _p, _p]),
+    "gd_ccl_bounds_host": (_i, [_p, _l, _l, _l, _i, _p]),
+    "gd_ccl_offsets": (_i, [_p, _i, _p, _p, _sz, _p]),
+    "gd_ccl_offsets_host": (_i, [_p, _i, _p]),
+    "gd_ccl_tracks": (_i, [_p, _i, _l, _l, _l, C.c_double, _p, _p, _p, _i, _l, _p, _i, _p, _p, _p]),
+    "gd_ccl_tracks_host": (_i, [_p, _i, _l, _l, _l, C.c_double, _p, _p, _p, _i, _l, _p, _i, _p, _p]),
+    "gd_ccl_totals": (_i, [_p, _p, _p, _i, _p, _p]),
+    "gd_ccl_totals_host": (_i, [_p, _p, _p, _i, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

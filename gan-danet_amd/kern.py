@@ -2634,3 +2634,195 @@ def drought_exceed_host(index, threshold: float):
     out = np.empty_like(x)
     L.check(lib().gd_drought_exceed_host(x.ctypes.data, dt, x.size, float(threshold), out.ctypes.data), "gd_drought_exceed_host")
     return out
+
+
+# ---- connected components (include/gandanet.h, "Connected components"; ccl.hip) ------------------------------------------------
+def _ccl_cube(x: Tensor, name: str) -> int:
+    """the dtype tag of a dense (T, H, W) fp32 / fp64 / uint8 device cube"""
+    if not isinstance(x, Tensor) or not x.is_cuda:
+        raise L.GandanetError(f"{name}: expected a GPU tensor (there is no CPU path)")
+    if x.dtype not in (torch.float32, torch.float64, torch.uint8):
+        raise L.GandanetError(f"{name}: expected float32, float64 or uint8, got {x.dtype}")
+    if x.dim() != 3 or x.numel() == 0 or not x.is_contiguous():
+        raise L.GandanetError(f"{name}: expected a dense non-empty (T, H, W) cube, got {tuple(x.shape)} with strides {x.stride()}")
+    return L.CCL_U8 if x.dtype == torch.uint8 else (L.FILTER_F64 if x.dtype == torch.float64 else L.FILTER_F32)
+
+
+def _ccl_ints(t: Tensor, shape, name: str) -> Tensor:
+    _dense(t, name, torch.int32)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise L.GandanetError(f"{name}: expected a dense {tuple(shape)} int32 tensor, got {tuple(t.shape)}")
+    return t
+
+
+def _ccl_ws(ws: Optional[Tensor], n: int, like: Tensor, name: str):
+    nbytes = lib().gd_ccl_ws_bytes(int(n))
+    ws = _ws(ws, nbytes, like, name)
+    return ws, ws.numel()
+
+
+def ccl_label(x: Tensor, threshold: float = 0.0, structure: int = 0, mask: Optional[Tensor] = None, tiles: bool = True,
+              out: Optional[Tensor] = None) -> Tensor:
+    """parent (T, H, W) int32 of a dense fp32 / fp64 / uint8 cube: the smallest raster index of every voxel's component, -1
+    on background.  ``structure``: the 13-bit word of backward offsets; ``tiles=False`` skips the LDS tile stage."""
+    dt = _ccl_cube(x, "ccl_label input")
+    T, H, W = x.shape
+    out = _out(out, (T, H, W), x, torch.int32, "ccl parent")
+    L.check(lib().gd_ccl_label(_ptr(x), dt, T, H, W, float(threshold), _ptr(_eval_mask(mask, H * W)), int(structure),
+                               0 if tiles else L.CCL_NO_TILES, _ptr(out), _stream()), "gd_ccl_label")
+    return out
+
+
+def ccl_filter(parent: Tensor, min_size: int, ws: Optional[Tensor] = None) -> Tensor:
+    """components of fewer than ``min_size`` voxels become background (-1), in place"""
+    _ccl_ints(parent, None, "ccl parent")
+    ws, nbytes = _ccl_ws(ws, parent.numel(), parent, "ccl_filter")
+    L.check(lib().gd_ccl_filter(_ptr(parent), parent.numel(), int(min_size), _ptr(ws), nbytes, _stream()), "gd_ccl_filter")
+    return parent
+
+
+def ccl_relabel(parent: Tensor, out: Optional[Tensor] = None, count: Optional[Tensor] = None, ws: Optional[Tensor] = None):
+    """(labels int32 of the shape of ``parent``, count (1,) int32 on the device): 0 on background, 1 .. K in raster order of
+    each component's first voxel.  ``out`` may be ``parent`` itself."""
+    _ccl_ints(parent, None, "ccl parent")
+    out = _ccl_ints(out, parent.shape, "ccl labels") if out is not None else torch.empty_like(parent)
+    count = _ccl_ints(count, (1,), "ccl count") if count is not None else torch.empty(1, device=parent.device, dtype=torch.int32)
+    ws, nbytes = _ccl_ws(ws, parent.numel(), parent, "ccl_relabel")
+    L.check(lib().gd_ccl_relabel(_ptr(parent), parent.numel(), _ptr(out), _ptr(count), _ptr(ws), nbytes, _stream()), "gd_ccl_relabel")
+    return out, count
+
+
+def ccl_bounds(labels: Tensor, K: int, out: Optional[Tensor] = None) -> Tensor:
+    """(K, 7) int32: n, t0, t1, h0, h1, w0, w1 of the labels 1 .. K of a dense (T, H, W) int32 cube"""
+    _ccl_ints(labels, None, "ccl labels")
+    if labels.dim() != 3:
+        raise L.GandanetError(f"ccl_bounds: expected a (T, H, W) label cube, got {tuple(labels.shape)}")
+    T, H, W = labels.shape
+    out = _out(out, (int(K), len(L.CCL_BOUNDS)), labels, torch.int32, "ccl bounds")
+    L.check(lib().gd_ccl_bounds(_ptr(labels), T, H, W, int(K), _ptr(out), _stream()), "gd_ccl_bounds")
+    return out
+
+
+def ccl_offsets(bounds: Tensor, out: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> Tensor:
+    """(K + 1) int32: the exclusive prefix sum of the clusters' durations; the last entry is the number of track records"""
+    _ccl_ints(bounds, None, "ccl bounds")
+    K = bounds.shape[0]
+    out = _out(out, (K + 1,), bounds, torch.int32, "ccl offsets")
+    ws, nbytes = _ccl_ws(ws, K, bounds, "ccl_offsets")
+    L.check(lib().gd_ccl_offsets(_ptr(bounds), K, _ptr(out), _ptr(ws), nbytes, _stream()), "gd_ccl_offsets")
+    return out
+
+
+def ccl_tracks(x: Optional[Tensor], labels: Tensor, bounds: Tensor, offsets: Tensor, R: int, threshold: float = 0.0,
+               weights: Optional[Tensor] = None, severity: bool = True):
+    """(tracks (R, 6) fp64, index (R, 2) int32) of the labelled clusters of the cube ``x`` (None or uint8: count and area only)"""
+    _ccl_ints(labels, None, "ccl labels")
+    T, H, W = labels.shape
+    dt = L.CCL_U8 if x is None else _ccl_cube(x, "ccl_tracks input")
+    if x is not None and tuple(x.shape) != (T, H, W):
+        raise L.GandanetError(f"ccl_tracks: the cube is {tuple(x.shape)}, the labels {tuple(labels.shape)}")
+    K = bounds.shape[0]
+    _ccl_ints(bounds, (K, len(L.CCL_BOUNDS)), "ccl bounds")
+    _ccl_ints(offsets, (K + 1,), "ccl offsets")
+    weights = _vec(weights, H * W, "ccl weights")
+    tracks = torch.empty((int(R), len(L.CCL_TRACK)), device=labels.device, dtype=torch.float64)
+    index = torch.empty((int(R), 2), device=labels.device, dtype=torch.int32)
+    L.check(lib().gd_ccl_tracks(_ptr(x), dt, T, H, W, float(threshold), _ptr(labels), _ptr(bounds), _ptr(offsets), K, int(R), _ptr(weights),
+                                L.CCL_SEVERITY if severity else 0, _ptr(tracks), _ptr(index), _stream()), "gd_ccl_tracks")
+    return tracks, index
+
+
+def ccl_totals(tracks: Tensor, bounds: Tensor, offsets: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """(K, 8) fp64: volume, severity, peak_area, peak_area_step, peak, centroid t, h, w of every cluster"""
+    K = bounds.shape[0]
+    _dense(tracks, "ccl tracks", torch.float64)
+    _ccl_ints(bounds, (K, len(L.CCL_BOUNDS)), "ccl bounds")
+    _ccl_ints(offsets, (K + 1,), "ccl offsets")
+    out = _out(out, (K, len(L.CCL_TOTALS)), tracks, torch.float64, "ccl totals")
+    L.check(lib().gd_ccl_totals(_ptr(tracks), _ptr(bounds), _ptr(offsets), K, _ptr(out), _stream()), "gd_ccl_totals")
+    return out
+
+
+def _ccl_host_cube(x, fn: str):
+    import numpy as np
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.float32, np.float64, np.uint8) or x.ndim != 3 or x.size == 0:
+        raise L.GandanetError(f"{fn}: expected a non-empty (T, H, W) float32 / float64 / uint8 array, got {x.dtype} {x.shape}")
+    return x, (L.CCL_U8 if x.dtype == np.uint8 else (L.FILTER_F64 if x.dtype == np.float64 else L.FILTER_F32))
+
+
+def ccl_label_host(x, threshold: float = 0.0, structure: int = 0, mask=None, tiles: bool = True):
+    """``ccl_label`` on a HOST array (a sequential union-find over the same code, no GPU)"""
+    import numpy as np
+    x, dt = _ccl_host_cube(x, "ccl_label_host")
+    T, H, W = x.shape
+    mask = _host_vec(mask, H * W, "ccl_label_host mask", "uint8")
+    out = np.empty((T, H, W), dtype=np.int32)
+    L.check(lib().gd_ccl_label_host(x.ctypes.data, dt, T, H, W, float(threshold), _np_ptr(mask), int(structure),
+                                    0 if tiles else L.CCL_NO_TILES, out.ctypes.data), "gd_ccl_label_host")
+    return out
+
+
+def ccl_filter_host(parent, min_size: int):
+    """``ccl_filter`` on a HOST array: a filtered copy"""
+    import numpy as np
+    parent = np.array(parent, dtype=np.int32, order="C")
+    L.check(lib().gd_ccl_filter_host(parent.ctypes.data, parent.size, int(min_size)), "gd_ccl_filter_host")
+    return parent
+
+
+def ccl_relabel_host(parent):
+    """``ccl_relabel`` on a HOST array: (labels, K)"""
+    import numpy as np
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    out, count = np.empty_like(parent), np.zeros(1, dtype=np.int32)
+    L.check(lib().gd_ccl_relabel_host(parent.ctypes.data, parent.size, out.ctypes.data, count.ctypes.data), "gd_ccl_relabel_host")
+    return out, int(count[0])
+
+
+def ccl_bounds_host(labels, K: int):
+    """``ccl_bounds`` on a HOST array"""
+    import numpy as np
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    T, H, W = labels.shape
+    out = np.empty((max(int(K), 0), len(L.CCL_BOUNDS)), dtype=np.int32)
+    L.check(lib().gd_ccl_bounds_host(labels.ctypes.data, T, H, W, int(K), out.ctypes.data), "gd_ccl_bounds_host")
+    return out
+
+
+def ccl_offsets_host(bounds):
+    """``ccl_offsets`` on a HOST array"""
+    import numpy as np
+    bounds = np.ascontiguousarray(bounds, dtype=np.int32)
+    out = np.empty(bounds.shape[0] + 1, dtype=np.int32)
+    L.check(lib().gd_ccl_offsets_host(bounds.ctypes.data, bounds.shape[0], out.ctypes.data), "gd_ccl_offsets_host")
+    return out
+
+
+def ccl_tracks_host(x, labels, bounds, offsets, threshold: float = 0.0, weights=None, severity: bool = True):
+    """``ccl_tracks`` on HOST arrays: (tracks (R, 6), index (R, 2)), R = offsets[-1]"""
+    import numpy as np
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    T, H, W = labels.shape
+    dt = L.CCL_U8
+    if x is not None:
+        x, dt = _ccl_host_cube(x, "ccl_tracks_host")
+    bounds, offsets = np.ascontiguousarray(bounds, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.int32)
+    K, R = bounds.shape[0], int(offsets[-1])
+    weights = _host_vec(weights, H * W, "ccl_tracks_host weights")
+    tracks, index = np.empty((R, len(L.CCL_TRACK))), np.empty((R, 2), dtype=np.int32)
+    L.check(lib().gd_ccl_tracks_host(None if x is None else x.ctypes.data, dt, T, H, W, float(threshold), labels.ctypes.data,
+                                     bounds.ctypes.data, offsets.ctypes.data, K, R, _np_ptr(weights), L.CCL_SEVERITY if severity else 0,
+                                     tracks.ctypes.data, index.ctypes.data), "gd_ccl_tracks_host")
+    return tracks, index
+
+
+def ccl_totals_host(tracks, bounds, offsets):
+    """``ccl_totals`` on HOST arrays"""
+    import numpy as np
+    tracks = np.ascontiguousarray(tracks, dtype=np.float64)
+    bounds, offsets = np.ascontiguousarray(bounds, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.int32)
+    out = np.empty((bounds.shape[0], len(L.CCL_TOTALS)))
+    L.check(lib().gd_ccl_totals_host(tracks.ctypes.data, bounds.ctypes.data, offsets.ctypes.data, bounds.shape[0], out.ctypes.data),
+            "gd_ccl_totals_host")
+    return out

@@ -1273,6 +1273,75 @@ int gd_drought_events_host(const void* index, int dtype, long T, long M, double 
 int gd_drought_exceed(const void* index, int dtype, long n, double threshold, void* out, void* stream);
 int gd_drought_exceed_host(const void* index, int dtype, long n, double threshold, void* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Connected components (ccl.hip, csrc/ccl_core.h): which dry voxels of a (T, H, W) cube belong to the same drought --
+ * 3-D connected-component labelling, a size filter, canonical labels, and per cluster its bounding box, its track (one
+ * record per step of its life) and its totals.  The cube stays on the device; two integers cross to the host, the number
+ * of clusters K (to size the tables) and the number of track records R.
+ * Voxel (t, h, w) of the dense cube has raster index i = (t H + h) W + w; N = T H W < 2^31; indices and labels are int32.
+ * Foreground: x fp32 (dtype 0) or fp64 (dtype 1): x[i] <= threshold (never for NaN) and, with mask (H W bytes, NULL = all),
+ * mask[h W + w] != 0; x uint8 (dtype GD_CCL_U8, for instance the in_event cube of gd_drought_events): x[i] != 0 (the
+ * threshold is not read).
+ * Neighbourhood: any symmetric 3 x 3 x 3 structure with its centre set, as the word `structure` of its 13 backward
+ * offsets: bit k, 0 <= k < 13, links (t, h, w) with (t + k / 9 - 1, h + k / 3 % 3 - 1, w + k % 3 - 1), the offsets that
+ * come before the centre in raster order (the forward half follows by symmetry).  0 links nothing.
+ * Every *_host twin takes the same arguments in HOST memory (no workspace, no stream), makes no GPU call and gives the
+ * same bits.  Every argument is checked before any launch (-1 and gd_last_error).  No float atomics anywhere: the integer
+ * outputs do not depend on the order the atomics land in, and the fp64 sums have the fixed order of csrc/ccl_core.h.
+ *
+ * gd_ccl_label: parent (N) int32 = the smallest raster index of the voxel's component, -1 on background.  Three kernels:
+ * union-find inside tiles of GD_CCL_TILE_T x _H x _W voxels in LDS, unions across tile faces, edges and corners in global
+ * memory, a flattening pass.  parent[i] <= i always holds and a parent is only lowered, by atomic min; no thread waits for
+ * another (the argument is at the top of csrc/ccl_core.h).  flags GD_CCL_NO_TILES skips the LDS stage (every union in
+ * global memory): the same output, kept for comparison.
+ * gd_ccl_filter: components of fewer than min_size (>= 1) voxels become background, in place.  ws: gd_ccl_ws_bytes(N).
+ * gd_ccl_relabel: labels (N) int32, 0 on background and 1 .. K in raster order of each component's first voxel (the
+ * numbering of scipy.ndimage.label); *count = K (device memory; host memory for the twin).  The roots are flagged and
+ * scanned by a plain three-pass exclusive prefix sum.  labels may be parent itself.  ws: gd_ccl_ws_bytes(N).
+ * gd_ccl_bounds: bounds (K, GD_CCL_BOUNDS) int32: n, t0, t1, h0, h1, w0, w1 (inclusive) of label k + 1 at row k.
+ * gd_ccl_offsets: offsets (K + 1) int32, the exclusive prefix sum of the durations t1 - t0 + 1; offsets[K] = R.
+ * ws: gd_ccl_ws_bytes(K).
+ * gd_ccl_tracks: tracks (R, GD_CCL_TRACK) doubles, record offsets[k] + (t - t0) for cluster k at step t: the pixel count,
+ * the area sum a, the severity sum a (threshold - x), sum a h, sum a w, and the smallest x; a = weights[h W + w] (H W
+ * doubles) or 1 with NULL.  index (R, 2) int32: k and t of every record.  One workgroup per record walks the bounding
+ * box of the cluster in that plane.  flags GD_CCL_SEVERITY asks for severity and minimum and needs an fp32 / fp64 x (with
+ * uint8 it is refused); without it x may be NULL and both are NaN.
+ * gd_ccl_totals: totals (K, GD_CCL_TOTALS) doubles from the records in ascending t: the volume sum_t area, the severity,
+ * the largest area and its (first) step, the smallest x, and the area-weighted centroid (t, h, w).
+ * ---------------------------------------------------------------------------------------- */
+#define GD_CCL_TILE_T 4
+#define GD_CCL_TILE_H 8
+#define GD_CCL_TILE_W 32
+#define GD_CCL_U8 2
+#define GD_CCL_STRUCT_BITS 13
+enum { GD_CCL_NO_TILES = 1 };   /* flags of gd_ccl_label */
+enum { GD_CCL_SEVERITY = 1 };   /* flags of gd_ccl_tracks */
+enum { GD_CCL_B_N = 0, GD_CCL_B_T0 = 1, GD_CCL_B_T1 = 2, GD_CCL_B_H0 = 3, GD_CCL_B_H1 = 4, GD_CCL_B_W0 = 5, GD_CCL_B_W1 = 6,
+       GD_CCL_BOUNDS = 7 };
+enum { GD_CCL_TR_COUNT = 0, GD_CCL_TR_AREA = 1, GD_CCL_TR_SEVERITY = 2, GD_CCL_TR_SUM_H = 3, GD_CCL_TR_SUM_W = 4, GD_CCL_TR_MIN = 5,
+       GD_CCL_TRACK = 6 };
+enum { GD_CCL_TO_VOLUME = 0, GD_CCL_TO_SEVERITY = 1, GD_CCL_TO_PEAK_AREA = 2, GD_CCL_TO_PEAK_AREA_STEP = 3, GD_CCL_TO_PEAK = 4,
+       GD_CCL_TO_CENTROID_T = 5, GD_CCL_TO_CENTROID_H = 6, GD_CCL_TO_CENTROID_W = 7, GD_CCL_TOTALS = 8 };
+size_t gd_ccl_ws_bytes(long n);
+int gd_ccl_label(const void* x, int dtype, long T, long H, long W, double threshold, const unsigned char* mask, int structure,
+                 int flags, int* parent, void* stream);
+int gd_ccl_label_host(const void* x, int dtype, long T, long H, long W, double threshold, const unsigned char* mask, int structure,
+                      int flags, int* parent);
+int gd_ccl_filter(int* parent, long n, int min_size, void* ws, size_t ws_bytes, void* stream);
+int gd_ccl_filter_host(int* parent, long n, int min_size);
+int gd_ccl_relabel(const int* parent, long n, int* labels, int* count, void* ws, size_t ws_bytes, void* stream);
+int gd_ccl_relabel_host(const int* parent, long n, int* labels, int* count);
+int gd_ccl_bounds(const int* labels, long T, long H, long W, int K, int* bounds, void* stream);
+int gd_ccl_bounds_host(const int* labels, long T, long H, long W, int K, int* bounds);
+int gd_ccl_offsets(const int* bounds, int K, int* offsets, void* ws, size_t ws_bytes, void* stream);
+int gd_ccl_offsets_host(const int* bounds, int K, int* offsets);
+int gd_ccl_tracks(const void* x, int dtype, long T, long H, long W, double threshold, const int* labels, const int* bounds,
+                  const int* offsets, int K, long R, const double* weights, int flags, double* tracks, int* index, void* stream);
+int gd_ccl_tracks_host(const void* x, int dtype, long T, long H, long W, double threshold, const int* labels, const int* bounds,
+                       const int* offsets, int K, long R, const double* weights, int flags, double* tracks, int* index);
+int gd_ccl_totals(const double* tracks, const int* bounds, const int* offsets, int K, double* totals, void* stream);
+int gd_ccl_totals_host(const double* tracks, const int* bounds, const int* offsets, int K, double* totals);
+
 #ifdef __cplusplus
 }
 #endif
