@@ -49,6 +49,8 @@ CCL_NO_TILES, CCL_SEVERITY = 1, 1   # GD_CCL_NO_TILES (gd_ccl_label flags), GD_C
 CCL_BOUNDS = ("n", "t0", "t1", "h0", "h1", "w0", "w1")   # GD_CCL_B_*: column k of the bounds table
 CCL_TRACK = ("count", "area", "severity", "sum_h", "sum_w", "min")   # GD_CCL_TR_*: column k of a track record
 CCL_TOTALS = ("volume", "severity", "peak_area", "peak_area_step", "peak", "centroid_t", "centroid_h", "centroid_w")   # GD_CCL_TO_*
+NBR_MAX_HW, NBR_MAX_K, NBR_MAX_S = 1 << 20, 8, 32   # GD_NBR_MAX_HW, GD_NBR_MAX_K, GD_NBR_MAX_S
+NBR_NORMALIZE = {"window": 0, "valid": 1}            # GD_NBR_WINDOW, GD_NBR_VALID
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -284,6 +286,11 @@ SIGNATURES = {
     "gd_ccl_tracks_host": (_i, [_p, _i, _l, _l, _l, C.c_double, _p, _p, _p, _i, _l, _p, _i, _p, _p]),
     "gd_ccl_totals": (_i, [_p, _p, _p, _i, _p, _p]),
     "gd_ccl_totals_host": (_i, [_p, _p, _p, _i, _p]),
+    "gd_nbr_ws_bytes": (_sz, [_l, _l, _i, _l]),
+    "gd_nbr_fss": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "gd_nbr_fss_host": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p]),
+    "gd_nbr_fraction": (_i, [_p, _i, _l, _l, _l, _p, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "gd_nbr_fraction_host": (_i, [_p, _i, _l, _l, _l, _p, _p, _i, _i, _i, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

@@ -2826,3 +2826,152 @@ def ccl_totals_host(tracks, bounds, offsets):
     L.check(lib().gd_ccl_totals_host(tracks.ctypes.data, bounds.ctypes.data, offsets.ctypes.data, bounds.shape[0], out.ctypes.data),
             "gd_ccl_totals_host")
     return out
+
+
+# ---- neighbourhood verification (include/gandanet.h, "Neighbourhood verification"; neighborhood.hip) ----------------------------
+NBR_WS_BUDGET = 256 << 20   # bytes of tables and partials in flight when the caller gives no workspace
+
+
+def _nbr_cube(x: Tensor, name: str) -> int:
+    if not isinstance(x, Tensor):
+        raise L.GandanetError(f"{name}: expected a GPU tensor (there is no CPU path)")
+    dt = _filter_dtype(x, name)
+    if x.dim() != 3 or x.numel() == 0:
+        raise L.GandanetError(f"{name}: expected a dense non-empty (T, H, W) cube, got {tuple(x.shape)}")
+    return dt
+
+
+def _nbr_thresholds(thr, T: int, name: str):
+    """the (T, K) fp64 HOST table of ``thr``: (K,) entries hold at every step"""
+    import numpy as np
+    a = np.asarray(thr.detach().cpu() if isinstance(thr, Tensor) else thr, dtype=np.float64)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (T, a.size))
+    if a.ndim != 2 or a.shape[0] != T or a.shape[1] == 0:
+        raise L.GandanetError(f"{name}: expected (K,) or ({T}, K) thresholds, got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _nbr_step_thresholds(thr, T: int, name: str):
+    """the (T,) fp64 HOST vector of one threshold, or of one per step"""
+    import numpy as np
+    a = np.asarray(thr.detach().cpu() if isinstance(thr, Tensor) else thr, dtype=np.float64).reshape(-1)
+    if a.size not in (1, T):
+        raise L.GandanetError(f"{name}: one threshold, or one per step ({T}), got {a.size}")
+    return np.ascontiguousarray(np.broadcast_to(a, (T,)))
+
+
+def _nbr_scales(scales):
+    import numpy as np
+    seq = [scales] if isinstance(scales, (int, np.integer)) else list(scales)
+    if any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 1 << 31 for n in seq):
+        raise L.GandanetError(f"scales: expected integer window widths, got {scales!r}")
+    return np.asarray(seq, dtype=np.int32).reshape(-1)
+
+
+def _nbr_normalize(normalize) -> int:
+    if normalize not in L.NBR_NORMALIZE:
+        raise L.GandanetError(f"normalize is one of {tuple(L.NBR_NORMALIZE)}, got {normalize!r}")
+    return L.NBR_NORMALIZE[normalize]
+
+
+def nbr_ws_bytes(H: int, W: int, K: int, planes: int = 1) -> int:
+    return int(lib().gd_nbr_ws_bytes(int(H), int(W), int(K), int(planes)))
+
+
+def _nbr_ws(ws: Optional[Tensor], like: Tensor, T: int, H: int, W: int, K: int, planes: Optional[int], name: str):
+    one = nbr_ws_bytes(H, W, K, 1)
+    if planes is None:
+        planes = max(1, min(T, NBR_WS_BUDGET // max(one, 1)))
+    ws = _ws(ws, one * max(1, min(int(planes), T)), like, name)
+    return ws, ws.numel()
+
+
+def nbr_fss(f: Tensor, o: Tensor, thr_f, thr_o, scales, below: bool = True, normalize: str = "window", maps: bool = False,
+            mask: Optional[Tensor] = None, ws: Optional[Tensor] = None, planes: Optional[int] = None):
+    """(sums (T, K, S, 3), base (T, K, 3), maps (K, S, H, W, 3) or None) of two dense fp32 / fp64 cubes (T, H, W) of one
+    dtype, all on the device: int64 tensors holding the unsigned 64-bit records (every value is below 2^61), or fp64
+    ``sums`` and ``maps`` with ``normalize="valid"``.  ``thr_f``, ``thr_o``: (K,) or (T, K) thresholds on the HOST; ``scales``:
+    odd widths; ``mask``: H W uint8.  ``planes`` steps in flight (default: NBR_WS_BUDGET bytes of them).  No host sync."""
+    dt = _nbr_cube(f, "nbr_fss forecast")
+    if not isinstance(o, Tensor) or o.dtype != f.dtype or _nbr_cube(o, "nbr_fss observed") != dt or o.shape != f.shape:
+        raise L.GandanetError(f"nbr_fss: forecast {tuple(f.shape)} {f.dtype} against observed "
+                              f"{tuple(getattr(o, 'shape', ()))} {getattr(o, 'dtype', type(o))}")
+    T, H, W = f.shape
+    tf = _nbr_thresholds(thr_f, T, "nbr_fss thresholds")
+    to = _nbr_thresholds(thr_o, T, "nbr_fss observed thresholds")
+    if tf.shape != to.shape:
+        raise L.GandanetError(f"nbr_fss: thresholds {tf.shape} against observed thresholds {to.shape}")
+    K, sc, mode = tf.shape[1], _nbr_scales(scales), _nbr_normalize(normalize)
+    S = sc.size
+    kind = torch.float64 if mode else torch.int64
+    rec = torch.empty(T * K * (S + 1) * 3, device=f.device, dtype=torch.int64)
+    n_s = T * K * S * 3
+    out = torch.empty((K, S, H, W, 3), device=f.device, dtype=kind) if maps else None
+    ws, nbytes = _nbr_ws(ws, f, T, H, W, K, planes, "nbr_fss")
+    L.check(lib().gd_nbr_fss(_ptr(f), _ptr(o), dt, T, H, W, _ptr(_eval_mask(mask, H * W)), tf.ctypes.data, to.ctypes.data, K, int(bool(below)),
+                             sc.ctypes.data, S, mode, rec.data_ptr(), rec.data_ptr() + 8 * n_s, _ptr(out), _ptr(ws), nbytes, _stream()),
+            "gd_nbr_fss")
+    return rec[:n_s].view(kind).view(T, K, S, 3), rec[n_s:].view(T, K, 3), out
+
+
+def nbr_fraction(x: Tensor, thr, scale: int, below: bool = True, normalize: str = "window", mask: Optional[Tensor] = None,
+                 out: Optional[Tensor] = None, ws: Optional[Tensor] = None, planes: Optional[int] = None) -> Tensor:
+    """the (T, H, W) fp64 neighbourhood fraction of a dense fp32 / fp64 cube at the odd width ``scale``; ``thr``: one
+    threshold or one per step, on the HOST"""
+    dt = _nbr_cube(x, "nbr_fraction input")
+    T, H, W = x.shape
+    th = _nbr_step_thresholds(thr, T, "nbr_fraction threshold")
+    sc = _nbr_scales(scale)
+    if sc.size != 1:
+        raise L.GandanetError(f"nbr_fraction: one scale, got {scale!r}")
+    out = _out(out, (T, H, W), x, torch.float64, "neighbourhood fraction")
+    ws, nbytes = _nbr_ws(ws, x, T, H, W, 1, planes, "nbr_fraction")
+    L.check(lib().gd_nbr_fraction(_ptr(x), dt, T, H, W, _ptr(_eval_mask(mask, H * W)), th.ctypes.data, int(bool(below)), int(sc[0]),
+                                  _nbr_normalize(normalize), _ptr(out), _ptr(ws), nbytes, _stream()), "gd_nbr_fraction")
+    return out
+
+
+def _nbr_host_cube(x, fn: str):
+    x, dt = _host_f(x, fn)
+    if x.ndim != 3:
+        raise L.GandanetError(f"{fn}: expected a (T, H, W) array, got {x.shape}")
+    return x, dt
+
+
+def nbr_fss_host(f, o, thr_f, thr_o, scales, below: bool = True, normalize: str = "window", maps: bool = False, mask=None):
+    """``nbr_fss`` on HOST arrays (plain C++ over the same per-pixel code, in the device's order of sums, no GPU): (sums
+    (T, K, S, 3) uint64 or fp64, base (T, K, 3) uint64, maps (K, S, H, W, 3) or None)"""
+    import numpy as np
+    f, dt = _nbr_host_cube(f, "nbr_fss_host")
+    o, dt2 = _nbr_host_cube(o, "nbr_fss_host")
+    if dt != dt2 or f.shape != o.shape:
+        raise L.GandanetError(f"nbr_fss_host: forecast {f.shape} {f.dtype} against observed {o.shape} {o.dtype}")
+    T, H, W = f.shape
+    tf, to = _nbr_thresholds(thr_f, T, "nbr_fss_host thresholds"), _nbr_thresholds(thr_o, T, "nbr_fss_host observed thresholds")
+    if tf.shape != to.shape:
+        raise L.GandanetError(f"nbr_fss_host: thresholds {tf.shape} against observed thresholds {to.shape}")
+    K, sc, mode = tf.shape[1], _nbr_scales(scales), _nbr_normalize(normalize)
+    kind = np.float64 if mode else np.uint64
+    mask = _host_vec(mask, H * W, "nbr_fss_host mask", "uint8")
+    sums, base = np.empty((T, K, sc.size, 3), dtype=kind), np.empty((T, K, 3), dtype=np.uint64)
+    out = np.empty((K, sc.size, H, W, 3), dtype=kind) if maps else None
+    L.check(lib().gd_nbr_fss_host(f.ctypes.data, o.ctypes.data, dt, T, H, W, _np_ptr(mask), tf.ctypes.data, to.ctypes.data, K, int(bool(below)),
+                                  sc.ctypes.data, sc.size, mode, sums.ctypes.data, base.ctypes.data, _np_ptr(out)), "gd_nbr_fss_host")
+    return sums, base, out
+
+
+def nbr_fraction_host(x, thr, scale: int, below: bool = True, normalize: str = "window", mask=None):
+    """``nbr_fraction`` on a HOST array"""
+    import numpy as np
+    x, dt = _nbr_host_cube(x, "nbr_fraction_host")
+    T, H, W = x.shape
+    th = _nbr_step_thresholds(thr, T, "nbr_fraction_host threshold")
+    sc = _nbr_scales(scale)
+    mask = _host_vec(mask, H * W, "nbr_fraction_host mask", "uint8")
+    out = np.empty((T, H, W))
+    L.check(lib().gd_nbr_fraction_host(x.ctypes.data, dt, T, H, W, _np_ptr(mask), th.ctypes.data, int(bool(below)), int(sc[0]),
+                                       _nbr_normalize(normalize), out.ctypes.data), "gd_nbr_fraction_host")
+    return out

@@ -1342,6 +1342,57 @@ int gd_ccl_tracks_host(const void* x, int dtype, long T, long H, long W, double 
 int gd_ccl_totals(const double* tracks, const int* bounds, const int* offsets, int K, double* totals, void* stream);
 int gd_ccl_totals_host(const double* tracks, const int* bounds, const int* offsets, int K, double* totals);
 
+/* ------------------------------------------------------------------------------------------
+ * Neighbourhood verification (neighborhood.hip, csrc/neighborhood_core.h): at which spatial scale does a forecast field put
+ * its events where the observed field puts them -- the fractions skill score (FSS) of Roberts & Lean 2008 over K thresholds
+ * and S window widths, and the neighbourhood fraction field of one cube.
+ * f (forecast) and o (observed): dense (T, H, W) cubes of ONE dtype, fp32 (0) or fp64 (1), on one grid; H W <= GD_NBR_MAX_HW,
+ * T H W < 2^31.  mask: NULL, or H W bytes, 0 = the pixel is not used.  thr_f, thr_o: (T, K) doubles in HOST memory (also for
+ * the device entry: they are checked for NaN before any launch and travel as kernel arguments), the thresholds of step t;
+ * 1 <= K <= GD_NBR_MAX_K.  scales: S odd window widths n >= 1 in HOST memory, 1 <= S <= GD_NBR_MAX_S; a window wider than
+ * the domain is the whole domain.  below 1: the event is x <= thr; below 0: x >= thr; compared in fp64, never for NaN.
+ *
+ * Pixel (t, i, j) is valid when the mask is nonzero there and neither f nor o is NaN.  I_f = valid && event(f), I_o = valid
+ * && event(o).  For n = 2 h + 1, cf, co, cv at (i, j) are the sums of I_f, I_o, valid over rows i - h .. i + h and columns
+ * j - h .. j + h; positions outside the domain count zero.  Per (t, k, s), over the VALID centre pixels:
+ *   GD_NBR_WINDOW: sums = A, B, C = sum (cf - co)^2, sum cf^2, sum co^2 as unsigned 64-bit integers (the n^4 of the fractions
+ *   c / n^2 cancels in FSS = 1 - A / (B + C)); exact, whatever the order.
+ *   GD_NBR_VALID: fractions cf / cv and co / cv in fp64; sums = the fp64 sums of (pf - po)^2, pf^2, po^2 in the fixed order
+ *   of csrc/neighborhood_core.h, every operation rounded on its own.
+ * sums: (T, K, S, 3) 8-byte words of that kind.  base: (T, K, 3) unsigned 64-bit: sum I_f, sum I_o, the number of valid
+ * pixels.  maps: NULL, or (K, S, H, W, 3) words: the same three sums per centre pixel over time; a pixel is one thread's,
+ * the steps are added in ascending t.  No atomics anywhere.
+ *
+ * Method: per step and threshold one summed-area table of (H + 1) x (W + 1) 64-bit words with a zero leading row and column;
+ * a word packs the three counts in 21-bit fields (each is at most 2^20), so a window is four 8-byte loads.  Rows are scanned
+ * by a wave (cross-lane scan, a carry between 64-lane segments), columns by one thread each; then every workgroup of the
+ * score kernel takes all scales of its centre pixels, one partial per workgroup and scale, added in ascending order.
+ * ws: gd_nbr_ws_bytes(H, W, K, planes) bytes hold the tables and partials of `planes` steps in flight (0 for arguments
+ * outside the limits); the entry walks T in chunks of as many steps as ws_bytes holds, at least one, and the result does
+ * not depend on it.  gd_nbr_fraction builds tables of K = 1: gd_nbr_ws_bytes(H, W, 1, planes).
+ *
+ * gd_nbr_fraction: out (T, H, W) doubles, cf / n^2 (GD_NBR_WINDOW; n^2 formed in fp64, exact for n < 2^26) or cf / cv
+ * (GD_NBR_VALID) of the one cube x at width `scale`; NaN at an invalid centre.  thr: T doubles in HOST memory.
+ * Every *_host twin takes the same arguments with the cubes and outputs in HOST memory (no workspace, no stream), makes no
+ * GPU call, runs the same per-pixel code and gives the same bits.  Every argument is checked before any launch (-1 and
+ * gd_last_error).
+ * ---------------------------------------------------------------------------------------- */
+#define GD_NBR_MAX_HW 1048576
+#define GD_NBR_MAX_K 8
+#define GD_NBR_MAX_S 32
+enum { GD_NBR_WINDOW = 0, GD_NBR_VALID = 1 };   /* normalize */
+size_t gd_nbr_ws_bytes(long H, long W, int K, long planes);
+int gd_nbr_fss(const void* f, const void* o, int dtype, long T, long H, long W, const unsigned char* mask, const double* thr_f,
+               const double* thr_o, int K, int below, const int* scales, int S, int normalize, void* sums, unsigned long long* base,
+               void* maps, void* ws, size_t ws_bytes, void* stream);
+int gd_nbr_fss_host(const void* f, const void* o, int dtype, long T, long H, long W, const unsigned char* mask, const double* thr_f,
+                    const double* thr_o, int K, int below, const int* scales, int S, int normalize, void* sums, unsigned long long* base,
+                    void* maps);
+int gd_nbr_fraction(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* thr, int below, int scale,
+                    int normalize, double* out, void* ws, size_t ws_bytes, void* stream);
+int gd_nbr_fraction_host(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* thr, int below,
+                         int scale, int normalize, double* out);
+
 #ifdef __cplusplus
 }
 #endif
