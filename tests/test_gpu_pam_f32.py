@@ -9,7 +9,7 @@ import torch
 
 from fill import fill_module
 from gpu_util import DEV, assert_close, load_golden, rell2, relmax, seeded
-from test_gpu_pam_wide import _reference
+from pam_util import reference as _reference
 
 pytestmark = pytest.mark.gpu
 

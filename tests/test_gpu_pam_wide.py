@@ -7,6 +7,7 @@ import torch
 
 from fill import fill_module
 from gpu_util import DEV, assert_close, bf16_round, rell2, relmax, seeded
+from pam_util import reference as _reference
 
 pytestmark = pytest.mark.gpu
 
@@ -55,20 +56,6 @@ def _run_wide(p, gamma=0.7, deterministic=None):
                    c_alg=C, f16=p["f16"], deterministic=deterministic)
     torch.cuda.synchronize()
     return dict(out=out, o=o_attn, lse=lse, delta=delta, dq=dqn[:, :r, :N], dk=dkn[:, :r, :N], dv=dv[:, :C, :N])
-
-
-def _reference(c, x, gamma=0.7):
-    """fp64 restatement of generator.py:115-122 and its gradients on the packed operands"""
-    e = c["q"] @ c["k"].transpose(1, 2)                        # (B, N, N) energies, no 1/sqrt(d)
-    lse = torch.logsumexp(e, -1)
-    p = torch.softmax(e, -1)
-    o = p @ c["v"]                                             # (B, N, C)
-    dp = c["do"] @ c["v"].transpose(1, 2)
-    delta = (c["do"] * o).sum(-1, keepdim=True)
-    ds = p * (dp - delta)
-    return dict(o=o.transpose(1, 2), out=gamma * o.transpose(1, 2) + x.double().cpu(), lse=lse,
-                dq=(ds @ c["k"]).transpose(1, 2), dk=(ds.transpose(1, 2) @ c["q"]).transpose(1, 2),
-                dv=(p.transpose(1, 2) @ c["do"]).transpose(1, 2))
 
 
 # measured worst case over the grid below (bf16 / fp16): o 1.8e-3 / 2.3e-4 relmax, lse 1.3e-7 / 1.3e-7 relmax,
