@@ -38,6 +38,8 @@ from . import clusters
 from .clusters import DroughtClusters, drought_clusters, label_components, structure_word
 from . import neighborhood
 from .neighborhood import FSSResult, drought_fss, fractions_skill_score, fss_cross_grid, neighborhood_fraction
+from . import biascorrect
+from .biascorrect import QuantileMap, series_quantiles
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

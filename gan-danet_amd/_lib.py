@@ -51,6 +51,11 @@ CCL_TRACK = ("count", "area", "severity", "sum_h", "sum_w", "min")   # GD_CCL_TR
 CCL_TOTALS = ("volume", "severity", "peak_area", "peak_area_step", "peak", "centroid_t", "centroid_h", "centroid_w")   # GD_CCL_TO_*
 NBR_MAX_HW, NBR_MAX_K, NBR_MAX_S = 1 << 20, 8, 32   # GD_NBR_MAX_HW, GD_NBR_MAX_K, GD_NBR_MAX_S
 NBR_NORMALIZE = {"window": 0, "valid": 1}            # GD_NBR_WINDOW, GD_NBR_VALID
+QM_MAX_T, QM_MAX_N, QM_MAX_Q, QM_MAX_PERIOD, QM_MAX_F, QM_SMALL_N = 2048, 2048, 256, 366, 16, 32   # GD_QM_MAX_*, GD_QM_SMALL_N
+QM_LAYOUT_QSM, QM_LAYOUT_SQM = 0, 1                  # GD_QM_LAYOUT_*
+QM_ROUTES = {"auto": 0, "small": 1, "long": 2}       # GD_QM_ROUTE_*
+QM_KINDS = {"eqm": 0, "qdm": 1}                      # GD_QM_EQM, GD_QM_QDM
+QM_EXTRAPOLATE = {"constant": 0, "clip": 1}          # GD_QM_CONSTANT, GD_QM_CLIP
 
 c_fp = C.c_void_p  # device pointers travel as integers
 
@@ -291,6 +296,10 @@ SIGNATURES = {
     "gd_nbr_fss_host": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p]),
     "gd_nbr_fraction": (_i, [_p, _i, _l, _l, _l, _p, _p, _i, _i, _i, _p, _p, _sz, _p]),
     "gd_nbr_fraction_host": (_i, [_p, _i, _l, _l, _l, _p, _p, _i, _i, _i, _p]),
+    "gd_qm_quantiles": (_i, [_p, _p, _i, _l, _l, _p, _i, _i, _i, _l, _l, _p, _i, _i, _i, _p, _p, _p]),
+    "gd_qm_quantiles_host": (_i, [_p, _p, _i, _l, _l, _p, _i, _i, _i, _l, _l, _p, _i, _i, _i, _p, _p]),
+    "gd_qm_apply": (_i, [_p, _i, _l, _l, _l, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "gd_qm_apply_host": (_i, [_p, _i, _l, _l, _l, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "gd_augment_d4": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _f, _p]),
     "gd_bcast_mul": (_i, [_p, _p, _p, _i, _i, _l, _i, _p]),
     "gd_row_dot": (_i, [_p, _p, _p, _l, _l, _p]),

@@ -129,11 +129,14 @@ def zoom_mask(mask: torch.Tensor, factor) -> torch.Tensor:
 @torch.no_grad()
 def assemble_product(res: torch.Tensor, trend25: torch.Tensor, scale: float, mean: float, *, trend_zoom=(1, 5, 5),
                      unit: float = 10.0, mask=None, bias=None, bias_zoom=(1, 1.25, 1.25), uncertainty=None,
-                     uncertainty_zoom=(1, 5, 5)) -> dict:
+                     uncertainty_zoom=(1, 5, 5), quantile_map=None, quantile_kind: str = "eqm") -> dict:
     """the post-loop chain of test.ipynb cell 3 on the device, from the stacked tiles ``res`` (T, H, W) to the product:
 
         trend_ups = zoom(trend25, trend_zoom, order=3)          res = res + trend_ups
         res_cm = scaler.inverse_transform(res) * unit           (scale, mean: the scaler's scale_ and mean_)
+        res_cm = quantile_map.apply(res_cm, quantile_kind)      (quantile_map given: a biascorrect.QuantileMap; not in
+                                                                 the notebook, whose only corrections are bias and the
+                                                                 global histogram match)
         res_cm[:, mask == 0] = nan                              (mask: (H, W), at product resolution)
         series = np.nanmean(res_cm, axis=(1, 2))
         product = res_cm + zoom(bias, bias_zoom, order=3)       (bias given)
@@ -146,7 +149,13 @@ def assemble_product(res: torch.Tensor, trend25: torch.Tensor, scale: float, mea
     if trend_ups.shape != res.shape:
         raise K.L.GandanetError(f"assemble_product: zoomed trend {tuple(trend_ups.shape)} vs tiles {tuple(res.shape)}")
     mask_u8 = None if mask is None else _mask_u8(mask, res.shape[-2:])
-    product = restore_units(res, trend_ups, scale, mean, unit, mask_u8)
+    if quantile_map is None:
+        product = restore_units(res, trend_ups, scale, mean, unit, mask_u8)
+    else:
+        product = restore_units(res, trend_ups, scale, mean, unit, None)
+        quantile_map.apply(product, kind=quantile_kind, out=product)         # one thread per element: in place is safe
+        if mask_u8 is not None:
+            product.masked_fill_(mask_u8 == 0, float("nan"))                 # plumbing: one ATen fill
     series, _ = K.masked_plane_mean_f64(product, mask_u8)
     if bias is not None:
         bias_ups = spline.zoom(bias, bias_zoom, order=3)

@@ -2975,3 +2975,192 @@ def nbr_fraction_host(x, thr, scale: int, below: bool = True, normalize: str = "
     L.check(lib().gd_nbr_fraction_host(x.ctypes.data, dt, T, H, W, _np_ptr(mask), th.ctypes.data, int(bool(below)), int(sc[0]),
                                        _nbr_normalize(normalize), out.ctypes.data), "gd_nbr_fraction_host")
     return out
+
+
+# ---- bias correction (include/gandanet.h, "Bias correction"; quantmap.hip) -----------------------------------------------------
+def qm_probs(q, fn: str, qmin: int = 1):
+    """the probabilities ``q`` (a number or a sequence, on the host) as a float64 numpy vector of ``qmin`` .. QM_MAX_Q entries
+    in [0, 1]"""
+    import numpy as np
+    try:
+        qa = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise L.GandanetError(f"{fn}: q is a sequence of numbers held on the host, got {type(q).__name__}") from None
+    if qa.ndim != 1 or not qmin <= qa.size <= L.QM_MAX_Q:
+        raise L.GandanetError(f"{fn}: q holds {qmin} .. {L.QM_MAX_Q} probabilities, got shape {qa.shape}")
+    if not bool(np.all((qa >= 0.0) & (qa <= 1.0))):
+        raise L.GandanetError(f"{fn}: every probability lies in [0, 1] (none is NaN), got {qa.tolist()}")
+    return np.ascontiguousarray(qa)
+
+
+def qm_nodes(n_quantiles: int):
+    """the node probabilities j / (Q - 1) of a quantile map of Q = ``n_quantiles`` nodes, a float64 numpy vector"""
+    import numpy as np
+    if isinstance(n_quantiles, bool) or not isinstance(n_quantiles, (int, np.integer)) or not 2 <= n_quantiles <= L.QM_MAX_Q:
+        raise L.GandanetError(f"quantile map: 2 <= n_quantiles <= {L.QM_MAX_Q}, got {n_quantiles!r}")
+    return np.arange(int(n_quantiles), dtype=np.float64) / float(int(n_quantiles) - 1)
+
+
+def _qm_calendar(fn: str, T: int, period, phase, b0, b1, min_samples) -> None:
+    """the limits of gd_qm_quantiles, each with a message of its own"""
+    if T > L.QM_MAX_T:
+        raise L.GandanetError(f"{fn}: T <= {L.QM_MAX_T}, got T = {T}")
+    if not 1 <= period <= L.QM_MAX_PERIOD:
+        raise L.GandanetError(f"{fn}: 1 <= period <= {L.QM_MAX_PERIOD}, got {period}")
+    if not 0 <= phase < period:
+        raise L.GandanetError(f"{fn}: 0 <= phase < period, got phase = {phase}, period = {period}")
+    if not 0 <= b0 < b1 <= T:
+        raise L.GandanetError(f"{fn}: the baseline is a half-open step range inside [0, {T}], got [{b0}, {b1})")
+    if -(-(b1 - b0) // period) > L.QM_MAX_N:
+        raise L.GandanetError(f"{fn}: at most {L.QM_MAX_N} baseline steps per slot, got {-(-(b1 - b0) // period)}")
+    if min_samples < 0:
+        raise L.GandanetError(f"{fn}: min_samples >= 0, got {min_samples}")
+
+
+def _qm_route(route) -> int:
+    if route not in L.QM_ROUTES:
+        raise L.GandanetError(f"quantile route: expected one of {tuple(L.QM_ROUTES)}, got {route!r}")
+    return L.QM_ROUTES[route]
+
+
+def qm_quantiles(x: Tensor, q, period: int = 1, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask: Optional[Tensor] = None,
+                 x2: Optional[Tensor] = None, min_samples: int = 1, layout: int = L.QM_LAYOUT_QSM, _route: str = "auto"):
+    """(nodes, n) of the M series of a dense fp32 / fp64 ``x`` (T, M): the quantiles at the probabilities ``q`` (a host
+    sequence, checked here, or an fp64 device vector the caller vouches for) of every calendar slot's baseline sample, fp64,
+    (Q, period, M) (QM_LAYOUT_QSM) or (period, Q, M) (QM_LAYOUT_SQM), and the sample sizes (period, M) int32.  ``x2``: a second
+    cube of the shape and dtype of ``x`` whose NaNs leave a step out as well.  ``_route`` ("auto", "small", "long") forces
+    one of the two sort kernels (for the tests: both give the same bits).  New tensors.  No host sync beyond the upload of
+    a host ``q``."""
+    dt = _series_2d(x, "qm_quantiles input")
+    T, M = x.shape
+    b1 = T if b1 is None else b1
+    period, phase, b0, b1, min_samples = int(period), int(phase), int(b0), int(b1), int(min_samples)
+    _qm_calendar("qm_quantiles", T, period, phase, b0, b1, min_samples)
+    if x2 is not None and (_series_2d(x2, "qm_quantiles second cube") != dt or x2.shape != x.shape):
+        raise L.GandanetError(f"qm_quantiles: the second cube is {tuple(x.shape)} {x.dtype} like the first, got {tuple(x2.shape)} {x2.dtype}")
+    if isinstance(q, Tensor):
+        qd = _dense(q, "qm_quantiles q", torch.float64).reshape(-1)
+        if not 1 <= qd.numel() <= L.QM_MAX_Q:
+            raise L.GandanetError(f"qm_quantiles: q holds 1 .. {L.QM_MAX_Q} probabilities, got {qd.numel()}")
+    else:
+        qd = torch.from_numpy(qm_probs(q, "qm_quantiles")).to(x.device)
+    Q = qd.numel()
+    if layout not in (L.QM_LAYOUT_QSM, L.QM_LAYOUT_SQM):
+        raise L.GandanetError(f"qm_quantiles: unknown layout {layout!r}")
+    route = _qm_route(_route)
+    if route == L.QM_ROUTES["small"] and -(-(b1 - b0) // period) > L.QM_SMALL_N:
+        raise L.GandanetError(f"qm_quantiles: the register route takes at most {L.QM_SMALL_N} baseline steps per slot")
+    quant = torch.empty((Q, period, M) if layout == L.QM_LAYOUT_QSM else (period, Q, M), device=x.device, dtype=torch.float64)
+    n = torch.empty((period, M), device=x.device, dtype=torch.int32)
+    L.check(lib().gd_qm_quantiles(_ptr(x), _ptr(x2), dt, T, M, _ptr(qd), Q, period, phase, b0, b1, _ptr(_eval_mask(mask, M)), min_samples,
+                                  layout, route, _ptr(quant), _ptr(n), _stream()), "gd_qm_quantiles")
+    return quant, n
+
+
+def _qm_tables(model_q, obs_q, fn: str, dev: bool):
+    for t, nm in ((model_q, "model_q"), (obs_q, "obs_q")):
+        if dev:
+            _dense(t, f"{fn} {nm}", torch.float64)
+        if t.ndim != 4 or tuple(t.shape) != tuple(model_q.shape):
+            raise L.GandanetError(f"{fn}: model_q and obs_q are (period, Q, H, W) float64 tables of one shape, got {nm} {tuple(t.shape)}")
+    period, Q, H, W = (int(v) for v in model_q.shape)
+    if not 1 <= period <= L.QM_MAX_PERIOD:
+        raise L.GandanetError(f"{fn}: 1 <= period <= {L.QM_MAX_PERIOD}, got {period}")
+    if not 2 <= Q <= L.QM_MAX_Q:
+        raise L.GandanetError(f"{fn}: 2 <= Q <= {L.QM_MAX_Q}, got {Q}")
+    if H == 0 or W == 0:
+        raise L.GandanetError(f"{fn}: empty table grid {(H, W)}")
+    return period, Q, H, W
+
+
+def _qm_factor(shape, H: int, W: int, fn: str) -> int:
+    """the integer 1 <= f <= QM_MAX_F with (Hx, Wx) = (f H, f W)"""
+    if len(shape) != 3 or 0 in tuple(shape):
+        raise L.GandanetError(f"{fn}: expected a non-empty (T, f H, f W) cube, got {tuple(shape)}")
+    f = shape[1] // H
+    if f < 1 or shape[1] != f * H or shape[2] != f * W:
+        raise L.GandanetError(f"{fn}: the cube's grid {tuple(shape[1:])} is not an integer multiple f of the table grid {(H, W)} on both axes")
+    if f > L.QM_MAX_F:
+        raise L.GandanetError(f"{fn}: f <= {L.QM_MAX_F}, got f = {f}")
+    return int(f)
+
+
+def _qm_codes(kind, extrapolate, phase, period, fn: str):
+    if kind not in L.QM_KINDS:
+        raise L.GandanetError(f"{fn}: kind is one of {tuple(L.QM_KINDS)}, got {kind!r}")
+    if extrapolate not in L.QM_EXTRAPOLATE:
+        raise L.GandanetError(f"{fn}: extrapolate is one of {tuple(L.QM_EXTRAPOLATE)}, got {extrapolate!r}")
+    if not 0 <= phase < period:
+        raise L.GandanetError(f"{fn}: 0 <= phase < period, got phase = {phase}, period = {period}")
+    return L.QM_KINDS[kind], L.QM_EXTRAPOLATE[extrapolate]
+
+
+def qm_apply(x: Tensor, model_q: Tensor, obs_q: Tensor, kind: str = "eqm", extrapolate: str = "constant", phase: int = 0,
+             own_q: Optional[Tensor] = None, p: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """the dense fp32 / fp64 cube ``x`` (T, f H, f W) mapped through the (period, Q, H, W) fp64 tables, in the dtype of ``x``;
+    step t uses slot (t + ``phase``) mod period.  ``"qdm"`` takes ``own_q`` (period, Q, f H, f W), the node table of ``x``
+    itself, and ``p``, the Q node probabilities on the device."""
+    dt = _filter_dtype(x, "qm_apply input")
+    period, Q, H, W = _qm_tables(model_q, obs_q, "qm_apply", True)
+    f = _qm_factor(x.shape, H, W, "qm_apply")
+    k, e = _qm_codes(kind, extrapolate, int(phase), period, "qm_apply")
+    if k == L.QM_KINDS["qdm"]:
+        if own_q is None or p is None:
+            raise L.GandanetError("qm_apply: 'qdm' needs own_q, the node table of x itself, and p, the node probabilities")
+        _dense(own_q, "qm_apply own_q", torch.float64)
+        if tuple(own_q.shape) != (period, Q) + tuple(x.shape[1:]):
+            raise L.GandanetError(f"qm_apply: own_q is {(period, Q) + tuple(x.shape[1:])}, got {tuple(own_q.shape)}")
+        _vec(p, Q, "qm_apply p")
+    else:
+        own_q = p = None
+    out = _out(out, x.shape, x, x.dtype, "qm_apply output")
+    L.check(lib().gd_qm_apply(_ptr(x), dt, x.shape[0], H, W, f, _ptr(model_q), _ptr(obs_q), _ptr(own_q), _ptr(p), Q, period, int(phase), k, e,
+                              _ptr(out), _stream()), "gd_qm_apply")
+    return out
+
+
+def qm_quantiles_host(x, q, period: int = 1, phase: int = 0, b0: int = 0, b1=None, mask=None, x2=None, min_samples: int = 1,
+                      layout: int = L.QM_LAYOUT_QSM, _route: str = "auto"):
+    """``qm_quantiles`` on HOST arrays (plain C++ loops over the same per-sample code, no GPU): (nodes, n)"""
+    import numpy as np
+    x, dt = _host_f(x, "qm_quantiles_host")
+    if x.ndim != 2:
+        raise L.GandanetError(f"qm_quantiles_host: expected a (T, M) array, got {x.shape}")
+    T, M = x.shape
+    b1 = T if b1 is None else b1
+    if x2 is not None:
+        x2, dt2 = _host_f(x2, "qm_quantiles_host second cube")
+        if dt2 != dt or x2.shape != x.shape:
+            raise L.GandanetError(f"qm_quantiles_host: the second cube is {x.shape} {x.dtype} like the first, got {x2.shape} {x2.dtype}")
+    qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+    Q, period = int(qa.size), int(period)
+    mask = _host_vec(mask, M, "qm_quantiles_host mask", "uint8")
+    quant = np.empty((Q, max(period, 0), M) if layout == L.QM_LAYOUT_QSM else (max(period, 0), Q, M))
+    n = np.empty((max(period, 0), M), dtype=np.int32)
+    L.check(lib().gd_qm_quantiles_host(x.ctypes.data, _np_ptr(x2), dt, T, M, qa.ctypes.data, Q, period, int(phase), int(b0), int(b1),
+                                       _np_ptr(mask), int(min_samples), int(layout), _qm_route(_route), quant.ctypes.data, n.ctypes.data),
+            "gd_qm_quantiles_host")
+    return quant, n
+
+
+def qm_apply_host(x, model_q, obs_q, kind: str = "eqm", extrapolate: str = "constant", phase: int = 0, own_q=None, p=None):
+    """``qm_apply`` on HOST arrays"""
+    import numpy as np
+    x, dt = _host_f(x, "qm_apply_host")
+    model_q, obs_q = (np.ascontiguousarray(t, dtype=np.float64) for t in (model_q, obs_q))
+    period, Q, H, W = _qm_tables(model_q, obs_q, "qm_apply_host", False)
+    f = _qm_factor(x.shape, H, W, "qm_apply_host")
+    k, e = _qm_codes(kind, extrapolate, int(phase), period, "qm_apply_host")
+    if k == L.QM_KINDS["qdm"]:
+        if own_q is None or p is None:
+            raise L.GandanetError("qm_apply_host: 'qdm' needs own_q and p")
+        own_q = np.ascontiguousarray(own_q, dtype=np.float64)
+        if own_q.shape != (period, Q) + x.shape[1:]:
+            raise L.GandanetError(f"qm_apply_host: own_q is {(period, Q) + x.shape[1:]}, got {own_q.shape}")
+        p = _host_vec(p, Q, "qm_apply_host p")
+    else:
+        own_q = p = None
+    out = np.empty_like(x)
+    L.check(lib().gd_qm_apply_host(x.ctypes.data, dt, x.shape[0], H, W, f, model_q.ctypes.data, obs_q.ctypes.data, _np_ptr(own_q), _np_ptr(p),
+                                   Q, period, int(phase), k, e, out.ctypes.data), "gd_qm_apply_host")
+    return out

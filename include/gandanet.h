@@ -1393,6 +1393,61 @@ int gd_nbr_fraction(const void* x, int dtype, long T, long H, long W, const unsi
 int gd_nbr_fraction_host(const void* x, int dtype, long T, long H, long W, const unsigned char* mask, const double* thr, int below,
                          int scale, int normalize, double* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Bias correction (quantmap.hip, csrc/quantmap_core.h): empirical quantile mapping per pixel and calendar slot, and its
+ * trend-preserving form, quantile delta mapping (Cannon et al. 2015, additive).
+ * x: a dense (T, M) cube, series m at x[t M + m], fp32 (dtype 0) or fp64 (dtype 1), 1 <= T <= GD_QM_MAX_T.  Step t belongs
+ * to slot s = (t + phase) mod period, 1 <= period <= GD_QM_MAX_PERIOD, 0 <= phase < period.  All arithmetic fp64, every
+ * operation rounded on its own (nothing is contracted into an FMA), nothing transcendental: the device entries, their
+ * *_host twins and numpy agree bit for bit.
+ *
+ * gd_qm_quantiles: the sample of (s, m) is the steps b0 <= t < b1 of slot s at which x[t, m] is not NaN (and, where x2 is
+ * given -- a second cube of the shape and dtype of x --, x2[t, m] is not NaN either); at most GD_QM_MAX_N steps per slot.
+ * n (period, M) ints: its size (0 for a pixel with mask[m] == 0; mask NULL or M bytes).  quant: Q <= GD_QM_MAX_Q doubles per
+ * (s, m), node j = numpy.nanquantile(sample, q[j]) with method "linear": v = (n - 1) q[j], i = floor(v), g = v - i, and
+ * i = i + 1 = n - 1, g = v + 1 where v >= n - 1; with a, b the i-th and (i + 1)-th smallest, d = b - a, the node is
+ * a + d g, or b - d (1 - g) where g >= 0.5 (numpy's _lerp).  NaN where n < max(min_samples, 1).  layout
+ * GD_QM_LAYOUT_QSM: node j of (s, m) at quant[(j period + s) M + m]; GD_QM_LAYOUT_SQM: at quant[(s Q + j) M + m].
+ * q: Q doubles in [0, 1], in DEVICE memory for the device entry (HOST memory for the twin).
+ * The samples are ordered by value with -0.0 below +0.0, so the result is a function of the sample alone.  route:
+ * GD_QM_ROUTE_AUTO takes the register route (one thread per (s, m), a sorting network over 16 or 32 registers) where no slot
+ * has more than GD_QM_SMALL_N baseline steps and the LDS route (one wave per (s, m), bitonic sort) otherwise;
+ * GD_QM_ROUTE_SMALL / GD_QM_ROUTE_LONG force one (SMALL is refused above GD_QM_SMALL_N steps per slot).  Both give the
+ * same bits.  No workspace, no atomics.
+ *
+ * gd_qm_apply: x (T, Hx, Wx) with Hx = f H, Wx = f W, 1 <= f <= GD_QM_MAX_F; model_q and obs_q (period, Q, H, W) doubles
+ * (GD_QM_LAYOUT_SQM), 2 <= Q <= GD_QM_MAX_Q.  Element (t, h, w) uses slot (t + phase) mod period of the tables of pixel
+ * (h / f, w / f).  out (T, Hx, Wx) in the dtype of x, rounded once.  A NaN x or a NaN first node gives NaN.
+ * GD_QM_EQM: inside [model_q[0], model_q[Q - 1]], numpy.interp(x, model_q, obs_q): j the last node with model_q[j] <= x;
+ * obs_q[j] where j = Q - 1 or model_q[j] == x; else s = (obs_q[j+1] - obs_q[j]) / (model_q[j+1] - model_q[j]) and
+ * s (x - model_q[j]) + obs_q[j].  Outside, with e the end node of that side: x + (obs_q[e] - model_q[e])
+ * (GD_QM_CONSTANT) or obs_q[e] (GD_QM_CLIP).
+ * GD_QM_QDM: own_q (period, Q, Hx, Wx) is the node table of x itself on its own grid (gd_qm_quantiles of x at the same
+ * period and phase, q = p); p: the Q node probabilities j / (Q - 1), DEVICE memory (HOST for the twin);
+ * tau = interp(x, own_q, p) and out = x + (interp(tau, p, obs_q) - interp(tau, p, model_q)).  own_q and p are not read
+ * for GD_QM_EQM.
+ * Every *_host twin takes the same arguments in HOST memory (no stream), makes no GPU call and runs the same per-sample
+ * code.  Every argument is checked before any launch (-1 and gd_last_error).
+ * ---------------------------------------------------------------------------------------- */
+#define GD_QM_MAX_T 2048
+#define GD_QM_MAX_N 2048
+#define GD_QM_MAX_Q 256
+#define GD_QM_MAX_PERIOD 366
+#define GD_QM_MAX_F 16
+#define GD_QM_SMALL_N 32
+enum { GD_QM_LAYOUT_QSM = 0, GD_QM_LAYOUT_SQM = 1 };
+enum { GD_QM_ROUTE_AUTO = 0, GD_QM_ROUTE_SMALL = 1, GD_QM_ROUTE_LONG = 2 };
+enum { GD_QM_EQM = 0, GD_QM_QDM = 1 };
+enum { GD_QM_CONSTANT = 0, GD_QM_CLIP = 1 };
+int gd_qm_quantiles(const void* x, const void* x2, int dtype, long T, long M, const double* q, int Q, int period, int phase, long b0,
+                    long b1, const unsigned char* mask, int min_samples, int layout, int route, double* quant, int* n, void* stream);
+int gd_qm_quantiles_host(const void* x, const void* x2, int dtype, long T, long M, const double* q, int Q, int period, int phase,
+                         long b0, long b1, const unsigned char* mask, int min_samples, int layout, int route, double* quant, int* n);
+int gd_qm_apply(const void* x, int dtype, long T, long H, long W, int f, const double* model_q, const double* obs_q,
+                const double* own_q, const double* p, int Q, int period, int phase, int kind, int extrapolate, void* out, void* stream);
+int gd_qm_apply_host(const void* x, int dtype, long T, long H, long W, int f, const double* model_q, const double* obs_q,
+                     const double* own_q, const double* p, int Q, int period, int phase, int kind, int extrapolate, void* out);
+
 #ifdef __cplusplus
 }
 #endif
