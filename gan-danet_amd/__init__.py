@@ -10,7 +10,7 @@ repo-root ``gan_danet_amd.py`` registers the package under that name -- or throu
 import paths ``from models import ...`` / ``from model import ...``.
 """
 from .config import config, layer_override, precision, set_precision, set_sync_bn
-from .kern import set_deterministic
+from .kern import set_deterministic, set_split_reduce
 from .attention import attention_report, cam_attention, pam_attention_rows, pam_attention_stats
 from .discriminator import SRGAND, Discriminator1
 from . import filters

@@ -99,6 +99,9 @@ SIGNATURES = {
     "gd_get_deterministic": (_i, []),
     "gd_set_det_reduce": (_i, [_i]),
     "gd_get_det_reduce": (_i, []),
+    "gd_set_split_reduce": (_i, [_i]),
+    "gd_get_split_reduce": (_i, []),
+    "gd_split_ws_bytes": (_sz, []),
     "gd_last_error": (_i, [C.c_char_p, _i]),
     "gd_sizeof_conv_desc": (_i, []),
     "gd_sizeof_gemm_nt_desc": (_i, []),

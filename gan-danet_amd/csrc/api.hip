@@ -49,3 +49,16 @@ extern "C" int gd_set_det_reduce(int mode) {
     return 0;
 }
 extern "C" int gd_get_det_reduce(void) { return g_det_reduce; }
+
+// How a split reduction combines its parts OUTSIDE deterministic mode: 0 = partial slabs in the library's own workspace
+// (gd_split_ws) + the ordered sum of det_reduce.hip, the default; 1 = fp32 atomics onto the zeroed output, what the
+// default used to be.  Discriminator1's stem gradient stays on atomics either way.  Process-global.
+namespace {
+int g_split_reduce = 0;
+}
+extern "C" int gd_set_split_reduce(int mode) {
+    GD_CHECK_ARG(mode == 0 || mode == 1, "gd_set_split_reduce: mode must be 0 (ordered slabs) or 1 (atomics)");
+    g_split_reduce = mode;
+    return 0;
+}
+extern "C" int gd_get_split_reduce(void) { return g_split_reduce; }

@@ -89,6 +89,17 @@ int gd_det_reduce_launch(const float* part, int splits, float* out, int B, int M
 int gd_det_reduce_stem_launch(const float* part, int splits, int Ci, int Co, float* dw, float* db, hipStream_t s);
 // true when a split reduction may use the ordered form with this workspace
 static inline bool gd_det_ordered(const void* ws) { return ws && gd_get_deterministic() && gd_get_det_reduce() == 1; }
+// Outside deterministic mode (api.hip): 0 = the default, partial slabs in the library's own workspace + the ordered sum;
+// 1 = fp32 atomics onto the zeroed output.
+extern "C" int gd_get_split_reduce(void);
+// true when a split reduction outside deterministic mode takes the slab form
+static inline bool gd_split_own() { return !gd_get_deterministic() && gd_get_split_reduce() == 0; }
+// det_reduce.hip: the library's slab workspace of the current device and this stream, grown to the largest request and
+// kept (16-byte aligned; NULL when the allocation fails).  Uses on one stream are stream-ordered; two streams never share.
+void* gd_split_ws(size_t bytes, hipStream_t s);
+// a default-mode reduction takes at most this many bytes of slabs; its split count is clamped to fit (as a caller's
+// workspace clamps the deterministic ordered form: 256 MiB is that mode's default too, so the two agree bit for bit)
+static const size_t GD_SPLIT_WS_CAP = (size_t)256 << 20;
 #define GD_CHECK_ARG(cond, msg)          \
     do {                                 \
         if (!(cond)) {                   \

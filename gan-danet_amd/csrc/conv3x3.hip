@@ -459,7 +459,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_nhwc_kernel(const NhwcConvArgs
                     }
                     *reinterpret_cast<uint2*>(scr + r * SLD + 8 * g + 4 * h) = hi;
                 }
-                // the wave's own LDS writes above are ordered before these reads (one wave: in-order DS queue)
+                // the wave's own LDS writes above are ordered before these reads (one wave: in-order DS queue); the wave
+                // barriers keep the compiler from moving a read above the writes, or the next round's writes above a read
+                __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int pass = 0; pass < 2; ++pass) {
                     const int px = pass * 16 + (lane >> 2), c8 = (lane & 3) * 8;
@@ -474,6 +476,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_nhwc_kernel(const NhwcConvArgs
                         }
                     }
                 }
+                __builtin_amdgcn_wave_barrier();
             }
         }
         return;
@@ -1124,9 +1127,9 @@ __global__ __launch_bounds__(NW * 64, PIPED ? GD_WGRAD_PIPED_MINW : 2) void conv
 // by gd_conv3x3_wgrad_plan and the launcher so that the two cannot drift.
 namespace {
 struct WgradPlan {
-    int best_nw, cs, groups, cs_nw, mblocks, tiles_x, tiles_y, Ho, Wo, tiles_per_split, splits, ordered;
+    int best_nw, cs, groups, cs_nw, mblocks, tiles_x, tiles_y, Ho, Wo, tiles_per_split, splits, ordered, own;
     long ntiles;
-    size_t ws_needed;
+    size_t ws_needed;                // of the CALLER's workspace: 0 when the slabs live in the library's own (own = 1)
 };
 int wgrad_plan(int B, int Cout, int Cin, int H, int W, int stride, size_t ws_bytes, WgradPlan* p) {
     GD_CHECK_ARG(B > 0 && Cout > 0 && Cin > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "gd_conv3x3_wgrad: bad sizes");
@@ -1153,7 +1156,9 @@ int wgrad_plan(int B, int Cout, int Cin, int H, int W, int stride, size_t ws_byt
     const int bm = cs ? 32 : 32 * best_nw;
     const int mblocks = (Cout + bm - 1) / bm;
     p->best_nw = best_nw; p->cs = cs; p->groups = groups; p->cs_nw = cs_nw; p->mblocks = mblocks;
-    const bool det = gd_get_deterministic() != 0, ordered_mode = det && gd_get_det_reduce() == 1;
+    // slabs + ordered sum: the default (in the library's workspace) and the deterministic "ordered" form (in the caller's)
+    const bool det = gd_get_deterministic() != 0, own = gd_split_own(), ordered_mode = own || (det && gd_get_det_reduce() == 1);
+    if (own) ws_bytes = GD_SPLIT_WS_CAP;
     long splits = 1024 / ((long)mblocks * groups);
     if (splits < 1 || (det && !ordered_mode)) splits = 1;    // deterministic, unsplit: one adder per dW element
     if (splits > ntiles) splits = ntiles;
@@ -1168,7 +1173,8 @@ int wgrad_plan(int B, int Cout, int Cin, int H, int W, int stride, size_t ws_byt
     splits = (ntiles + p->tiles_per_split - 1) / p->tiles_per_split;
     p->splits = (int)splits;
     p->ordered = ordered_mode && splits > 1;
-    p->ws_needed = p->ordered ? (size_t)splits * out_bytes : 0;
+    p->own = own && p->ordered;
+    p->ws_needed = p->ordered && !own ? (size_t)splits * out_bytes : 0;
     return 0;
 }
 }  // namespace
@@ -1183,7 +1189,9 @@ extern "C" int gd_conv3x3_wgrad_plan(int B, int Cout, int Cin, int H, int W, int
 }
 
 // dw (Cout, Cin, 3, 3) fp32 is overwritten (accumulate = 0) or added to.  Same input-transform contract as gd_conv2d.
-// ws / ws_bytes: caller-owned scratch for the ordered deterministic mode (NULL: never used).
+// ws / ws_bytes: caller-owned scratch for the ordered deterministic mode (NULL: never used).  Outside deterministic mode
+// the pixel splits write partial slabs into the library's own workspace and det_reduce.hip sums them in order (the
+// default), or add into dw with fp32 atomics (gd_set_split_reduce(1)).
 extern "C" int gd_conv3x3_wgrad_ws(const float* dy, long dy_bs, const void* dy_bf16, const float* x, long x_bs,
                                    const void* x_nhwc16, int x_ld, const float* in_scale, const float* in_shift, int in_relu,
                                    int B, int Cout, int Cin, int H, int W, int stride, int accumulate, float* dw, void* stream,
@@ -1196,8 +1204,12 @@ extern "C" int gd_conv3x3_wgrad_ws(const float* dy, long dy_bs, const void* dy_b
     WgradPlan p;
     if (wgrad_plan(B, Cout, Cin, H, W, stride, ws ? ws_bytes : 0, &p)) return -1;
     hipStream_t s = (hipStream_t)stream;
+    if (p.own) {
+        ws = gd_split_ws((size_t)p.splits * Cout * Cin * 9 * sizeof(float), s);
+        GD_CHECK_ARG(ws != nullptr, "gd_conv3x3_wgrad: no memory for the partial slabs");
+    }
     // atomic path: the pixel splits add into dw with fp32 atomics: it starts from zero, or (accumulate) from what it
-    // holds.  The ordered path overwrites its slabs and the reduce kernel writes dw.
+    // holds.  The ordered path overwrites its slabs and the reduce kernel writes dw without reading it (accumulate: adds).
     if (!accumulate && !p.ordered)
         GD_CHECK_ARG(hipMemsetAsync(dw, 0, (size_t)Cout * Cin * 9 * sizeof(float), s) == hipSuccess, "gd_conv3x3_wgrad: memset failed");
     WgradArgs a;

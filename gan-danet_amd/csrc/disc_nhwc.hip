@@ -314,7 +314,13 @@ extern "C" int gd_nhwc_to_nchw16_ws(const void* g, int B, int HW, int C, void* g
     // part's slabs follow the hi part's), as many as fit
     float* part = nullptr;
     const int launches = split ? 2 : 1;
-    if (csum && gd_det_ordered(ws)) {
+    // outside deterministic mode the slabs live in the library's own workspace (the default; gd_set_split_reduce(1): atomics)
+    if (csum && gy > 1 && gd_split_own()) {
+        ws_bytes = (size_t)gy * C * sizeof(float) * launches;
+        ws = gd_split_ws(ws_bytes, NS(stream));
+        GD_CHECK_ARG(ws != nullptr, "gd_nhwc_to_nchw16: no memory for the partial slabs");
+    }
+    if (csum && (gd_det_ordered(ws) || (ws && gd_split_own()))) {
         const size_t fit = ws_bytes / ((size_t)C * sizeof(float) * launches);
         if ((size_t)gy > fit) gy = (long)fit;
         if (gy < 2) gy = 1;         // one adder per channel and launch: the atomic path is already ordered

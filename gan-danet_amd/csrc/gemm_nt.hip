@@ -5,9 +5,10 @@
 // fragments want.  k = (segment s, offset kk): a segment is one image of the batch, which is how the
 // convolution weight gradient (k = output pixels of all images), CAM's Gram matrix, nn.Linear forward
 // and the unfused fp32 PAM products all map onto one kernel.  The reduction is split over
-// blockIdx.z; partial tiles are combined with fp32 atomics (hardware global_atomic_add_f32), or -- ordered
-// deterministic mode -- written as alpha * acc into a dense [split][B][M][N] slab of the caller's workspace that
-// det_reduce.hip sums in ascending split order (adding the bias once, honouring c_bs / ldc / accumulate).
+// blockIdx.z; partial tiles are written as alpha * acc into a dense [split][B][M][N] slab -- of the library's own
+// workspace by default, of the caller's in ordered deterministic mode -- that det_reduce.hip sums in ascending split
+// order (adding the bias once, honouring c_bs / ldc / accumulate), or, gd_set_split_reduce(1), combined with fp32 atomics
+// (hardware global_atomic_add_f32).
 #include "common.h"
 #include "tile_mma.h"
 #include "../../include/gandanet.h"
@@ -327,7 +328,7 @@ int launch(const gd_gemm_nt_desc& d, int ktiles, int tps, int splits, float* par
 
 // Split count of a descriptor: a pure function of the sizes, the deterministic mode and the workspace size, shared by
 // gd_gemm_nt_plan and the launcher so that the two cannot drift.
-struct NtPlan { int ktiles, bm, tiles_per_split, splits, ordered; size_t ws_needed; };
+struct NtPlan { int ktiles, bm, tiles_per_split, splits, ordered, own; size_t ws_needed; };   // ws_needed: of the CALLER's workspace
 int nt_plan(const gd_gemm_nt_desc& d, size_t ws_bytes, NtPlan* p) {
     GD_CHECK_ARG(d.B > 0 && d.M > 0 && d.N > 0 && d.kseg > 0 && d.klen > 0, "gd_gemm_nt: bad sizes");
     GD_CHECK_ARG((long)d.kseg * d.klen < (1L << 31), "gd_gemm_nt: reduction too long");
@@ -353,8 +354,10 @@ int nt_plan(const gd_gemm_nt_desc& d, size_t ws_bytes, NtPlan* p) {
         if (splits > ktiles / 8) splits = ktiles / 8 > 0 ? ktiles / 8 : 1;
     }
     if (splits > ktiles) splits = ktiles;
-    const bool det = gd_get_deterministic() != 0, ordered_mode = det && gd_get_det_reduce() == 1;
-    if (det && !ordered_mode) splits = 1;                    // deterministic, unsplit: no atomic combine of k-splits
+    // slabs + ordered sum: the default (in the library's workspace) and the deterministic "ordered" form (in the caller's)
+    const bool det = gd_get_deterministic() != 0, own = gd_split_own(), ordered_mode = own || (det && gd_get_det_reduce() == 1);
+    if (own) ws_bytes = GD_SPLIT_WS_CAP;
+    if (det && !ordered_mode) splits = 1;                   // deterministic, unsplit: no atomic combine of k-splits
     if ((long)d.B * splits > 65535) splits = (int)(65535 / d.B);
     const size_t out_bytes = (size_t)d.B * d.M * d.N * sizeof(float);
     if (ordered_mode) {                                      // ordered: one dense slab per split must fit the workspace
@@ -366,7 +369,8 @@ int nt_plan(const gd_gemm_nt_desc& d, size_t ws_bytes, NtPlan* p) {
     splits = (ktiles + tps - 1) / tps;                       // no empty splits
     p->ktiles = ktiles; p->bm = bm; p->tiles_per_split = tps; p->splits = splits;
     p->ordered = ordered_mode && splits > 1;
-    p->ws_needed = p->ordered ? (size_t)splits * out_bytes : 0;
+    p->own = own && p->ordered;
+    p->ws_needed = p->ordered && !own ? (size_t)splits * out_bytes : 0;
     return 0;
 }
 
@@ -388,8 +392,12 @@ extern "C" int gd_gemm_nt_ws(const gd_gemm_nt_desc* dp, void* stream, void* ws, 
     GD_CHECK_ARG(((uintptr_t)ws % 16) == 0, "gd_gemm_nt: the workspace must be 16-byte aligned");
     NtPlan p;
     if (nt_plan(d, ws ? ws_bytes : 0, &p)) return -1;
-    float* part = p.ordered ? (float*)ws : nullptr;
     hipStream_t s = (hipStream_t)stream;
+    if (p.own) {
+        ws = gd_split_ws((size_t)p.splits * d.B * d.M * d.N * sizeof(float), s);
+        GD_CHECK_ARG(ws != nullptr, "gd_gemm_nt: no memory for the partial slabs");
+    }
+    float* part = p.ordered ? (float*)ws : nullptr;
     if (p.bm == 32) return launch<32>(d, p.ktiles, p.tiles_per_split, p.splits, part, s);
     if (p.bm == 64) return launch<64>(d, p.ktiles, p.tiles_per_split, p.splits, part, s);
     return launch<128>(d, p.ktiles, p.tiles_per_split, p.splits, part, s);

@@ -217,7 +217,7 @@ def conv2d_wgrad(dy: Tensor, x: Tensor, k: int, stride: int, pad: int, precision
                  in_shift=None, in_relu=False, alpha: Optional[Tensor] = None, splits: int = 0) -> Tensor:
     """Gradient of nn.Conv2d w.r.t. its OIHW weight: dW[co][ci,kh,kw] = sum_{b,p} dy[b,co,p] x~[b,ci,p(+)tap].
     ``alpha`` (1x1 convs only): device scalar multiplying the result; ``splits`` (1x1 convs only): k-splits of the GEMM
-    (0 = chosen by the kernel and combined with atomics, 1 = unsplit: bitwise reproducible)."""
+    (0 = chosen by the kernel and combined as set_split_reduce says, 1 = unsplit)."""
     if alpha is not None and not (k == 1 and stride == 1 and pad == 0):
         raise L.GandanetError("conv2d_wgrad: alpha is supported for 1x1 convs only")
     dbs, xbs = _bview(dy, "wgrad dy"), _bview(x, "wgrad x")
@@ -854,6 +854,27 @@ def set_deterministic(on: bool, reduce: Optional[str] = None) -> None:
     if reduce is not None:
         L.check(lib().gd_set_det_reduce(_DET_REDUCE_MODES[reduce]), "gd_set_det_reduce")
         DET_REDUCE = reduce
+
+
+SPLIT_REDUCE = "ordered"          # how a split reduction combines its parts outside deterministic mode (gd_set_split_reduce)
+_SPLIT_REDUCE_MODES = {"ordered": 0, "atomic": 1}
+
+
+def set_split_reduce(mode: str) -> None:
+    """how the split reductions outside PAM (3x3 and 1x1 weight gradients, split-K GEMMs, the D trunk's bias sums) combine
+    their parts when deterministic mode is off: "ordered" -- the default: every split stores a partial slab into a
+    workspace the library owns and a sum kernel adds the slabs in ascending order, bitwise reproducible, the output neither
+    zeroed nor read -- or "atomic": fp32 atomics onto the zeroed output."""
+    global SPLIT_REDUCE
+    if mode not in _SPLIT_REDUCE_MODES:
+        raise L.GandanetError(f"set_split_reduce: mode must be one of {sorted(_SPLIT_REDUCE_MODES)}, got {mode!r}")
+    L.check(lib().gd_set_split_reduce(_SPLIT_REDUCE_MODES[mode]), "gd_set_split_reduce")
+    SPLIT_REDUCE = mode
+
+
+def split_ws_bytes() -> int:
+    """bytes of partial-slab workspace the library holds for the default mode (hipMalloc: not in torch's statistics)"""
+    return int(lib().gd_split_ws_bytes())
 
 
 def det_ws_bytes() -> int:

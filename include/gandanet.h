@@ -42,6 +42,16 @@ int gd_get_deterministic(void);
  * gd_set_det_reduce returns 0, or -1 for any other mode. */
 int gd_set_det_reduce(int mode);
 int gd_get_det_reduce(void);
+/* how a split reduction combines its parts OUTSIDE deterministic mode (process-global):
+ *   0 = ordered slabs (the default): the same partial slabs and ascending sum as above, in a workspace the library owns
+ *       (one hipMalloc per device and stream, grown to the largest request, at most 256 MiB per request, kept); the output
+ *       is not zeroed and not read unless the call accumulates; a caller's ws is not touched;
+ *   1 = atomics: the parts are added with fp32 atomics onto the zeroed output (order-dependent rounding).
+ * Discriminator1's stem gradient (gd_disc_stem_wgrad) uses atomics in both.  Returns 0, or -1 for any other mode. */
+int gd_set_split_reduce(int mode);
+int gd_get_split_reduce(void);
+/* bytes of slab workspace the library currently holds (all devices and streams) */
+size_t gd_split_ws_bytes(void);
 int gd_version(void);
 /* copies the calling thread's last error message (NUL terminated) into buf; returns its length */
 int gd_last_error(char* buf, int n);
