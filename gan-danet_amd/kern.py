@@ -8,10 +8,12 @@ CPU tensors are rejected -- there is no fallback path.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1348,15 +1350,16 @@ def nhwc_l1_grad(a: Tensor, b: Tensor, upstream: Tensor, relu_mask: bool, split:
 
 
 # ---- evaluation (evalstats.hip) ----------------------------------------------------------------------------------------
-def _filter_dtype(t: Tensor, name: str) -> int:
-    """fp32 -> GD_FILTER_F32, fp64 -> GD_FILTER_F64 for a dense GPU tensor; the tag of every analysis entry point"""
-    if not t.is_cuda:
+def _filter_dtype(t: Tensor, name: str, u8: bool = False) -> int:
+    """fp32 -> GD_FILTER_F32, fp64 -> GD_FILTER_F64 (with ``u8``: uint8 -> GD_CCL_U8) for a dense GPU tensor; the tag of every
+    analysis entry point"""
+    if not isinstance(t, Tensor) or not t.is_cuda:
         raise L.GandanetError(f"{name}: expected a GPU tensor (there is no CPU fallback in the product path)")
-    if t.dtype not in (torch.float32, torch.float64):
-        raise L.GandanetError(f"{name}: expected float32 or float64, got {t.dtype}")
+    if t.dtype not in (torch.float32, torch.float64) and not (u8 and t.dtype == torch.uint8):
+        raise L.GandanetError(f"{name}: expected float32{', ' if u8 else ' or '}float64{' or uint8' if u8 else ''}, got {t.dtype}")
     if not t.is_contiguous():
         raise L.GandanetError(f"{name}: expected a contiguous tensor, got strides {t.stride()}")
-    return int(t.dtype == torch.float64)
+    return _Dev.tags[t.dtype]
 
 
 def _out_dtype(out_dtype, src: Tensor, fn: str):
@@ -1371,15 +1374,6 @@ def _plane_chunks(planes: int):
     """(lo, k): the planes [lo, lo + k) of one launch, at most 65535 (the grid.y limit)"""
     for lo in range(0, planes, 65535):
         yield lo, min(65535, planes - lo)
-
-
-def _eval_mask(mask: Optional[Tensor], hw: int) -> Optional[Tensor]:
-    if mask is None:
-        return None
-    _chk(mask, "mask", torch.uint8)
-    if not mask.is_contiguous() or mask.numel() != hw:
-        raise L.GandanetError(f"mask: expected {hw} contiguous uint8 entries (one per pixel of a plane), got {tuple(mask.shape)}")
-    return mask
 
 
 def eval_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] = None, affine=None,
@@ -1397,7 +1391,7 @@ def eval_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] 
     hw = n if mask is None else mask.numel()
     if hw <= 0 or n % hw:
         raise L.GandanetError(f"eval_stats: a mask of {hw} entries does not tile {tuple(pred.shape)}")
-    mask = _eval_mask(mask, hw)
+    mask = _DEV.vec(mask, hw, "mask", torch.uint8)
     a, b = (1.0, 0.0) if affine is None else (float(affine[0]), float(affine[1]))
     nbytes = int(lib().gd_eval_stats_ws_bytes(n))
     ws = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
@@ -1413,7 +1407,7 @@ def _plane_mean(x: Tensor, mask: Optional[Tensor], plane_dims: int, dtype) -> Tu
     launch, ws_bytes = getattr(lib(), fn), getattr(lib(), fn + "_ws_bytes")
     lead = tuple(x.shape[:x.dim() - plane_dims])
     hw = math.prod(x.shape[x.dim() - plane_dims:])
-    mask = _eval_mask(mask, hw)
+    mask = _DEV.vec(mask, hw, "mask", torch.uint8)
     mean = torch.empty(lead, device=x.device, dtype=torch.float64)
     count = torch.empty(lead, device=x.device, dtype=torch.int64)
     for lo, k in _plane_chunks(math.prod(lead)):
@@ -1457,7 +1451,6 @@ def ensemble_stats(x: Tensor, mean: Optional[Tensor] = None, std: Optional[Tenso
 
 def eval_merge_host(records) -> Tuple[list, dict]:
     """merge (k, 8) host records in the given order (plain C++ on the host, no GPU): (merged record, metrics dict)"""
-    import numpy as np
     recs = np.ascontiguousarray(np.asarray(records, dtype=np.float64).reshape(-1, 8))
     out, met = (C.c_double * 8)(), (C.c_double * 4)()
     ptr = recs.ctypes.data_as(C.POINTER(C.c_double)) if len(recs) else None
@@ -1638,7 +1631,7 @@ def restore_units(x: Tensor, trend: Optional[Tensor], mask: Optional[Tensor], sc
     hw = n
     if mask is not None:
         hw = mask.numel()
-        _eval_mask(mask, hw)
+        _DEV.vec(mask, hw, "mask", torch.uint8)
         if hw == 0 or n % hw or tuple(x.shape[x.dim() - mask.dim():]) != tuple(mask.shape):
             raise L.GandanetError(f"restore_units: mask {tuple(mask.shape)} does not cover the trailing dims of {tuple(x.shape)}")
     L.check(lib().gd_restore_units(_ptr(x), xdt, _ptr(trend), tdt, _ptr(mask), n // hw, hw, float(scale), float(mean),
@@ -1664,7 +1657,6 @@ def channel_moments(x: Tensor, channels: int) -> Tensor:
 
 def scale_from_moments_host(rec):
     """sklearn's (mean_, var_, scale_) as fp64 numpy arrays from a (C, 3) HOST array of records (plain C++, no GPU)"""
-    import numpy as np
     rec = np.ascontiguousarray(rec, dtype=np.float64)
     if rec.ndim != 2 or rec.shape[1] != 3:
         raise L.GandanetError(f"scale_from_moments_host: expected (C, 3) records, got {rec.shape}")
@@ -1705,7 +1697,6 @@ def channel_affine(src: Tensor, mean: Tensor, scale: Tensor, inverse: bool = Fal
 
 def freq_cos_table_host(n: int, k1: int):
     """the (k1, n) fp64 numpy table cos(2 pi ((k t) mod n) / n) / n (plain C++ on the host, no GPU)"""
-    import numpy as np
     if n <= 0 or k1 < 1:
         raise L.GandanetError(f"freq_cos_table_host: L = {n}, K1 = {k1}")
     coef = np.empty((k1, n))
@@ -1734,7 +1725,6 @@ def freq_augment_axis(src: Tensor, dst: Tensor, axis: int, noise: Tensor, coef: 
 
 # ---- basin analysis (include/gandanet.h, "Basin analysis"; basins.hip) -------------------------------------------------------
 def _zone_edges_host(edges, offsets):
-    import numpy as np
     edges = np.ascontiguousarray(edges, dtype=np.float64)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     if edges.ndim != 2 or edges.shape[1] != 4 or offsets.ndim != 1 or offsets.size < 2:
@@ -1746,7 +1736,6 @@ def zone_rasterize(edges: Tensor, offsets, xs: Tensor, ys: Tensor, out: Optional
     """(H, W) uint32 words, bit z set where the grid point (xs[j], ys[i]) lies in zone z: ``edges`` (E, 4) fp64 on the
     device, ``offsets`` Z + 1 host integers (1 <= Z <= 32), ``xs`` (W) and ``ys`` (H) fp64 on the device.  Every word of
     ``out`` is written.  No host sync."""
-    import numpy as np
     for t, nm in ((edges, "zone edges"), (xs, "zone grid xs"), (ys, "zone grid ys")):
         _dense(t, nm, torch.float64)
     if edges.dim() != 2 or edges.shape[1] != 4 or xs.dim() != 1 or ys.dim() != 1:
@@ -1765,7 +1754,6 @@ def zone_rasterize(edges: Tensor, offsets, xs: Tensor, ys: Tensor, out: Optional
 
 def zone_rasterize_host(edges, offsets, xs, ys):
     """``zone_rasterize`` on HOST arrays (plain C++ loops over the same predicate, no GPU): an (H, W) uint32 numpy array"""
-    import numpy as np
     edges, off = _zone_edges_host(edges, offsets)
     xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1)
     ys = np.ascontiguousarray(ys, dtype=np.float64).reshape(-1)
@@ -1809,32 +1797,123 @@ def zone_mean(x: Tensor, bits: Tensor, zones: int, weights: Optional[Tensor] = N
     return mean, count
 
 
-# ---- argument helpers of the analysis wrappers below (stl .. drought) ----------------------------------------------------------
-def _vec(t: Optional[Tensor], n: int, name: str, dtype=torch.float64) -> Optional[Tensor]:
-    """an optional dense device vector of ``n`` entries (any shape) of ``dtype``"""
-    if t is None:
-        return None
-    _dense(t, name, dtype)
-    if t.numel() != n:
-        raise L.GandanetError(f"{name}: expected {n} entries, got {tuple(t.shape)}")
-    return t
+# ---- the two argument backends of the analysis wrappers below (stl .. bias correction) -----------------------------------------
+# Every wrapper below that has a host twin is written once, over one of these: _DEV for GPU tensors (enqueues on torch's
+# current stream) and _HOST for numpy arrays (calls the gd_*_host twin, plain C++).  The device side refuses what is not a
+# dense GPU tensor; the host side converts lists and strided arrays first.  Where a twin has never made a check that the
+# other makes, the body says so with ``be.host``.
+class _Dev:
+    host = False
+    f32, f64, u8, i32 = torch.float32, torch.float64, torch.uint8, torch.int32
+    tags = {torch.float32: L.FILTER_F32, torch.float64: L.FILTER_F64, torch.uint8: L.CCL_U8}
+
+    @staticmethod
+    def array(x, name: str, ndim: Optional[int] = None, u8: bool = False):
+        """(x, dtype tag) of the main array: a dense, non-empty fp32 / fp64 (``u8``: or uint8) GPU tensor of ``ndim`` dims"""
+        tag = _filter_dtype(x, name, u8)
+        if x.numel() == 0 or (ndim is not None and x.dim() != ndim):
+            raise L.GandanetError(f"{name}: expected a dense, non-empty {'' if ndim is None else f'{ndim}-D '}tensor, got {tuple(x.shape)}")
+        return x, tag
+
+    @staticmethod
+    def dense(x, name: str, dtype):
+        return _dense(x, name, dtype)
+
+    @staticmethod
+    def vec(x, n: Optional[int], name: str, dtype=torch.float64):
+        """an optional dense device vector of ``n`` entries (any shape; None: any number) of ``dtype``"""
+        if x is None:
+            return None
+        _dense(x, name, dtype)
+        if n is not None and x.numel() != n:
+            raise L.GandanetError(f"{name}: expected {n} entries, got {tuple(x.shape)}")
+        return x
+
+    @staticmethod
+    def empty(shape, dtype, like):
+        return torch.empty(tuple(shape), device=like.device, dtype=dtype)
+
+    @staticmethod
+    def out(out, shape, dtype, like, name: str):
+        """the dense output of ``shape`` and ``dtype``: ``out`` when one is given, else a new tensor on the device of ``like``"""
+        if out is None:
+            return torch.empty(tuple(shape), device=like.device, dtype=dtype)
+        _dense(out, name, dtype)
+        if tuple(out.shape) != tuple(shape):
+            raise L.GandanetError(f"{name}: expected a dense {tuple(shape)} {dtype} tensor, got {tuple(out.shape)}")
+        return out
+
+    @staticmethod
+    def ws(ws, nbytes: int, like, name: str):
+        """the (pointer, bytes) arguments of the dense uint8 workspace: ``ws`` when one is given (the C entry checks its size),
+        else a new one of ``nbytes``"""
+        if ws is None:
+            ws = torch.empty(max(int(nbytes), 8), device=like.device, dtype=torch.uint8)
+        return _dense(ws, name + " workspace", torch.uint8).data_ptr(), ws.numel()
+
+    ptr = staticmethod(_ptr)
+
+    @staticmethod
+    def call(fn: str, *args) -> None:
+        L.check(getattr(lib(), fn)(*args, _stream()), fn)
 
 
-def _out(out: Optional[Tensor], shape, like: Tensor, dtype, name: str) -> Tensor:
-    """the dense output of ``shape`` and ``dtype``: ``out`` when one is given, else a new tensor on the device of ``like``"""
-    if out is None:
-        return torch.empty(shape, device=like.device, dtype=dtype)
-    _dense(out, name, dtype)
-    if tuple(out.shape) != tuple(shape):
-        raise L.GandanetError(f"{name}: expected a dense {tuple(shape)} {dtype} tensor, got {tuple(out.shape)}")
-    return out
+class _Host:
+    host = True
+    f32, f64, u8, i32 = np.float32, np.float64, np.uint8, np.int32
+    tags = {"float32": L.FILTER_F32, "float64": L.FILTER_F64, "uint8": L.CCL_U8}
+
+    @staticmethod
+    def array(x, name: str, ndim: Optional[int] = None, u8: bool = False):
+        """(x, dtype tag) of the main array: a contiguous copy unless it is one, non-empty, fp32 / fp64 (``u8``: or uint8), of
+        ``ndim`` dims"""
+        x = np.asarray(x)
+        if x.dtype.name not in _Host.tags or (x.dtype == np.uint8 and not u8) or x.size == 0 or (ndim is not None and x.ndim != ndim):
+            raise L.GandanetError(f"{name}: expected a non-empty float32 / float64{' / uint8' if u8 else ''} array"
+                                  f"{'' if ndim is None else f' of {ndim} dims'}, got {x.dtype} {x.shape}")
+        return np.ascontiguousarray(x), _Host.tags[x.dtype.name]
+
+    @staticmethod
+    def dense(x, name: str, dtype):
+        return np.ascontiguousarray(x, dtype=dtype)
+
+    @staticmethod
+    def vec(x, n: Optional[int], name: str, dtype=np.float64):
+        """an optional flat HOST vector: None, or a contiguous 1-D ``dtype`` array, of ``n`` entries where ``n`` is given"""
+        if x is None:
+            return None
+        x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+        if n is not None and x.size != n:
+            raise L.GandanetError(f"{name}: expected {n} entries, got {x.size}")
+        return x
+
+    @staticmethod
+    def empty(shape, dtype, like=None):
+        return np.empty(tuple(shape), dtype=dtype)
+
+    @staticmethod
+    def out(out, shape, dtype, like, name: str):
+        """a new array; the host twins that take an ``out`` write into a C-contiguous array of ``shape`` and ``dtype``"""
+        if out is None:
+            return np.empty(tuple(shape), dtype=dtype)
+        if not isinstance(out, np.ndarray) or out.dtype != dtype or out.shape != tuple(shape) or not out.flags["C_CONTIGUOUS"]:
+            raise L.GandanetError(f"{name}: expected a contiguous {tuple(shape)} {np.dtype(dtype)} array")
+        return out
+
+    @staticmethod
+    def ws(ws, nbytes: int, like, name: str):
+        return ()                                                      # the host twins take no workspace
+
+    @staticmethod
+    def ptr(x):
+        return None if x is None else x.ctypes.data
+
+    @staticmethod
+    def call(fn: str, *args) -> None:
+        L.check(getattr(lib(), fn + "_host")(*args), fn + "_host")
 
 
-def _ws(ws: Optional[Tensor], nbytes: int, like: Tensor, name: str) -> Tensor:
-    """the dense uint8 workspace: ``ws`` when one is given (the C entry checks its size), else a new one of ``nbytes``"""
-    if ws is None:
-        ws = torch.empty(max(nbytes, 8), device=like.device, dtype=torch.uint8)
-    return _dense(ws, name + " workspace", torch.uint8)
+_DEV, _HOST = _Dev, _Host
 
 
 def _which(names, table, what: str) -> int:
@@ -1854,52 +1933,24 @@ def _which_names(which: int, table) -> list:
     return [nm for k, nm in enumerate(table) if which >> k & 1]
 
 
-def _np_ptr(a):
-    return None if a is None else a.ctypes.data
-
-
-def _host_vec(a, n: Optional[int], name: str, dtype="float64"):
-    """an optional flat HOST vector: None, or a contiguous 1-D ``dtype`` array, of ``n`` entries where ``n`` is given"""
-    import numpy as np
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
-    if n is not None and a.size != n:
-        raise L.GandanetError(f"{name}: expected {n} entries, got {a.size}")
-    return a
-
-
 # ---- STL decomposition (include/gandanet.h, "STL decomposition"; stl.hip) ------------------------------------------------------
 def _stl_args(p: dict):
     return [int(p[k]) for k in ("period", "seasonal", "trend", "low_pass", "seasonal_deg", "trend_deg", "low_pass_deg", "inner_iter",
                                 "outer_iter")]
 
 
-def stl_decompose(x: Tensor, p: dict, want_weights: bool = True):
+def _stl_decompose(be, x, p: dict, want_weights: bool = True):
     """STL of the M series of a dense fp32 / fp64 ``x`` (T, M), series m at ``x[:, m]``; ``p`` holds period, seasonal, trend,
     low_pass, the three degrees, inner_iter and outer_iter.  New tensors (trend, seasonal, resid, weights or None) shaped
     like ``x``.  No host sync."""
-    dt = _filter_dtype(x, "stl_decompose input")
-    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
-        raise L.GandanetError(f"stl_decompose: expected a dense, non-empty (T, M) tensor, got {tuple(x.shape)} with strides {x.stride()}")
-    outs = [torch.empty_like(x) for _ in range(4 if want_weights else 3)]
-    L.check(lib().gd_stl_decompose(_ptr(x), dt, x.shape[0], x.shape[1], *_stl_args(p), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
-                                   _ptr(outs[3]) if want_weights else None, _stream()), "gd_stl_decompose")
-    return outs[0], outs[1], outs[2], outs[3] if want_weights else None
-
-
-def stl_decompose_host(x, p: dict):
-    """``stl_decompose`` on a HOST array (T, M), fp32 or fp64 (plain C++ loops over the same arithmetic, no GPU): numpy
-    arrays (trend, seasonal, resid, weights)"""
-    import numpy as np
-    x = np.asarray(x)
-    if x.dtype not in (np.float32, np.float64) or x.ndim != 2 or x.size == 0:
-        raise L.GandanetError(f"stl_decompose_host: expected a non-empty float32 / float64 (T, M) array, got {x.dtype} {x.shape}")
-    x = np.ascontiguousarray(x)
-    outs = [np.empty_like(x) for _ in range(4)]
-    L.check(lib().gd_stl_decompose_host(x.ctypes.data, L.FILTER_F64 if x.dtype == np.float64 else L.FILTER_F32, x.shape[0], x.shape[1],
-                                        *_stl_args(p), *[o.ctypes.data for o in outs]), "gd_stl_decompose_host")
+    x, dt = be.array(x, "stl_decompose input", 2)
+    outs = [be.empty(x.shape, x.dtype, x) if k < 3 or want_weights else None for k in range(4)]
+    be.call("gd_stl_decompose", be.ptr(x), dt, x.shape[0], x.shape[1], *_stl_args(p), *[be.ptr(o) for o in outs])
     return tuple(outs)
+
+
+stl_decompose = functools.partial(_stl_decompose, _DEV)
+stl_decompose_host = functools.partial(_stl_decompose, _HOST)   # on a HOST array: plain C++ loops over the same arithmetic, no GPU
 
 
 # ---- per-pixel time series (include/gandanet.h, "Per-pixel time series"; series.hip) -----------------------------------------
@@ -1908,11 +1959,17 @@ def skill_which(metrics) -> int:
     return _which(metrics, L.SKILL_MAPS, "skill")
 
 
-def _series_2d(x: Tensor, name: str) -> int:
-    dt = _filter_dtype(x, name)
-    if x.dim() != 2 or x.numel() == 0:
-        raise L.GandanetError(f"{name}: expected a dense, non-empty (T, M) tensor, got {tuple(x.shape)}")
-    return dt
+def _series_stats(be, pred, truth, rec, mask, skip_nan: bool, accumulate: bool):
+    pred, dt = be.array(pred, "series_stats pred", 2)
+    truth, dt2 = be.array(truth, "series_stats truth", 2)
+    if dt2 != dt or truth.shape != pred.shape:
+        raise L.GandanetError(f"series_stats: pred {tuple(pred.shape)} {pred.dtype} vs truth {tuple(truth.shape)} {truth.dtype}")
+    T, M = pred.shape
+    rec = be.out(rec, (8, M), be.f64, pred, "series records")
+    mask = be.vec(mask, None if be.host else M, "series_stats mask", be.u8)      # the host twin takes the length on trust
+    be.call("gd_series_stats", be.ptr(pred), be.ptr(truth), dt, T, M, be.ptr(mask), L.EVAL_SKIP_NAN if skip_nan else 0, be.ptr(rec),
+            int(accumulate))
+    return rec
 
 
 def series_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] = None, skip_nan: bool = True,
@@ -1920,46 +1977,52 @@ def series_stats(pred: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor
     """the records of the M series of ``pred`` against ``truth`` (dense fp32 / fp64 (T, M), series m at ``[:, m]``) into
     ``rec`` (8, M) fp64; ``mask``: M uint8, 0 = skip the series; ``accumulate`` continues from the records in ``rec``.  No
     host sync."""
-    dt = _series_2d(pred, "series_stats pred")
-    if _series_2d(truth, "series_stats truth") != dt or truth.shape != pred.shape:
-        raise L.GandanetError(f"series_stats: pred {tuple(pred.shape)} {pred.dtype} vs truth {tuple(truth.shape)} {truth.dtype}")
-    T, M = pred.shape
-    _dense(rec, "series records", torch.float64)
-    if tuple(rec.shape) != (8, M):
-        raise L.GandanetError(f"series_stats: the records are (8, {M}) float64, got {tuple(rec.shape)}")
-    mask = _eval_mask(mask, M)
-    L.check(lib().gd_series_stats(_ptr(pred), _ptr(truth), dt, T, M, _ptr(mask), L.EVAL_SKIP_NAN if skip_nan else 0, _ptr(rec),
-                                  int(accumulate), _stream()), "gd_series_stats")
-    return rec
+    if rec is None:
+        raise L.GandanetError("series_stats: the records are an (8, M) float64 GPU tensor, got None")
+    return _series_stats(_DEV, pred, truth, rec, mask, skip_nan, accumulate)
 
 
-def series_skill(rec: Tensor, metrics, ddof: int = 0) -> Tensor:
-    """the maps named by ``metrics`` from (8, M) records: a new (len(set(metrics)), M) fp64 tensor, the maps in the order of
-    L.SKILL_MAPS"""
-    _dense(rec, "series records", torch.float64)
-    if rec.dim() != 2 or rec.shape[0] != 8 or rec.shape[1] == 0:
+def series_stats_host(pred, truth, mask=None, skip_nan: bool = True, rec=None):
+    """``series_stats`` on HOST arrays (plain C++ loops over the same arithmetic, no GPU): the (8, M) records, continued
+    from a copy of ``rec`` when one is given"""
+    acc = rec is not None
+    return _series_stats(_HOST, pred, truth, np.array(rec, dtype=np.float64, order="C") if acc else None, mask, skip_nan, acc)
+
+
+def _series_skill(be, rec, metrics, ddof: int = 0):
+    """the maps named by ``metrics`` from (8, M) fp64 records, in the order of L.SKILL_MAPS: on the device a new
+    (len(set(metrics)), M) fp64 tensor, on the host a dict name -> (M) array"""
+    rec = be.dense(rec, "series records", be.f64)
+    if not be.host and (rec.ndim != 2 or rec.shape[0] != 8 or rec.shape[1] == 0):
         raise L.GandanetError(f"series_skill: the records are (8, M) float64, got {tuple(rec.shape)}")
     which = skill_which(metrics)
-    M = rec.shape[1]
-    out = torch.empty((bin(which).count("1"), M), device=rec.device, dtype=torch.float64)
-    L.check(lib().gd_series_skill(_ptr(rec), M, int(ddof), which, _ptr(out), _stream()), "gd_series_skill")
-    return out
+    names, M = _which_names(which, L.SKILL_MAPS), rec.shape[1]
+    out = be.empty((len(names), M), be.f64, rec)
+    be.call("gd_series_skill", be.ptr(rec), M, int(ddof), which, be.ptr(out))
+    return dict(zip(names, out)) if be.host else out
 
 
-def series_lstsq(x: Tensor, basis: Tensor, want_rss: bool = True) -> Tuple[Tensor, Optional[Tensor], Tensor]:
+series_skill = functools.partial(_series_skill, _DEV)
+series_skill_host = functools.partial(_series_skill, _HOST)
+
+
+def _series_lstsq(be, x, basis, want_rss: bool = True):
     """least squares of the M series of ``x`` (dense fp32 / fp64 (T, M)) against ``basis`` (T, P) fp64, NaN samples left
     out: new fp64 tensors (coef (P, M), rss (M) or None, n (M))"""
-    dt = _series_2d(x, "series_lstsq input")
+    x, dt = be.array(x, "series_lstsq input", 2)
     T, M = x.shape
-    _dense(basis, "series_lstsq basis", torch.float64)
-    if basis.dim() != 2 or basis.shape[0] != T or not 1 <= basis.shape[1] <= L.LSTSQ_MAX_P:
+    basis = be.dense(basis, "series_lstsq basis", be.f64)
+    if not be.host and (basis.ndim != 2 or basis.shape[0] != T or not 1 <= basis.shape[1] <= L.LSTSQ_MAX_P):
         raise L.GandanetError(f"series_lstsq: the basis is ({T}, P) float64 with 1 <= P <= {L.LSTSQ_MAX_P}, got {tuple(basis.shape)}")
     P = basis.shape[1]
-    coef = torch.empty((P, M), device=x.device, dtype=torch.float64)
-    rss = torch.empty(M, device=x.device, dtype=torch.float64) if want_rss else None
-    n = torch.empty(M, device=x.device, dtype=torch.float64)
-    L.check(lib().gd_series_lstsq(_ptr(x), dt, T, M, _ptr(basis), P, _ptr(coef), _ptr(rss), _ptr(n), _stream()), "gd_series_lstsq")
+    coef, n = be.empty((P, M), be.f64, x), be.empty((M,), be.f64, x)
+    rss = be.empty((M,), be.f64, x) if want_rss else None
+    be.call("gd_series_lstsq", be.ptr(x), dt, T, M, be.ptr(basis), P, be.ptr(coef), be.ptr(rss), be.ptr(n))
     return coef, rss, n
+
+
+series_lstsq = functools.partial(_series_lstsq, _DEV)
+series_lstsq_host = functools.partial(_series_lstsq, _HOST)
 
 
 def harmonic_finalize(coef: Tensor, K: int, has_trend: bool, tau_scale: float, rss: Optional[Tensor], n: Optional[Tensor]):
@@ -1978,89 +2041,30 @@ def harmonic_finalize(coef: Tensor, K: int, has_trend: bool, tau_scale: float, r
     return amp, phase, slope, rms
 
 
-def block_mean(x: Tensor, fy: int, fx: int, weights: Optional[Tensor] = None, min_count: int = 1) -> Tuple[Tensor, Tensor]:
+def _block_mean(be, x, fy: int, fx: int, weights=None, min_count: int = 1):
     """NaN-aware mean of every ``fy`` x ``fx`` block of the last two dims of the dense fp32 / fp64 ``x`` (..., H, W);
     ``weights``: (H, W) fp64 or None.  Returns (mean in the dtype of ``x``, count int32), shaped (..., H / fy, W / fx)."""
-    dt = _filter_dtype(x, "block_mean input")
-    if x.dim() < 2 or x.numel() == 0:
-        raise L.GandanetError(f"block_mean: expected a non-empty (..., H, W) tensor, got {tuple(x.shape)}")
+    x, dt = be.array(x, "block_mean input")
+    if x.ndim < 2:
+        raise L.GandanetError(f"block_mean: expected a non-empty (..., H, W) array, got {tuple(x.shape)}")
     H, W = x.shape[-2:]
-    fy, fx = int(fy), int(fx)
-    if fy < 1 or fx < 1 or H % fy or W % fx:
-        raise L.GandanetError(f"block_mean: blocks of {fy} x {fx} do not divide ({H}, {W})")
-    if weights is not None:
-        _dense(weights, "block_mean weights", torch.float64)
-        if tuple(weights.shape) != (H, W):
+    if be.host:                                 # the host twin leaves the blocks to the C entry and the weights' length to the caller
+        weights = be.vec(weights, None, "block_mean weights")
+    else:
+        fy, fx = int(fy), int(fx)
+        if fy < 1 or fx < 1 or H % fy or W % fx:
+            raise L.GandanetError(f"block_mean: blocks of {fy} x {fx} do not divide ({H}, {W})")
+        if weights is not None and tuple(be.dense(weights, "block_mean weights", be.f64).shape) != (H, W):
             raise L.GandanetError(f"block_mean: weights {tuple(weights.shape)} vs planes ({H}, {W})")
-    shape = tuple(x.shape[:-2]) + (H // fy, W // fx)
-    out = torch.empty(shape, device=x.device, dtype=x.dtype)
-    count = torch.empty(shape, device=x.device, dtype=torch.int32)
-    L.check(lib().gd_block_mean(_ptr(x), dt, math.prod(x.shape[:-2]), H, W, fy, fx, _ptr(weights), int(min_count), _ptr(out),
-                                _ptr(count), _stream()), "gd_block_mean")
-    return out, count
-
-
-def _host_f(x, name: str):
-    import numpy as np
-    x = np.asarray(x)
-    if x.dtype not in (np.float32, np.float64) or x.size == 0:
-        raise L.GandanetError(f"{name}: expected a non-empty float32 / float64 array, got {x.dtype} {x.shape}")
-    return np.ascontiguousarray(x), (L.FILTER_F64 if x.dtype == np.float64 else L.FILTER_F32)
-
-
-def series_stats_host(pred, truth, mask=None, skip_nan: bool = True, rec=None):
-    """``series_stats`` on HOST arrays (plain C++ loops over the same arithmetic, no GPU): the (8, M) records, continued
-    from ``rec`` when one is given"""
-    import numpy as np
-    pred, dt = _host_f(pred, "series_stats_host")
-    truth, dt2 = _host_f(truth, "series_stats_host")
-    if dt != dt2 or pred.shape != truth.shape or pred.ndim != 2:
-        raise L.GandanetError(f"series_stats_host: pred {pred.dtype} {pred.shape} vs truth {truth.dtype} {truth.shape}")
-    T, M = pred.shape
-    acc = rec is not None
-    rec = np.ascontiguousarray(rec, dtype=np.float64).copy() if acc else np.empty((8, M))
-    mask = _host_vec(mask, None, "series_stats_host mask", "uint8")
-    L.check(lib().gd_series_stats_host(pred.ctypes.data, truth.ctypes.data, dt, T, M, _np_ptr(mask),
-                                       L.EVAL_SKIP_NAN if skip_nan else 0, rec.ctypes.data, int(acc)), "gd_series_stats_host")
-    return rec
-
-
-def series_skill_host(rec, metrics, ddof: int = 0):
-    """``series_skill`` on (8, M) HOST records: a dict name -> (M) array"""
-    import numpy as np
-    rec = np.ascontiguousarray(rec, dtype=np.float64)
-    which = skill_which(metrics)
-    names = _which_names(which, L.SKILL_MAPS)
-    out = np.empty((len(names), rec.shape[1]))
-    L.check(lib().gd_series_skill_host(rec.ctypes.data, rec.shape[1], int(ddof), which, out.ctypes.data), "gd_series_skill_host")
-    return dict(zip(names, out))
-
-
-def series_lstsq_host(x, basis):
-    """``series_lstsq`` on HOST arrays: (coef (P, M), rss (M), n (M))"""
-    import numpy as np
-    x, dt = _host_f(x, "series_lstsq_host")
-    basis = np.ascontiguousarray(basis, dtype=np.float64)
-    T, M = x.shape
-    P = basis.shape[1]
-    coef, rss, n = np.empty((P, M)), np.empty(M), np.empty(M)
-    L.check(lib().gd_series_lstsq_host(x.ctypes.data, dt, T, M, basis.ctypes.data, P, coef.ctypes.data, rss.ctypes.data, n.ctypes.data),
-            "gd_series_lstsq_host")
-    return coef, rss, n
-
-
-def block_mean_host(x, fy: int, fx: int, weights=None, min_count: int = 1):
-    """``block_mean`` on a HOST array (..., H, W): (mean, count)"""
-    import numpy as np
-    x, dt = _host_f(x, "block_mean_host")
-    H, W = x.shape[-2:]
-    weights = _host_vec(weights, None, "block_mean_host weights")
-    planes = math.prod(x.shape[:-2])
     shape = tuple(x.shape[:-2]) + (H // max(fy, 1), W // max(fx, 1))
-    out, count = np.empty(shape, dtype=x.dtype), np.empty(shape, dtype=np.int32)
-    L.check(lib().gd_block_mean_host(x.ctypes.data, dt, planes, H, W, int(fy), int(fx), _np_ptr(weights),
-                                     int(min_count), out.ctypes.data, count.ctypes.data), "gd_block_mean_host")
+    out, count = be.empty(shape, x.dtype, x), be.empty(shape, be.i32, x)
+    be.call("gd_block_mean", be.ptr(x), dt, math.prod(x.shape[:-2]), H, W, int(fy), int(fx), be.ptr(weights), int(min_count), be.ptr(out),
+            be.ptr(count))
     return out, count
+
+
+block_mean = functools.partial(_block_mean, _DEV)
+block_mean_host = functools.partial(_block_mean, _HOST)
 
 
 # ---- per-pixel trend tests (include/gandanet.h, "Per-pixel trend tests"; trend.hip) ------------------------------------------
@@ -2068,38 +2072,24 @@ def trend_flags(sen: bool, ci: bool, continuity: bool) -> int:
     return (L.TREND_SEN if sen else 0) | (L.TREND_CI if ci else 0) | (L.TREND_CONTINUITY if continuity else 0)
 
 
-def trend_test(x: Tensor, times: Tensor, period: int = 0, mask: Optional[Tensor] = None, flags: int = L.TREND_CONTINUITY,
-               zq: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
-    """Mann-Kendall / Theil-Sen of the M series of a dense fp32 / fp64 ``x`` (T, M) at the fp64 device ``times`` (T), which
-    the caller has checked to be finite and increasing; ``period`` 0 = not seasonal; ``mask``: M uint8.  The planes
-    (L.TREND_MAPS) go into ``out`` (10, M) fp64, a new tensor unless one is given; those that ``flags`` does not ask for are
-    left as they are.  No host sync."""
-    dt = _series_2d(x, "trend_test input")
+def _trend_test(be, x, times, period: int = 0, mask=None, flags: int = L.TREND_CONTINUITY, zq: float = 0.0, out=None):
+    """Mann-Kendall / Theil-Sen of the M series of a dense fp32 / fp64 ``x`` (T, M) at the fp64 ``times`` (T), which the
+    caller of the device entry has checked to be finite and increasing (the host twin looks itself); ``period`` 0 = not
+    seasonal; ``mask``: M uint8.  The planes (L.TREND_MAPS) go into ``out`` (10, M) fp64, a new tensor unless one is given;
+    those that ``flags`` does not ask for are left as they are.  No host sync."""
+    x, dt = be.array(x, "trend_test input", 2)
     T, M = x.shape
-    _dense(times, "trend_test times", torch.float64)
-    if times.dim() != 1 or times.shape[0] != T:
+    times = be.vec(times, T, "trend_test times")
+    if not be.host and times.ndim != 1:
         raise L.GandanetError(f"trend_test: {tuple(times.shape)} times for {T} samples")
-    out = _out(out, (len(L.TREND_MAPS), M), x, torch.float64, "trend_test output")
-    mask = _eval_mask(mask, M)
-    L.check(lib().gd_trend_test(_ptr(x), dt, T, M, _ptr(times), int(period), _ptr(mask), int(flags), float(zq), _ptr(out), _stream()),
-            "gd_trend_test")
+    out = be.out(out, (len(L.TREND_MAPS), M), be.f64, x, "trend_test output")
+    mask = be.vec(mask, None if be.host else M, "trend_test mask", be.u8)        # the host twin takes the length on trust
+    be.call("gd_trend_test", be.ptr(x), dt, T, M, be.ptr(times), int(period), be.ptr(mask), int(flags), float(zq), be.ptr(out))
     return out
 
 
-def trend_test_host(x, times, period: int = 0, mask=None, flags: int = L.TREND_CONTINUITY, zq: float = 0.0, out=None):
-    """``trend_test`` on HOST arrays (plain C++ over the same per-pair arithmetic; the order statistics by sorting the
-    stored slopes): the (10, M) planes"""
-    import numpy as np
-    x, dt = _host_f(x, "trend_test_host")
-    if x.ndim != 2:
-        raise L.GandanetError(f"trend_test_host: expected a (T, M) array, got {x.shape}")
-    T, M = x.shape
-    times = _host_vec(times, T, "trend_test_host times")
-    out = np.empty((len(L.TREND_MAPS), M)) if out is None else out
-    mask = _host_vec(mask, None, "trend_test_host mask", "uint8")
-    L.check(lib().gd_trend_test_host(x.ctypes.data, dt, T, M, _np_ptr(times), int(period), _np_ptr(mask),
-                                     int(flags), float(zq), out.ctypes.data), "gd_trend_test_host")
-    return out
+trend_test = functools.partial(_trend_test, _DEV)
+trend_test_host = functools.partial(_trend_test, _HOST)   # plain C++ over the same per-pair arithmetic; sorts the stored slopes
 
 
 # ---- ensemble verification (include/gandanet.h, "Ensemble verification"; ensverify.hip) ------------------------------------
@@ -2122,6 +2112,8 @@ def _ens_members(x, is_host: bool, fn: str):
     return M, n, int(stride)
 
 
+# The two twins of ens_verify stay apart: the members are read in place (a strided stack is not copied), the device entry
+# writes into the caller's record and maps and takes a workspace, the host twin allocates all of them.
 def ens_verify(x: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] = None, scale: float = 1.0, fair: bool = False,
                crps_map: Optional[Tensor] = None, err_map: Optional[Tensor] = None, spread_map: Optional[Tensor] = None,
                rank_map: Optional[Tensor] = None) -> Tensor:
@@ -2141,23 +2133,21 @@ def ens_verify(x: Tensor, truth: Tensor, rec: Tensor, mask: Optional[Tensor] = N
     hw = n if mask is None else mask.numel()
     if hw <= 0 or n % hw:
         raise L.GandanetError(f"ens_verify: a mask of {hw} entries does not tile {tuple(truth.shape)}")
-    mask = _eval_mask(mask, hw)
+    _DEV.vec(mask, hw, "ens_verify mask", torch.uint8)
     for o, nm, dt in ((crps_map, "crps_map", x.dtype), (err_map, "err_map", x.dtype), (spread_map, "spread_map", x.dtype),
                       (rank_map, "rank_map", torch.uint8)):
-        if o is not None and (_dense(o, "ens_verify " + nm, dt).numel() != n):
-            raise L.GandanetError(f"ens_verify: {nm} must hold {n} elements, got {tuple(o.shape)}")
+        _DEV.vec(o, n, "ens_verify " + nm, dt)
     nbytes = int(lib().gd_ens_verify_ws_bytes(n))
     ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    L.check(lib().gd_ens_verify(_ptr(x), M, stride, _ptr(truth), n // hw, hw, _ptr(mask), float(scale),
-                                ens_verify_flags(x.dtype == torch.float64, fair), _ptr(rec), _ptr(crps_map), _ptr(err_map),
-                                _ptr(spread_map), _ptr(rank_map), _ptr(ws), nbytes, _stream()), "gd_ens_verify")
+    _DEV.call("gd_ens_verify", _ptr(x), M, stride, _ptr(truth), n // hw, hw, _ptr(mask), float(scale),
+              ens_verify_flags(x.dtype == torch.float64, fair), _ptr(rec), _ptr(crps_map), _ptr(err_map), _ptr(spread_map), _ptr(rank_map),
+              _ptr(ws), nbytes)
     return rec
 
 
 def ens_verify_host(x, truth, mask=None, scale: float = 1.0, fair: bool = False, maps: bool = True):
     """``ens_verify`` on HOST arrays (plain C++ over the same per-element core, walking the device's grid; no GPU):
     (record, maps) with maps = dict(crps, err, spread, rank) shaped like ``truth``, or None"""
-    import numpy as np
     x = np.asarray(x)
     if x.dtype not in (np.float32, np.float64):
         raise L.GandanetError(f"ens_verify_host: expected float32 / float64 members, got {x.dtype}")
@@ -2165,26 +2155,21 @@ def ens_verify_host(x, truth, mask=None, scale: float = 1.0, fair: bool = False,
     truth = np.ascontiguousarray(truth, dtype=x.dtype)
     if truth.size != n:
         raise L.GandanetError(f"ens_verify_host: members of {n} elements against a truth of {truth.size}")
-    mask = _host_vec(mask, None, "ens_verify_host mask", "uint8")
+    mask = _HOST.vec(mask, None, "ens_verify_host mask", np.uint8)
     hw = n if mask is None else mask.size
     if hw <= 0 or n % hw:
         raise L.GandanetError(f"ens_verify_host: a mask of {hw} entries does not tile {truth.shape}")
     rec = np.empty(L.ENSV_REC)
-    out = None
-    if maps:
-        out = {"crps": np.empty(truth.shape, x.dtype), "err": np.empty(truth.shape, x.dtype), "spread": np.empty(truth.shape, x.dtype),
-               "rank": np.empty(truth.shape, np.uint8)}
-    ptr = lambda k: out[k].ctypes.data if maps else None
-    L.check(lib().gd_ens_verify_host(x.ctypes.data, M, stride, truth.ctypes.data, n // hw, hw, _np_ptr(mask),
-                                     float(scale), ens_verify_flags(x.dtype == np.float64, fair), rec.ctypes.data, ptr("crps"), ptr("err"),
-                                     ptr("spread"), ptr("rank")), "gd_ens_verify_host")
+    out = {k: np.empty(truth.shape, np.uint8 if k == "rank" else x.dtype) for k in ("crps", "err", "spread", "rank")} if maps else None
+    _HOST.call("gd_ens_verify", x.ctypes.data, M, stride, truth.ctypes.data, n // hw, hw, _HOST.ptr(mask), float(scale),
+               ens_verify_flags(x.dtype == np.float64, fair), rec.ctypes.data, *[out[k].ctypes.data if maps else None for k in
+                                                                                  ("crps", "err", "spread", "rank")])
     return rec, out
 
 
 def ens_verify_merge_host(records, M: int) -> Tuple[list, dict]:
     """add (k, L.ENSV_REC) host records in the given order (plain C++ on the host, no GPU): (merged record, metrics dict).
     ``coverage`` maps the nominal levels L.ENSV_LEVELS to the observed fractions; ``rank_hist`` holds M + 1 fractions"""
-    import numpy as np
     recs = np.ascontiguousarray(np.asarray(records, dtype=np.float64).reshape(-1, L.ENSV_REC))
     out, met = (C.c_double * L.ENSV_REC)(), (C.c_double * L.ENSV_METRICS)()
     ptr = recs.ctypes.data_as(C.POINTER(C.c_double)) if len(recs) else None
@@ -2201,146 +2186,97 @@ def ens_verify_merge_host(records, M: int) -> Tuple[list, dict]:
 
 
 # ---- EOF analysis (include/gandanet.h, "EOF analysis"; eof.hip) ---------------------------------------------------------------
-def eof_prepare(x: Tensor, mask: Optional[Tensor] = None, weight: Optional[Tensor] = None, center: bool = True,
-                mean: Optional[Tensor] = None, valid: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+def _eof_series(be, x, mean, valid, weight, fn: str):
+    """(x, dtype tag, mean, valid, weight) of a (T, M) array with its M fp64 means, M uint8 flags and optional M fp64 weights"""
+    x, dt = be.array(x, fn + " input", 2)
+    M = x.shape[1]
+    return x, dt, be.vec(mean, M, fn + " mean"), be.vec(valid, M, fn + " valid", be.u8), be.vec(weight, M, fn + " weight")
+
+
+def _eof_prepare(be, x, mask=None, weight=None, center: bool = True, mean=None, valid=None):
     """(mean (M) fp64, valid (M) uint8) of the M series of a dense fp32 / fp64 ``x`` (T, M); ``mask``: M uint8; ``weight``:
     M fp64; ``mean`` and ``valid`` may be dense views to write into.  No host sync."""
-    dt = _series_2d(x, "eof_prepare input")
+    x, dt = be.array(x, "eof_prepare input", 2)
     T, M = x.shape
-    mask, weight = _eval_mask(mask, M), _vec(weight, M, "eof_prepare weight")
-    mean = torch.empty(M, device=x.device, dtype=torch.float64) if mean is None else _vec(mean, M, "eof_prepare mean")
-    valid = torch.empty(M, device=x.device, dtype=torch.uint8) if valid is None else _vec(valid, M, "eof_prepare valid", torch.uint8)
-    L.check(lib().gd_eof_prepare(_ptr(x), dt, T, M, _ptr(mask), _ptr(weight), int(bool(center)), _ptr(mean), _ptr(valid), _stream()),
-            "gd_eof_prepare")
+    n = None if be.host else M                                                   # the host twin takes the lengths on trust
+    mask, weight = be.vec(mask, n, "eof_prepare mask", be.u8), be.vec(weight, n, "eof_prepare weight")
+    mean = be.empty((M,), be.f64, x) if mean is None else be.vec(mean, M, "eof_prepare mean")
+    valid = be.empty((M,), be.u8, x) if valid is None else be.vec(valid, M, "eof_prepare valid", be.u8)
+    be.call("gd_eof_prepare", be.ptr(x), dt, T, M, be.ptr(mask), be.ptr(weight), int(bool(center)), be.ptr(mean), be.ptr(valid))
     return mean, valid
+
+
+eof_prepare = functools.partial(_eof_prepare, _DEV)
+eof_prepare_host = functools.partial(_eof_prepare, _HOST)
 
 
 def eof_gram_ws_bytes(T: int, M: int) -> int:
     return int(lib().gd_eof_gram_ws_bytes(int(T), int(M)))
 
 
-def eof_gram(x: Tensor, mean: Tensor, valid: Tensor, weight: Optional[Tensor] = None, out: Optional[Tensor] = None,
-             ws: Optional[Tensor] = None) -> Tensor:
+def _eof_gram(be, x, mean, valid, weight=None, out=None, ws=None):
     """the (T, T) fp64 Gram matrix of the weighted anomalies of the dense fp32 / fp64 ``x`` (T, M), 2 <= T <= L.EOF_MAX_T;
-    ``out`` and the uint8 workspace ``ws`` (eof_gram_ws_bytes) are allocated unless given.  No host sync."""
-    dt = _series_2d(x, "eof_gram input")
+    ``out`` and the uint8 workspace ``ws`` (eof_gram_ws_bytes) are allocated unless given.  On the host every entry is summed
+    over m in ascending order.  No host sync."""
+    x, dt, mean, valid, weight = _eof_series(be, x, mean, valid, weight, "eof_gram")
     T, M = x.shape
-    _vec(mean, M, "eof_gram mean")
-    _vec(valid, M, "eof_gram valid", torch.uint8)
-    _vec(weight, M, "eof_gram weight")
-    if out is None:
-        out = torch.empty((T, T), device=x.device, dtype=torch.float64)
-    _dense(out, "eof_gram output", torch.float64)
-    if out.numel() != T * T:
-        raise L.GandanetError(f"eof_gram: the output is ({T}, {T}) float64, got {tuple(out.shape)}")
-    ws = _ws(ws, eof_gram_ws_bytes(T, M), x, "eof_gram")
-    L.check(lib().gd_eof_gram(_ptr(x), dt, T, M, _ptr(mean), _ptr(valid), _ptr(weight), _ptr(out), _ptr(ws), ws.numel(), _stream()),
-            "gd_eof_gram")
+    out = be.empty((T, T), be.f64, x) if out is None else be.vec(out, T * T, "eof_gram output")
+    be.call("gd_eof_gram", be.ptr(x), dt, T, M, be.ptr(mean), be.ptr(valid), be.ptr(weight), be.ptr(out),
+            *be.ws(ws, eof_gram_ws_bytes(T, M), x, "eof_gram"))
     return out
 
 
-def eof_project(x: Tensor, mean: Tensor, valid: Tensor, coef: Tensor, weight: Optional[Tensor] = None, use_weight: bool = False,
-                out: Optional[Tensor] = None) -> Tensor:
-    """(K, M) fp64 planes out[k, m] = s_m sum_t coef[t, k] (x[t, m] - mean[m]) for ``coef`` (T, K) fp64 on the device,
-    1 <= K <= L.EOF_MAX_K; ``out`` may be a dense (K, M) view to write into.  No host sync."""
-    dt = _series_2d(x, "eof_project input")
+eof_gram = functools.partial(_eof_gram, _DEV)
+eof_gram_host = functools.partial(_eof_gram, _HOST)
+
+
+def _eof_project(be, x, mean, valid, coef, weight=None, use_weight: bool = False, out=None):
+    """(K, M) fp64 planes out[k, m] = s_m sum_t coef[t, k] (x[t, m] - mean[m]) for ``coef`` (T, K) fp64, 1 <= K <=
+    L.EOF_MAX_K; ``out`` may be a dense (K, M) view to write into.  No host sync."""
+    x, dt, mean, valid, weight = _eof_series(be, x, mean, valid, weight, "eof_project")
     T, M = x.shape
-    _vec(mean, M, "eof_project mean")
-    _vec(valid, M, "eof_project valid", torch.uint8)
-    _vec(weight, M, "eof_project weight")
-    _dense(coef, "eof_project coefficients", torch.float64)
-    if coef.dim() != 2 or coef.shape[0] != T or not 1 <= coef.shape[1] <= L.EOF_MAX_K:
+    coef = be.dense(coef, "eof_project coefficients", be.f64)
+    if not be.host and (coef.ndim != 2 or coef.shape[0] != T or not 1 <= coef.shape[1] <= L.EOF_MAX_K):
         raise L.GandanetError(f"eof_project: the coefficients are ({T}, K) float64 with 1 <= K <= {L.EOF_MAX_K}, got {tuple(coef.shape)}")
     K = coef.shape[1]
-    out = _out(out, (K, M), x, torch.float64, "eof_project output")
-    L.check(lib().gd_eof_project(_ptr(x), dt, T, M, _ptr(mean), _ptr(valid), _ptr(weight), int(bool(use_weight)), _ptr(coef), K, _ptr(out),
-                                 _stream()), "gd_eof_project")
+    out = be.out(out, (K, M), be.f64, x, "eof_project output")
+    be.call("gd_eof_project", be.ptr(x), dt, T, M, be.ptr(mean), be.ptr(valid), be.ptr(weight), int(bool(use_weight)), be.ptr(coef), K,
+            be.ptr(out))
     return out
 
 
-def eof_reconstruct(eofs: Tensor, pcs: Tensor, mean: Tensor, valid: Tensor, weight: Optional[Tensor] = None,
-                    dtype=torch.float64, out: Optional[Tensor] = None) -> Tensor:
-    """(T, M) in ``dtype`` (fp32 / fp64): mean[m] + (sum_k pcs[t, k] eofs[k, m]) / sqrt(weight[m]) for ``eofs`` (K, M) and
-    ``pcs`` (T, K) fp64 on the device, 1 <= K <= L.EOF_MAX_K; ``out`` may be a dense (T, M) view of ``dtype`` to write into.
-    No host sync."""
-    _dense(eofs, "eof_reconstruct eofs", torch.float64)
-    _dense(pcs, "eof_reconstruct pcs", torch.float64)
-    if eofs.dim() != 2 or pcs.dim() != 2 or pcs.shape[1] != eofs.shape[0] or not 1 <= eofs.shape[0] <= L.EOF_MAX_K:
+eof_project = functools.partial(_eof_project, _DEV)
+eof_project_host = functools.partial(_eof_project, _HOST)
+
+
+def _eof_reconstruct(be, eofs, pcs, mean, valid, weight=None, dtype=None, out=None):
+    """(T, M) in ``dtype`` (fp32 / fp64, fp64 unless given): mean[m] + (sum_k pcs[t, k] eofs[k, m]) / sqrt(weight[m]) for
+    ``eofs`` (K, M) and ``pcs`` (T, K) fp64, 1 <= K <= L.EOF_MAX_K; ``out`` may be a dense (T, M) view of ``dtype`` to write
+    into.  No host sync."""
+    eofs, pcs = be.dense(eofs, "eof_reconstruct eofs", be.f64), be.dense(pcs, "eof_reconstruct pcs", be.f64)
+    if not be.host and (eofs.ndim != 2 or pcs.ndim != 2 or pcs.shape[1] != eofs.shape[0] or not 1 <= eofs.shape[0] <= L.EOF_MAX_K):
         raise L.GandanetError(f"eof_reconstruct: eofs (K, M) and pcs (T, K) with 1 <= K <= {L.EOF_MAX_K}, got {tuple(eofs.shape)} and "
                               f"{tuple(pcs.shape)}")
-    if dtype not in (torch.float32, torch.float64):
+    dtype = be.f64 if dtype is None else (np.dtype(dtype) if be.host else dtype)
+    if dtype not in (be.f32, be.f64):
         raise L.GandanetError(f"eof_reconstruct: the output is float32 or float64, got {dtype}")
     (K, M), T = eofs.shape, pcs.shape[0]
-    _vec(mean, M, "eof_reconstruct mean")
-    _vec(valid, M, "eof_reconstruct valid", torch.uint8)
-    _vec(weight, M, "eof_reconstruct weight")
-    out = _out(out, (T, M), eofs, dtype, "eof_reconstruct output")
-    L.check(lib().gd_eof_reconstruct(_ptr(eofs), _ptr(pcs), _ptr(mean), _ptr(valid), _ptr(weight), T, M, K, _ptr(out),
-                                     int(dtype == torch.float64), _stream()), "gd_eof_reconstruct")
+    n = None if be.host else M                                                   # the host twin takes the lengths on trust
+    mean, valid = be.vec(mean, n, "eof_reconstruct mean"), be.vec(valid, n, "eof_reconstruct valid", be.u8)
+    weight = be.vec(weight, n, "eof_reconstruct weight")
+    out = be.out(out, (T, M), dtype, eofs, "eof_reconstruct output")
+    be.call("gd_eof_reconstruct", be.ptr(eofs), be.ptr(pcs), be.ptr(mean), be.ptr(valid), be.ptr(weight), T, M, K, be.ptr(out),
+            int(dtype == be.f64))
     return out
 
 
-def _eof_host_args(x, mean, valid, weight, fn: str):
-    x, dt = _host_f(x, fn)
-    if x.ndim != 2:
-        raise L.GandanetError(f"{fn}: expected a (T, M) array, got {x.shape}")
-    M = x.shape[1]
-    return x, dt, _host_vec(mean, M, fn + " mean"), _host_vec(valid, M, fn + " valid", "uint8"), _host_vec(weight, M, fn + " weight")
-
-
-def eof_prepare_host(x, mask=None, weight=None, center: bool = True):
-    """``eof_prepare`` on HOST arrays (plain C++ over the same arithmetic, no GPU): (mean, valid)"""
-    import numpy as np
-    x, dt = _host_f(x, "eof_prepare_host")
-    T, M = x.shape
-    mask, weight = _host_vec(mask, None, "eof_prepare_host mask", "uint8"), _host_vec(weight, None, "eof_prepare_host weight")
-    mean, valid = np.empty(M), np.empty(M, dtype=np.uint8)
-    L.check(lib().gd_eof_prepare_host(x.ctypes.data, dt, T, M, _np_ptr(mask), _np_ptr(weight), int(bool(center)), mean.ctypes.data,
-                                      valid.ctypes.data), "gd_eof_prepare_host")
-    return mean, valid
-
-
-def eof_gram_host(x, mean, valid, weight=None):
-    """``eof_gram`` on HOST arrays: the (T, T) Gram matrix, every entry summed over m in ascending order"""
-    import numpy as np
-    x, dt, mean, valid, weight = _eof_host_args(x, mean, valid, weight, "eof_gram_host")
-    T, M = x.shape
-    G = np.empty((T, T))
-    L.check(lib().gd_eof_gram_host(x.ctypes.data, dt, T, M, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), G.ctypes.data),
-            "gd_eof_gram_host")
-    return G
-
-
-def eof_project_host(x, mean, valid, coef, weight=None, use_weight: bool = False):
-    """``eof_project`` on HOST arrays: (K, M)"""
-    import numpy as np
-    x, dt, mean, valid, weight = _eof_host_args(x, mean, valid, weight, "eof_project_host")
-    T, M = x.shape
-    coef = np.ascontiguousarray(coef, dtype=np.float64)
-    K = coef.shape[1]
-    out = np.empty((K, M))
-    L.check(lib().gd_eof_project_host(x.ctypes.data, dt, T, M, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), int(bool(use_weight)),
-                                      coef.ctypes.data, K, out.ctypes.data), "gd_eof_project_host")
-    return out
-
-
-def eof_reconstruct_host(eofs, pcs, mean, valid, weight=None, dtype="float64"):
-    """``eof_reconstruct`` on HOST arrays: (T, M) in ``dtype``"""
-    import numpy as np
-    eofs, pcs = np.ascontiguousarray(eofs, dtype=np.float64), np.ascontiguousarray(pcs, dtype=np.float64)
-    (K, M), T = eofs.shape, pcs.shape[0]
-    mean, valid = _host_vec(mean, None, "eof_reconstruct_host mean"), _host_vec(valid, None, "eof_reconstruct_host valid", "uint8")
-    weight = _host_vec(weight, None, "eof_reconstruct_host weight")
-    out = np.empty((T, M), dtype=np.dtype(dtype))
-    L.check(lib().gd_eof_reconstruct_host(eofs.ctypes.data, pcs.ctypes.data, mean.ctypes.data, valid.ctypes.data, _np_ptr(weight), T, M, K,
-                                          out.ctypes.data, int(out.dtype == np.float64)), "gd_eof_reconstruct_host")
-    return out
+eof_reconstruct = functools.partial(_eof_reconstruct, _DEV)
+eof_reconstruct_host = functools.partial(_eof_reconstruct, _HOST)
 
 
 # ---- Spatial spectra (include/gandanet.h, "Spatial spectra"; spectra.hip) -----------------------------------------------------
 def spec_twiddle_host(N: int):
     """cos and sin of 2 pi r / N, r = 0 .. N - 1, as one HOST array of 2 N doubles (octant reduction, within 1 ulp)"""
-    import numpy as np
     tw = np.empty(2 * int(N))
     L.check(lib().gd_spec_twiddle_host(int(N), tw.ctypes.data), "gd_spec_twiddle_host")
     return tw
@@ -2352,7 +2288,6 @@ def spec_default_bins(H: int, W: int, dy: float, dx: float) -> int:
 
 def spec_bins_host(H: int, W: int, dy: float, dx: float, nbins: int, kmax: float = 0.0):
     """the HOST bin table of an (H, W) grid of spacing (dy, dx): (bin (H, W // 2 + 1) int32, kcentre (nbins), count (nbins))"""
-    import numpy as np
     H, W, nbins = int(H), int(W), int(nbins)
     bins = np.empty((max(H, 0), max(W, 0) // 2 + 1), dtype=np.int32)
     kc, count = np.empty(max(nbins, 0)), np.empty(max(nbins, 0), dtype=np.int64)
@@ -2361,29 +2296,28 @@ def spec_bins_host(H: int, W: int, dy: float, dx: float, nbins: int, kmax: float
     return bins, kc, count
 
 
-def _spec_cube(x: Tensor, name: str) -> int:
-    dt = _filter_dtype(x, name)
-    if x.dim() != 3 or x.numel() == 0:
-        raise L.GandanetError(f"{name}: expected a dense, non-empty (T, H, W) tensor, got {tuple(x.shape)}")
-    return dt
+def _spec_cube(be, x, mask, wy, wx, fn: str):
+    """(x, dtype tag, mask, wy, wx) of a (T, H, W) cube with its optional H W uint8 mask and fp64 tapers of H and W entries"""
+    x, dt = be.array(x, fn + " input", 3)
+    T, H, W = x.shape
+    return x, dt, be.vec(mask, H * W, fn + " mask", be.u8), be.vec(wy, H, fn + " wy"), be.vec(wx, W, fn + " wx")
 
 
-def spec_prepare(x: Tensor, mask: Optional[Tensor] = None, wy: Optional[Tensor] = None, wx: Optional[Tensor] = None,
-                 detrend: str = "mean", coef: Optional[Tensor] = None, S: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+def _spec_prepare(be, x, mask=None, wy=None, wx=None, detrend: str = "mean", coef=None, S=None):
     """(coef (T, 3), S (T, 2)) fp64 of the fields of a dense fp32 / fp64 ``x`` (T, H, W): the detrend coefficients
     (a, b, c) about the field's centre, and (sum of wy^2 wx^2, count) over the valid pixels.  ``mask``: H * W uint8 shared
     by all fields; ``wy`` (H), ``wx`` (W): fp64 tapers.  No host sync."""
-    dt = _spec_cube(x, "spec_prepare input")
+    x, dt, mask, wy, wx = _spec_cube(be, x, mask, wy, wx, "spec_prepare")
     if detrend not in L.SPEC_DETREND:
         raise L.GandanetError(f"spec_prepare: detrend is one of {sorted(L.SPEC_DETREND)}, got {detrend!r}")
     T, H, W = x.shape
-    mask = _eval_mask(mask, H * W)
-    _vec(wy, H, "spec_prepare wy")
-    _vec(wx, W, "spec_prepare wx")
-    coef, S = _out(coef, (T, 3), x, torch.float64, "spec_prepare coef"), _out(S, (T, 2), x, torch.float64, "spec_prepare S")
-    L.check(lib().gd_spec_prepare(_ptr(x), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), L.SPEC_DETREND[detrend], _ptr(coef), _ptr(S),
-                                  _stream()), "gd_spec_prepare")
+    coef, S = be.out(coef, (T, 3), be.f64, x, "spec_prepare coef"), be.out(S, (T, 2), be.f64, x, "spec_prepare S")
+    be.call("gd_spec_prepare", be.ptr(x), dt, T, H, W, be.ptr(mask), be.ptr(wy), be.ptr(wx), L.SPEC_DETREND[detrend], be.ptr(coef), be.ptr(S))
     return coef, S
+
+
+spec_prepare = functools.partial(_spec_prepare, _DEV)
+spec_prepare_host = functools.partial(_spec_prepare, _HOST)
 
 
 def spec_power_ws_bytes(T: int, H: int, W: int, nbins: int) -> int:
@@ -2394,14 +2328,30 @@ def spec_cross_ws_bytes(T: int, H: int, W: int, nbins: int) -> int:
     return int(lib().gd_spec_cross_ws_bytes(int(T), int(H), int(W), int(nbins)))
 
 
-def _spec_tables(x: Tensor, twid_h: Tensor, twid_w: Tensor, bins: Tensor, fn: str) -> int:
+def _spec_tables(be, x, twid_h, twid_w, bins, fn: str):
+    """the twiddle tables of 2 H and 2 W doubles and the (H, W // 2 + 1) int32 bin table of the cube ``x``"""
     T, H, W = x.shape
-    _vec(twid_h, 2 * H, fn + " twid_h")
-    _vec(twid_w, 2 * W, fn + " twid_w")
-    _dense(bins, fn + " bins", torch.int32)
-    if tuple(bins.shape) != (H, W // 2 + 1):
+    bins = be.dense(bins, fn + " bins", be.i32)
+    if not be.host and tuple(bins.shape) != (H, W // 2 + 1):                     # the host twin takes the table's shape on trust
         raise L.GandanetError(f"{fn}: the bin table is ({H}, {W // 2 + 1}) int32, got {tuple(bins.shape)}")
-    return T
+    return be.vec(twid_h, 2 * H, fn + " twid_h"), be.vec(twid_w, 2 * W, fn + " twid_w"), bins
+
+
+def _spec_power(be, x, coef, S, twid_h, twid_w, bins, nbins: int, mask=None, wy=None, wx=None, power=None, dropped=None, p2d=None,
+                ws=None):
+    x, dt, mask, wy, wx = _spec_cube(be, x, mask, wy, wx, "spec_power")
+    T, H, W = x.shape
+    twid_h, twid_w, bins = _spec_tables(be, x, twid_h, twid_w, bins, "spec_power")
+    coef, S = be.vec(coef, None if be.host else 3 * T, "spec_power coef"), be.vec(S, None if be.host else 2 * T, "spec_power S")
+    nbins = int(nbins)
+    power = be.out(power, (T, max(nbins, 0)), be.f64, x, "spec_power power")
+    dropped = be.out(dropped, (T,), be.f64, x, "spec_power dropped")
+    if p2d is not None:
+        be.out(p2d, (T, H, W // 2 + 1), be.f64, x, "spec_power p2d")
+    be.call("gd_spec_power", be.ptr(x), dt, T, H, W, be.ptr(mask), be.ptr(wy), be.ptr(wx), be.ptr(coef), be.ptr(S), be.ptr(twid_h),
+            be.ptr(twid_w), be.ptr(bins), nbins, be.ptr(power), be.ptr(dropped), be.ptr(p2d),
+            *be.ws(ws, spec_power_ws_bytes(T, H, W, nbins), x, "spec_power"))
+    return power, dropped
 
 
 def spec_power(x: Tensor, coef: Tensor, S: Tensor, twid_h: Tensor, twid_w: Tensor, bins: Tensor, nbins: int,
@@ -2411,104 +2361,43 @@ def spec_power(x: Tensor, coef: Tensor, S: Tensor, twid_h: Tensor, twid_w: Tenso
     ``spec_prepare`` and the device copies of the twiddle and bin tables; ``p2d`` (T, H, W // 2 + 1) fp64, when given,
     receives the un-binned power.  Outputs and the uint8 workspace (spec_power_ws_bytes) are allocated unless given.  No
     host sync."""
-    dt = _spec_cube(x, "spec_power input")
-    T, H, W = x.shape
-    _spec_tables(x, twid_h, twid_w, bins, "spec_power")
-    mask = _eval_mask(mask, H * W)
-    _vec(wy, H, "spec_power wy")
-    _vec(wx, W, "spec_power wx")
-    _vec(coef, 3 * T, "spec_power coef")
-    _vec(S, 2 * T, "spec_power S")
-    nbins = int(nbins)
-    power = _out(power, (T, max(nbins, 0)), x, torch.float64, "spec_power power")
-    dropped = _out(dropped, (T,), x, torch.float64, "spec_power dropped")
-    if p2d is not None:
-        _out(p2d, (T, H, W // 2 + 1), x, torch.float64, "spec_power p2d")
-    ws = _ws(ws, spec_power_ws_bytes(T, H, W, nbins), x, "spec_power")
-    L.check(lib().gd_spec_power(_ptr(x), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), _ptr(coef), _ptr(S), _ptr(twid_h), _ptr(twid_w),
-                                _ptr(bins), nbins, _ptr(power), _ptr(dropped), _ptr(p2d), _ptr(ws), ws.numel(), _stream()), "gd_spec_power")
-    return power, dropped
-
-
-def spec_cross(xa: Tensor, xb: Tensor, coef_a: Tensor, S_a: Tensor, coef_b: Tensor, S_b: Tensor, twid_h: Tensor, twid_w: Tensor,
-               bins: Tensor, nbins: int, mask: Optional[Tensor] = None, wy: Optional[Tensor] = None, wx: Optional[Tensor] = None,
-               out: Optional[Tensor] = None, dropped: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-    """(out (4, T, nbins), dropped (T, 4)) fp64: the bin sums of P_aa, P_bb, co and quad of two dense cubes of one shape and
-    dtype.  No host sync."""
-    dt = _spec_cube(xa, "spec_cross input a")
-    if _spec_cube(xb, "spec_cross input b") != dt or xa.shape != xb.shape:
-        raise L.GandanetError(f"spec_cross: a {tuple(xa.shape)} {xa.dtype} vs b {tuple(xb.shape)} {xb.dtype}")
-    T, H, W = xa.shape
-    _spec_tables(xa, twid_h, twid_w, bins, "spec_cross")
-    mask = _eval_mask(mask, H * W)
-    _vec(wy, H, "spec_cross wy")
-    _vec(wx, W, "spec_cross wx")
-    for c, s in ((coef_a, S_a), (coef_b, S_b)):
-        _vec(c, 3 * T, "spec_cross coef")
-        _vec(s, 2 * T, "spec_cross S")
-    nbins = int(nbins)
-    out = _out(out, (4, T, max(nbins, 0)), xa, torch.float64, "spec_cross out")
-    dropped = _out(dropped, (T, 4), xa, torch.float64, "spec_cross dropped")
-    ws = _ws(ws, spec_cross_ws_bytes(T, H, W, nbins), xa, "spec_cross")
-    L.check(lib().gd_spec_cross(_ptr(xa), _ptr(xb), dt, T, H, W, _ptr(mask), _ptr(wy), _ptr(wx), _ptr(coef_a), _ptr(S_a), _ptr(coef_b),
-                                _ptr(S_b), _ptr(twid_h), _ptr(twid_w), _ptr(bins), nbins, _ptr(out), _ptr(dropped), _ptr(ws), ws.numel(),
-                                _stream()), "gd_spec_cross")
-    return out, dropped
-
-
-def _spec_host_args(x, mask, wy, wx, fn: str):
-    x, dt = _host_f(x, fn)
-    if x.ndim != 3:
-        raise L.GandanetError(f"{fn}: expected a (T, H, W) array, got {x.shape}")
-    T, H, W = x.shape
-    return x, dt, _host_vec(mask, H * W, fn + " mask", "uint8"), _host_vec(wy, H, fn + " wy"), _host_vec(wx, W, fn + " wx")
-
-
-def spec_prepare_host(x, mask=None, wy=None, wx=None, detrend: str = "mean"):
-    """``spec_prepare`` on HOST arrays (plain C++ over the same arithmetic, no GPU): (coef (T, 3), S (T, 2))"""
-    import numpy as np
-    x, dt, mask, wy, wx = _spec_host_args(x, mask, wy, wx, "spec_prepare_host")
-    if detrend not in L.SPEC_DETREND:
-        raise L.GandanetError(f"spec_prepare_host: detrend is one of {sorted(L.SPEC_DETREND)}, got {detrend!r}")
-    T, H, W = x.shape
-    coef, S = np.empty((T, 3)), np.empty((T, 2))
-    L.check(lib().gd_spec_prepare_host(x.ctypes.data, dt, T, H, W, _np_ptr(mask), _np_ptr(wy), _np_ptr(wx), L.SPEC_DETREND[detrend],
-                                       coef.ctypes.data, S.ctypes.data), "gd_spec_prepare_host")
-    return coef, S
+    return _spec_power(_DEV, x, coef, S, twid_h, twid_w, bins, nbins, mask, wy, wx, power, dropped, p2d, ws)
 
 
 def spec_power_host(x, coef, S, bins, nbins: int, mask=None, wy=None, wx=None, two_d: bool = False):
-    """``spec_power`` on HOST arrays: (power (T, nbins), dropped (T), p2d (T, H, W // 2 + 1) or None)"""
-    import numpy as np
-    x, dt, mask, wy, wx = _spec_host_args(x, mask, wy, wx, "spec_power_host")
-    T, H, W = x.shape
-    coef, S = np.ascontiguousarray(coef, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
-    bins = np.ascontiguousarray(bins, dtype=np.int32)
-    th, tw = spec_twiddle_host(H), spec_twiddle_host(W)
-    power, dropped = np.empty((T, nbins)), np.empty(T)
+    """``spec_power`` on HOST arrays, with twiddle tables of its own: (power (T, nbins), dropped (T), p2d (T, H, W // 2 + 1)
+    or None)"""
+    T, H, W = _HOST.array(x, "spec_power input", 3)[0].shape
     p2d = np.empty((T, H, W // 2 + 1)) if two_d else None
-    L.check(lib().gd_spec_power_host(x.ctypes.data, dt, T, H, W, _np_ptr(mask), _np_ptr(wy), _np_ptr(wx), coef.ctypes.data, S.ctypes.data,
-                                     th.ctypes.data, tw.ctypes.data, bins.ctypes.data, int(nbins), power.ctypes.data, dropped.ctypes.data,
-                                     _np_ptr(p2d)), "gd_spec_power_host")
-    return power, dropped, p2d
+    return (*_spec_power(_HOST, x, coef, S, spec_twiddle_host(H), spec_twiddle_host(W), bins, nbins, mask, wy, wx, p2d=p2d), p2d)
+
+
+def _spec_cross(be, xa, xb, coef_a, S_a, coef_b, S_b, twid_h, twid_w, bins, nbins: int, mask=None, wy=None, wx=None, out=None,
+                dropped=None, ws=None):
+    xa, dt, mask, wy, wx = _spec_cube(be, xa, mask, wy, wx, "spec_cross")
+    xb, dtb = be.array(xb, "spec_cross input b", 3)
+    if dtb != dt or xa.shape != xb.shape:
+        raise L.GandanetError(f"spec_cross: a {tuple(xa.shape)} {xa.dtype} vs b {tuple(xb.shape)} {xb.dtype}")
+    T, H, W = xa.shape
+    twid_h, twid_w, bins = _spec_tables(be, xa, twid_h, twid_w, bins, "spec_cross")
+    coef_a, coef_b = (be.vec(c, None if be.host else 3 * T, "spec_cross coef") for c in (coef_a, coef_b))
+    S_a, S_b = (be.vec(s, None if be.host else 2 * T, "spec_cross S") for s in (S_a, S_b))
+    nbins = int(nbins)
+    out = be.out(out, (4, T, max(nbins, 0)), be.f64, xa, "spec_cross out")
+    dropped = be.out(dropped, (T, 4), be.f64, xa, "spec_cross dropped")
+    be.call("gd_spec_cross", be.ptr(xa), be.ptr(xb), dt, T, H, W, be.ptr(mask), be.ptr(wy), be.ptr(wx), be.ptr(coef_a), be.ptr(S_a),
+            be.ptr(coef_b), be.ptr(S_b), be.ptr(twid_h), be.ptr(twid_w), be.ptr(bins), nbins, be.ptr(out), be.ptr(dropped),
+            *be.ws(ws, spec_cross_ws_bytes(T, H, W, nbins), xa, "spec_cross"))
+    return out, dropped
+
+
+spec_cross = functools.partial(_spec_cross, _DEV)   # (out (4, T, nbins), dropped (T, 4)) fp64: the bin sums of P_aa, P_bb, co and quad
 
 
 def spec_cross_host(xa, xb, coef_a, S_a, coef_b, S_b, bins, nbins: int, mask=None, wy=None, wx=None):
-    """``spec_cross`` on HOST arrays: (out (4, T, nbins), dropped (T, 4))"""
-    import numpy as np
-    xa, dt, mask, wy, wx = _spec_host_args(xa, mask, wy, wx, "spec_cross_host")
-    xb, dtb = _host_f(xb, "spec_cross_host")
-    if dtb != dt or xb.shape != xa.shape:
-        raise L.GandanetError(f"spec_cross_host: a {xa.shape} {xa.dtype} vs b {xb.shape} {xb.dtype}")
-    T, H, W = xa.shape
-    ca, sa, cb, sb = (np.ascontiguousarray(v, dtype=np.float64) for v in (coef_a, S_a, coef_b, S_b))
-    bins = np.ascontiguousarray(bins, dtype=np.int32)
-    th, tw = spec_twiddle_host(H), spec_twiddle_host(W)
-    out, dropped = np.empty((4, T, nbins)), np.empty((T, 4))
-    L.check(lib().gd_spec_cross_host(xa.ctypes.data, xb.ctypes.data, dt, T, H, W, _np_ptr(mask), _np_ptr(wy), _np_ptr(wx), ca.ctypes.data,
-                                     sa.ctypes.data, cb.ctypes.data, sb.ctypes.data, th.ctypes.data, tw.ctypes.data, bins.ctypes.data,
-                                     int(nbins), out.ctypes.data, dropped.ctypes.data), "gd_spec_cross_host")
-    return out, dropped
+    """``spec_cross`` on HOST arrays, with twiddle tables of its own: (out (4, T, nbins), dropped (T, 4))"""
+    T, H, W = _HOST.array(xa, "spec_cross input", 3)[0].shape
+    return _spec_cross(_HOST, xa, xb, coef_a, S_a, coef_b, S_b, spec_twiddle_host(H), spec_twiddle_host(W), bins, nbins, mask, wy, wx)
 
 
 # ---- drought analysis (include/gandanet.h, "Drought analysis"; drought.hip) --------------------------------------------------
@@ -2517,354 +2406,225 @@ def drought_which(maps) -> int:
     return _which(maps, L.DROUGHT_EV_MAPS, "drought event")
 
 
-def drought_clim(x: Tensor, period: int = 12, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask: Optional[Tensor] = None,
-                 out: Optional[Tensor] = None) -> Tensor:
+def _drought_series(be, x, mask, fn: str):
+    """(x, dtype tag, mask) of a (T, M) array with its optional M uint8 mask"""
+    x, dt = be.array(x, fn + " input", 2)
+    return x, dt, be.vec(mask, x.shape[1], fn + " mask", be.u8)
+
+
+def _drought_clim(be, x, period: int = 12, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask=None, out=None):
     """the (3, period, M) fp64 record (n, mean, M2 per slot) of the M series of a dense fp32 / fp64 ``x`` (T, M) over the
     baseline steps [b0, b1); ``mask``: M uint8.  A new tensor unless ``out`` is given.  No host sync."""
-    dt = _series_2d(x, "drought_clim input")
+    x, dt, mask = _drought_series(be, x, mask, "drought_clim")
     T, M = x.shape
-    b1 = T if b1 is None else b1
-    out = _out(out, (3, int(period), M), x, torch.float64, "drought climatology")
-    L.check(lib().gd_drought_clim(_ptr(x), dt, T, M, int(period), int(phase), int(b0), int(b1), _ptr(_eval_mask(mask, M)), _ptr(out),
-                                  _stream()), "gd_drought_clim")
+    out = be.out(out, (3, max(int(period), 0), M), be.f64, x, "drought climatology")
+    be.call("gd_drought_clim", be.ptr(x), dt, T, M, int(period), int(phase), int(b0), int(T if b1 is None else b1), be.ptr(mask), be.ptr(out))
     return out
 
 
-def drought_index(x: Tensor, clim: Tensor, phase: int = 0, kind: int = L.DROUGHT_STANDARDIZED, ddof: int = 0,
-                  mask: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+drought_clim = functools.partial(_drought_clim, _DEV)
+drought_clim_host = functools.partial(_drought_clim, _HOST)
+
+
+def _drought_index(be, x, clim, phase: int = 0, kind: int = L.DROUGHT_STANDARDIZED, ddof: int = 0, mask=None, out=None):
     """the anomaly or standardised index of a dense fp32 / fp64 ``x`` (T, M) against ``clim`` (3, period, M) fp64, in the
     dtype of ``x``"""
-    dt = _series_2d(x, "drought_index input")
+    x, dt, mask = _drought_series(be, x, mask, "drought_index")
     T, M = x.shape
-    _dense(clim, "drought climatology", torch.float64)
-    if clim.dim() != 3 or clim.shape[0] != 3 or clim.shape[2] != M:
-        raise L.GandanetError(f"drought_index: the climatology is (3, period, {M}) float64, got {tuple(clim.shape)}")
-    out = _out(out, (T, M), x, x.dtype, "drought index")
-    L.check(lib().gd_drought_index(_ptr(x), dt, T, M, _ptr(clim), clim.shape[1], int(phase), int(kind), int(ddof),
-                                   _ptr(_eval_mask(mask, M)), _ptr(out), _stream()), "gd_drought_index")
-    return out
-
-
-def drought_rank(x: Tensor, table: Tensor, period: int = 12, phase: int = 0, b0: int = 0, b1: Optional[int] = None,
-                 mask: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
-    """the rank index of a dense fp32 / fp64 ``x`` (T, M) through ``table`` (nmax, nmax) or (nmax^2) fp64 on the device, in
-    the dtype of ``x``"""
-    dt = _series_2d(x, "drought_rank input")
-    T, M = x.shape
-    b1 = T if b1 is None else b1
-    _dense(table, "drought rank table", torch.float64)
-    nmax = math.isqrt(table.numel())
-    if nmax * nmax != table.numel() or nmax == 0:
-        raise L.GandanetError(f"drought_rank: the table holds nmax^2 doubles, got {table.numel()}")
-    out = _out(out, (T, M), x, x.dtype, "drought rank index")
-    L.check(lib().gd_drought_rank(_ptr(x), dt, T, M, int(period), int(phase), int(b0), int(b1), _ptr(_eval_mask(mask, M)), _ptr(table),
-                                  nmax, _ptr(out), _stream()), "gd_drought_rank")
-    return out
-
-
-def drought_events(index: Tensor, threshold: float, min_duration: int = 3, maps=L.DROUGHT_EV_MAPS, mask: Optional[Tensor] = None,
-                   want_steps: bool = False, out: Optional[Tensor] = None, in_event: Optional[Tensor] = None):
-    """(maps (len(set(maps)), M) fp64 in the order of L.DROUGHT_EV_MAPS, in_event (T, M) uint8 or None) of a dense fp32 /
-    fp64 ``index`` (T, M)"""
-    dt = _series_2d(index, "drought_events input")
-    T, M = index.shape
-    which = drought_which(maps)
-    out = _out(out, (bin(which).count("1"), M), index, torch.float64, "drought event maps")
-    if want_steps or in_event is not None:
-        in_event = _out(in_event, (T, M), index, torch.uint8, "drought in_event")
-    L.check(lib().gd_drought_events(_ptr(index), dt, T, M, float(threshold), int(min_duration), which, _ptr(_eval_mask(mask, M)),
-                                    _ptr(out), _ptr(in_event), _stream()), "gd_drought_events")
-    return out, in_event
-
-
-def drought_exceed(index: Tensor, threshold: float, out: Optional[Tensor] = None) -> Tensor:
-    """1 where ``index`` <= ``threshold``, 0 where not, NaN where NaN, in the dtype of the dense fp32 / fp64 ``index``"""
-    dt = _filter_dtype(index, "drought_exceed input")
-    if index.numel() == 0:
-        raise L.GandanetError("drought_exceed: empty tensor")
-    out = _out(out, index.shape, index, index.dtype, "drought indicator")
-    L.check(lib().gd_drought_exceed(_ptr(index), dt, index.numel(), float(threshold), _ptr(out), _stream()), "gd_drought_exceed")
-    return out
-
-
-def _drought_host_args(x, mask, fn: str):
-    x, dt = _host_f(x, fn)
-    if x.ndim != 2:
-        raise L.GandanetError(f"{fn}: expected a (T, M) array, got {x.shape}")
-    return x, dt, _host_vec(mask, x.shape[1], fn + " mask", "uint8")
-
-
-def drought_clim_host(x, period: int = 12, phase: int = 0, b0: int = 0, b1=None, mask=None):
-    """``drought_clim`` on HOST arrays (plain C++ loops over the same per-series code, no GPU): the (3, period, M) record"""
-    import numpy as np
-    x, dt, mask = _drought_host_args(x, mask, "drought_clim_host")
-    T, M = x.shape
-    out = np.empty((3, max(int(period), 0), M))
-    L.check(lib().gd_drought_clim_host(x.ctypes.data, dt, T, M, int(period), int(phase), int(b0), int(T if b1 is None else b1),
-                                       _np_ptr(mask), out.ctypes.data), "gd_drought_clim_host")
-    return out
-
-
-def drought_index_host(x, clim, phase: int = 0, kind: int = L.DROUGHT_STANDARDIZED, ddof: int = 0, mask=None):
-    """``drought_index`` on HOST arrays"""
-    import numpy as np
-    x, dt, mask = _drought_host_args(x, mask, "drought_index_host")
-    T, M = x.shape
-    clim = np.ascontiguousarray(clim, dtype=np.float64)
+    clim = be.dense(clim, "drought climatology", be.f64)
     if clim.ndim != 3 or clim.shape[0] != 3 or clim.shape[2] != M:
-        raise L.GandanetError(f"drought_index_host: the climatology is (3, period, {M}), got {clim.shape}")
-    out = np.empty_like(x)
-    L.check(lib().gd_drought_index_host(x.ctypes.data, dt, T, M, clim.ctypes.data, clim.shape[1], int(phase), int(kind), int(ddof),
-                                        _np_ptr(mask), out.ctypes.data), "gd_drought_index_host")
+        raise L.GandanetError(f"drought_index: the climatology is (3, period, {M}) float64, got {tuple(clim.shape)}")
+    out = be.out(out, (T, M), x.dtype, x, "drought index")
+    be.call("gd_drought_index", be.ptr(x), dt, T, M, be.ptr(clim), clim.shape[1], int(phase), int(kind), int(ddof), be.ptr(mask), be.ptr(out))
     return out
 
 
-def drought_rank_host(x, table, period: int = 12, phase: int = 0, b0: int = 0, b1=None, mask=None):
-    """``drought_rank`` on HOST arrays"""
-    import numpy as np
-    x, dt, mask = _drought_host_args(x, mask, "drought_rank_host")
+drought_index = functools.partial(_drought_index, _DEV)
+drought_index_host = functools.partial(_drought_index, _HOST)
+
+
+def _drought_rank(be, x, table, period: int = 12, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask=None, out=None):
+    """the rank index of a dense fp32 / fp64 ``x`` (T, M) through ``table`` (nmax, nmax) or (nmax^2) fp64, in the dtype of
+    ``x``"""
+    x, dt, mask = _drought_series(be, x, mask, "drought_rank")
     T, M = x.shape
-    table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
-    nmax = math.isqrt(table.size)
-    if nmax * nmax != table.size or nmax == 0:
-        raise L.GandanetError(f"drought_rank_host: the table holds nmax^2 doubles, got {table.size}")
-    out = np.empty_like(x)
-    L.check(lib().gd_drought_rank_host(x.ctypes.data, dt, T, M, int(period), int(phase), int(b0), int(T if b1 is None else b1),
-                                       _np_ptr(mask), table.ctypes.data, nmax, out.ctypes.data), "gd_drought_rank_host")
+    table = be.vec(table, None, "drought rank table")
+    nmax = math.isqrt(math.prod(table.shape))
+    if nmax * nmax != math.prod(table.shape) or nmax == 0:
+        raise L.GandanetError(f"drought_rank: the table holds nmax^2 doubles, got {math.prod(table.shape)}")
+    out = be.out(out, (T, M), x.dtype, x, "drought rank index")
+    be.call("gd_drought_rank", be.ptr(x), dt, T, M, int(period), int(phase), int(b0), int(T if b1 is None else b1), be.ptr(mask),
+            be.ptr(table), nmax, be.ptr(out))
     return out
 
 
-def drought_events_host(index, threshold: float, min_duration: int = 3, maps=L.DROUGHT_EV_MAPS, mask=None, want_steps: bool = False):
-    """``drought_events`` on HOST arrays: (dict name -> (M) array, in_event (T, M) uint8 or None)"""
-    import numpy as np
-    x, dt, mask = _drought_host_args(index, mask, "drought_events_host")
+drought_rank = functools.partial(_drought_rank, _DEV)
+drought_rank_host = functools.partial(_drought_rank, _HOST)
+
+
+def _drought_events(be, index, threshold: float, min_duration: int = 3, maps=L.DROUGHT_EV_MAPS, mask=None, want_steps: bool = False,
+                    out=None, in_event=None):
+    """(maps, in_event (T, M) uint8 or None) of a dense fp32 / fp64 ``index`` (T, M); the maps in the order of
+    L.DROUGHT_EV_MAPS: on the device (len(set(maps)), M) fp64, on the host a dict name -> (M) array"""
+    x, dt, mask = _drought_series(be, index, mask, "drought_events")
     T, M = x.shape
     which = drought_which(maps)
     names = _which_names(which, L.DROUGHT_EV_MAPS)
-    out = np.empty((len(names), M))
-    steps = np.empty((T, M), dtype=np.uint8) if want_steps else None
-    L.check(lib().gd_drought_events_host(x.ctypes.data, dt, T, M, float(threshold), int(min_duration), which, _np_ptr(mask),
-                                         out.ctypes.data, _np_ptr(steps)), "gd_drought_events_host")
-    return dict(zip(names, out)), steps
+    out = be.out(out, (len(names), M), be.f64, x, "drought event maps")
+    if want_steps or in_event is not None:
+        in_event = be.out(in_event, (T, M), be.u8, x, "drought in_event")
+    be.call("gd_drought_events", be.ptr(x), dt, T, M, float(threshold), int(min_duration), which, be.ptr(mask), be.ptr(out),
+            be.ptr(in_event))
+    return (dict(zip(names, out)) if be.host else out), in_event
 
 
-def drought_exceed_host(index, threshold: float):
-    """``drought_exceed`` on a HOST array"""
-    import numpy as np
-    x, dt = _host_f(index, "drought_exceed_host")
-    out = np.empty_like(x)
-    L.check(lib().gd_drought_exceed_host(x.ctypes.data, dt, x.size, float(threshold), out.ctypes.data), "gd_drought_exceed_host")
+drought_events = functools.partial(_drought_events, _DEV)
+drought_events_host = functools.partial(_drought_events, _HOST)
+
+
+def _drought_exceed(be, index, threshold: float, out=None):
+    """1 where ``index`` <= ``threshold``, 0 where not, NaN where NaN, in the dtype of the dense fp32 / fp64 ``index``"""
+    x, dt = be.array(index, "drought_exceed input")
+    out = be.out(out, x.shape, x.dtype, x, "drought indicator")
+    be.call("gd_drought_exceed", be.ptr(x), dt, math.prod(x.shape), float(threshold), be.ptr(out))
     return out
 
 
+drought_exceed = functools.partial(_drought_exceed, _DEV)
+drought_exceed_host = functools.partial(_drought_exceed, _HOST)
+
+
 # ---- connected components (include/gandanet.h, "Connected components"; ccl.hip) ------------------------------------------------
-def _ccl_cube(x: Tensor, name: str) -> int:
-    """the dtype tag of a dense (T, H, W) fp32 / fp64 / uint8 device cube"""
-    if not isinstance(x, Tensor) or not x.is_cuda:
-        raise L.GandanetError(f"{name}: expected a GPU tensor (there is no CPU path)")
-    if x.dtype not in (torch.float32, torch.float64, torch.uint8):
-        raise L.GandanetError(f"{name}: expected float32, float64 or uint8, got {x.dtype}")
-    if x.dim() != 3 or x.numel() == 0 or not x.is_contiguous():
-        raise L.GandanetError(f"{name}: expected a dense non-empty (T, H, W) cube, got {tuple(x.shape)} with strides {x.stride()}")
-    return L.CCL_U8 if x.dtype == torch.uint8 else (L.FILTER_F64 if x.dtype == torch.float64 else L.FILTER_F32)
-
-
-def _ccl_ints(t: Tensor, shape, name: str) -> Tensor:
-    _dense(t, name, torch.int32)
-    if shape is not None and tuple(t.shape) != tuple(shape):
+def _ccl_ints(be, t, shape, name: str):
+    """a dense int32 array; the device side holds it to ``shape`` where one is given, the host twins take the shape on trust"""
+    t = be.dense(t, name, be.i32)
+    if shape is not None and not be.host and tuple(t.shape) != tuple(shape):
         raise L.GandanetError(f"{name}: expected a dense {tuple(shape)} int32 tensor, got {tuple(t.shape)}")
     return t
 
 
-def _ccl_ws(ws: Optional[Tensor], n: int, like: Tensor, name: str):
-    nbytes = lib().gd_ccl_ws_bytes(int(n))
-    ws = _ws(ws, nbytes, like, name)
-    return ws, ws.numel()
+def _ccl_ws(be, ws, n: int, like, name: str):
+    return be.ws(ws, lib().gd_ccl_ws_bytes(int(n)), like, name)
 
 
-def ccl_label(x: Tensor, threshold: float = 0.0, structure: int = 0, mask: Optional[Tensor] = None, tiles: bool = True,
-              out: Optional[Tensor] = None) -> Tensor:
+def _ccl_label(be, x, threshold: float = 0.0, structure: int = 0, mask=None, tiles: bool = True, out=None):
     """parent (T, H, W) int32 of a dense fp32 / fp64 / uint8 cube: the smallest raster index of every voxel's component, -1
-    on background.  ``structure``: the 13-bit word of backward offsets; ``tiles=False`` skips the LDS tile stage."""
-    dt = _ccl_cube(x, "ccl_label input")
+    on background.  ``structure``: the 13-bit word of backward offsets; ``tiles=False`` skips the LDS tile stage.  The host
+    twin is a sequential union-find over the same code."""
+    x, dt = be.array(x, "ccl_label input", 3, u8=True)
     T, H, W = x.shape
-    out = _out(out, (T, H, W), x, torch.int32, "ccl parent")
-    L.check(lib().gd_ccl_label(_ptr(x), dt, T, H, W, float(threshold), _ptr(_eval_mask(mask, H * W)), int(structure),
-                               0 if tiles else L.CCL_NO_TILES, _ptr(out), _stream()), "gd_ccl_label")
+    mask = be.vec(mask, H * W, "ccl_label mask", be.u8)
+    out = be.out(out, (T, H, W), be.i32, x, "ccl parent")
+    be.call("gd_ccl_label", be.ptr(x), dt, T, H, W, float(threshold), be.ptr(mask), int(structure), 0 if tiles else L.CCL_NO_TILES,
+            be.ptr(out))
     return out
 
 
-def ccl_filter(parent: Tensor, min_size: int, ws: Optional[Tensor] = None) -> Tensor:
-    """components of fewer than ``min_size`` voxels become background (-1), in place"""
-    _ccl_ints(parent, None, "ccl parent")
-    ws, nbytes = _ccl_ws(ws, parent.numel(), parent, "ccl_filter")
-    L.check(lib().gd_ccl_filter(_ptr(parent), parent.numel(), int(min_size), _ptr(ws), nbytes, _stream()), "gd_ccl_filter")
+ccl_label = functools.partial(_ccl_label, _DEV)
+ccl_label_host = functools.partial(_ccl_label, _HOST)
+
+
+def _ccl_filter(be, parent, min_size: int, ws=None):
+    """components of fewer than ``min_size`` voxels become background (-1): in place on the device, in a copy on the host"""
+    parent = np.array(parent, dtype=np.int32, order="C") if be.host else _ccl_ints(be, parent, None, "ccl parent")
+    n = math.prod(parent.shape)
+    be.call("gd_ccl_filter", be.ptr(parent), n, int(min_size), *_ccl_ws(be, ws, n, parent, "ccl_filter"))
     return parent
 
 
-def ccl_relabel(parent: Tensor, out: Optional[Tensor] = None, count: Optional[Tensor] = None, ws: Optional[Tensor] = None):
-    """(labels int32 of the shape of ``parent``, count (1,) int32 on the device): 0 on background, 1 .. K in raster order of
-    each component's first voxel.  ``out`` may be ``parent`` itself."""
-    _ccl_ints(parent, None, "ccl parent")
-    out = _ccl_ints(out, parent.shape, "ccl labels") if out is not None else torch.empty_like(parent)
-    count = _ccl_ints(count, (1,), "ccl count") if count is not None else torch.empty(1, device=parent.device, dtype=torch.int32)
-    ws, nbytes = _ccl_ws(ws, parent.numel(), parent, "ccl_relabel")
-    L.check(lib().gd_ccl_relabel(_ptr(parent), parent.numel(), _ptr(out), _ptr(count), _ptr(ws), nbytes, _stream()), "gd_ccl_relabel")
-    return out, count
+ccl_filter = functools.partial(_ccl_filter, _DEV)
+ccl_filter_host = functools.partial(_ccl_filter, _HOST)
 
 
-def ccl_bounds(labels: Tensor, K: int, out: Optional[Tensor] = None) -> Tensor:
+def _ccl_relabel(be, parent, out=None, count=None, ws=None):
+    """(labels int32 of the shape of ``parent``, count): 0 on background, 1 .. K in raster order of each component's first
+    voxel; the count is a (1,) int32 tensor on the device, an int on the host.  ``out`` may be ``parent`` itself."""
+    parent = _ccl_ints(be, parent, None, "ccl parent")
+    n = math.prod(parent.shape)
+    out = be.empty(parent.shape, be.i32, parent) if out is None else _ccl_ints(be, out, parent.shape, "ccl labels")
+    count = be.empty((1,), be.i32, parent) if count is None else _ccl_ints(be, count, (1,), "ccl count")
+    be.call("gd_ccl_relabel", be.ptr(parent), n, be.ptr(out), be.ptr(count), *_ccl_ws(be, ws, n, parent, "ccl_relabel"))
+    return out, (int(count[0]) if be.host else count)
+
+
+ccl_relabel = functools.partial(_ccl_relabel, _DEV)
+ccl_relabel_host = functools.partial(_ccl_relabel, _HOST)
+
+
+def _ccl_bounds(be, labels, K: int, out=None):
     """(K, 7) int32: n, t0, t1, h0, h1, w0, w1 of the labels 1 .. K of a dense (T, H, W) int32 cube"""
-    _ccl_ints(labels, None, "ccl labels")
-    if labels.dim() != 3:
+    labels = _ccl_ints(be, labels, None, "ccl labels")
+    if labels.ndim != 3:
         raise L.GandanetError(f"ccl_bounds: expected a (T, H, W) label cube, got {tuple(labels.shape)}")
     T, H, W = labels.shape
-    out = _out(out, (int(K), len(L.CCL_BOUNDS)), labels, torch.int32, "ccl bounds")
-    L.check(lib().gd_ccl_bounds(_ptr(labels), T, H, W, int(K), _ptr(out), _stream()), "gd_ccl_bounds")
+    out = be.out(out, (max(int(K), 0), len(L.CCL_BOUNDS)), be.i32, labels, "ccl bounds")
+    be.call("gd_ccl_bounds", be.ptr(labels), T, H, W, int(K), be.ptr(out))
     return out
 
 
-def ccl_offsets(bounds: Tensor, out: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> Tensor:
+ccl_bounds = functools.partial(_ccl_bounds, _DEV)
+ccl_bounds_host = functools.partial(_ccl_bounds, _HOST)
+
+
+def _ccl_offsets(be, bounds, out=None, ws=None):
     """(K + 1) int32: the exclusive prefix sum of the clusters' durations; the last entry is the number of track records"""
-    _ccl_ints(bounds, None, "ccl bounds")
+    bounds = _ccl_ints(be, bounds, None, "ccl bounds")
     K = bounds.shape[0]
-    out = _out(out, (K + 1,), bounds, torch.int32, "ccl offsets")
-    ws, nbytes = _ccl_ws(ws, K, bounds, "ccl_offsets")
-    L.check(lib().gd_ccl_offsets(_ptr(bounds), K, _ptr(out), _ptr(ws), nbytes, _stream()), "gd_ccl_offsets")
+    out = be.out(out, (K + 1,), be.i32, bounds, "ccl offsets")
+    be.call("gd_ccl_offsets", be.ptr(bounds), K, be.ptr(out), *_ccl_ws(be, ws, K, bounds, "ccl_offsets"))
     return out
 
 
-def ccl_tracks(x: Optional[Tensor], labels: Tensor, bounds: Tensor, offsets: Tensor, R: int, threshold: float = 0.0,
-               weights: Optional[Tensor] = None, severity: bool = True):
+ccl_offsets = functools.partial(_ccl_offsets, _DEV)
+ccl_offsets_host = functools.partial(_ccl_offsets, _HOST)
+
+
+def _ccl_tracks(be, x, labels, bounds, offsets, R: int, threshold: float = 0.0, weights=None, severity: bool = True):
     """(tracks (R, 6) fp64, index (R, 2) int32) of the labelled clusters of the cube ``x`` (None or uint8: count and area only)"""
-    _ccl_ints(labels, None, "ccl labels")
+    labels = _ccl_ints(be, labels, None, "ccl labels")
     T, H, W = labels.shape
-    dt = L.CCL_U8 if x is None else _ccl_cube(x, "ccl_tracks input")
-    if x is not None and tuple(x.shape) != (T, H, W):
-        raise L.GandanetError(f"ccl_tracks: the cube is {tuple(x.shape)}, the labels {tuple(labels.shape)}")
-    K = bounds.shape[0]
-    _ccl_ints(bounds, (K, len(L.CCL_BOUNDS)), "ccl bounds")
-    _ccl_ints(offsets, (K + 1,), "ccl offsets")
-    weights = _vec(weights, H * W, "ccl weights")
-    tracks = torch.empty((int(R), len(L.CCL_TRACK)), device=labels.device, dtype=torch.float64)
-    index = torch.empty((int(R), 2), device=labels.device, dtype=torch.int32)
-    L.check(lib().gd_ccl_tracks(_ptr(x), dt, T, H, W, float(threshold), _ptr(labels), _ptr(bounds), _ptr(offsets), K, int(R), _ptr(weights),
-                                L.CCL_SEVERITY if severity else 0, _ptr(tracks), _ptr(index), _stream()), "gd_ccl_tracks")
+    dt = L.CCL_U8
+    if x is not None:
+        x, dt = be.array(x, "ccl_tracks input", 3, u8=True)
+        if not be.host and tuple(x.shape) != (T, H, W):                          # the host twin takes the cube's shape on trust
+            raise L.GandanetError(f"ccl_tracks: the cube is {tuple(x.shape)}, the labels {tuple(labels.shape)}")
+    K = len(bounds)
+    bounds, offsets = _ccl_ints(be, bounds, (K, len(L.CCL_BOUNDS)), "ccl bounds"), _ccl_ints(be, offsets, (K + 1,), "ccl offsets")
+    weights = be.vec(weights, H * W, "ccl weights")
+    tracks, index = be.empty((int(R), len(L.CCL_TRACK)), be.f64, labels), be.empty((int(R), 2), be.i32, labels)
+    be.call("gd_ccl_tracks", be.ptr(x), dt, T, H, W, float(threshold), be.ptr(labels), be.ptr(bounds), be.ptr(offsets), K, int(R),
+            be.ptr(weights), L.CCL_SEVERITY if severity else 0, be.ptr(tracks), be.ptr(index))
     return tracks, index
 
 
-def ccl_totals(tracks: Tensor, bounds: Tensor, offsets: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """(K, 8) fp64: volume, severity, peak_area, peak_area_step, peak, centroid t, h, w of every cluster"""
-    K = bounds.shape[0]
-    _dense(tracks, "ccl tracks", torch.float64)
-    _ccl_ints(bounds, (K, len(L.CCL_BOUNDS)), "ccl bounds")
-    _ccl_ints(offsets, (K + 1,), "ccl offsets")
-    out = _out(out, (K, len(L.CCL_TOTALS)), tracks, torch.float64, "ccl totals")
-    L.check(lib().gd_ccl_totals(_ptr(tracks), _ptr(bounds), _ptr(offsets), K, _ptr(out), _stream()), "gd_ccl_totals")
-    return out
-
-
-def _ccl_host_cube(x, fn: str):
-    import numpy as np
-    x = np.ascontiguousarray(x)
-    if x.dtype not in (np.float32, np.float64, np.uint8) or x.ndim != 3 or x.size == 0:
-        raise L.GandanetError(f"{fn}: expected a non-empty (T, H, W) float32 / float64 / uint8 array, got {x.dtype} {x.shape}")
-    return x, (L.CCL_U8 if x.dtype == np.uint8 else (L.FILTER_F64 if x.dtype == np.float64 else L.FILTER_F32))
-
-
-def ccl_label_host(x, threshold: float = 0.0, structure: int = 0, mask=None, tiles: bool = True):
-    """``ccl_label`` on a HOST array (a sequential union-find over the same code, no GPU)"""
-    import numpy as np
-    x, dt = _ccl_host_cube(x, "ccl_label_host")
-    T, H, W = x.shape
-    mask = _host_vec(mask, H * W, "ccl_label_host mask", "uint8")
-    out = np.empty((T, H, W), dtype=np.int32)
-    L.check(lib().gd_ccl_label_host(x.ctypes.data, dt, T, H, W, float(threshold), _np_ptr(mask), int(structure),
-                                    0 if tiles else L.CCL_NO_TILES, out.ctypes.data), "gd_ccl_label_host")
-    return out
-
-
-def ccl_filter_host(parent, min_size: int):
-    """``ccl_filter`` on a HOST array: a filtered copy"""
-    import numpy as np
-    parent = np.array(parent, dtype=np.int32, order="C")
-    L.check(lib().gd_ccl_filter_host(parent.ctypes.data, parent.size, int(min_size)), "gd_ccl_filter_host")
-    return parent
-
-
-def ccl_relabel_host(parent):
-    """``ccl_relabel`` on a HOST array: (labels, K)"""
-    import numpy as np
-    parent = np.ascontiguousarray(parent, dtype=np.int32)
-    out, count = np.empty_like(parent), np.zeros(1, dtype=np.int32)
-    L.check(lib().gd_ccl_relabel_host(parent.ctypes.data, parent.size, out.ctypes.data, count.ctypes.data), "gd_ccl_relabel_host")
-    return out, int(count[0])
-
-
-def ccl_bounds_host(labels, K: int):
-    """``ccl_bounds`` on a HOST array"""
-    import numpy as np
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    T, H, W = labels.shape
-    out = np.empty((max(int(K), 0), len(L.CCL_BOUNDS)), dtype=np.int32)
-    L.check(lib().gd_ccl_bounds_host(labels.ctypes.data, T, H, W, int(K), out.ctypes.data), "gd_ccl_bounds_host")
-    return out
-
-
-def ccl_offsets_host(bounds):
-    """``ccl_offsets`` on a HOST array"""
-    import numpy as np
-    bounds = np.ascontiguousarray(bounds, dtype=np.int32)
-    out = np.empty(bounds.shape[0] + 1, dtype=np.int32)
-    L.check(lib().gd_ccl_offsets_host(bounds.ctypes.data, bounds.shape[0], out.ctypes.data), "gd_ccl_offsets_host")
-    return out
+ccl_tracks = functools.partial(_ccl_tracks, _DEV)
 
 
 def ccl_tracks_host(x, labels, bounds, offsets, threshold: float = 0.0, weights=None, severity: bool = True):
     """``ccl_tracks`` on HOST arrays: (tracks (R, 6), index (R, 2)), R = offsets[-1]"""
-    import numpy as np
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    T, H, W = labels.shape
-    dt = L.CCL_U8
-    if x is not None:
-        x, dt = _ccl_host_cube(x, "ccl_tracks_host")
-    bounds, offsets = np.ascontiguousarray(bounds, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.int32)
-    K, R = bounds.shape[0], int(offsets[-1])
-    weights = _host_vec(weights, H * W, "ccl_tracks_host weights")
-    tracks, index = np.empty((R, len(L.CCL_TRACK))), np.empty((R, 2), dtype=np.int32)
-    L.check(lib().gd_ccl_tracks_host(None if x is None else x.ctypes.data, dt, T, H, W, float(threshold), labels.ctypes.data,
-                                     bounds.ctypes.data, offsets.ctypes.data, K, R, _np_ptr(weights), L.CCL_SEVERITY if severity else 0,
-                                     tracks.ctypes.data, index.ctypes.data), "gd_ccl_tracks_host")
-    return tracks, index
+    return _ccl_tracks(_HOST, x, labels, bounds, offsets, int(np.asarray(offsets).reshape(-1)[-1]), threshold, weights, severity)
 
 
-def ccl_totals_host(tracks, bounds, offsets):
-    """``ccl_totals`` on HOST arrays"""
-    import numpy as np
-    tracks = np.ascontiguousarray(tracks, dtype=np.float64)
-    bounds, offsets = np.ascontiguousarray(bounds, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.int32)
-    out = np.empty((bounds.shape[0], len(L.CCL_TOTALS)))
-    L.check(lib().gd_ccl_totals_host(tracks.ctypes.data, bounds.ctypes.data, offsets.ctypes.data, bounds.shape[0], out.ctypes.data),
-            "gd_ccl_totals_host")
+def _ccl_totals(be, tracks, bounds, offsets, out=None):
+    """(K, 8) fp64: volume, severity, peak_area, peak_area_step, peak, centroid t, h, w of every cluster"""
+    K = len(bounds)
+    tracks = be.dense(tracks, "ccl tracks", be.f64)
+    bounds, offsets = _ccl_ints(be, bounds, (K, len(L.CCL_BOUNDS)), "ccl bounds"), _ccl_ints(be, offsets, (K + 1,), "ccl offsets")
+    out = be.out(out, (K, len(L.CCL_TOTALS)), be.f64, tracks, "ccl totals")
+    be.call("gd_ccl_totals", be.ptr(tracks), be.ptr(bounds), be.ptr(offsets), K, be.ptr(out))
     return out
+
+
+ccl_totals = functools.partial(_ccl_totals, _DEV)
+ccl_totals_host = functools.partial(_ccl_totals, _HOST)
 
 
 # ---- neighbourhood verification (include/gandanet.h, "Neighbourhood verification"; neighborhood.hip) ----------------------------
 NBR_WS_BUDGET = 256 << 20   # bytes of tables and partials in flight when the caller gives no workspace
 
 
-def _nbr_cube(x: Tensor, name: str) -> int:
-    if not isinstance(x, Tensor):
-        raise L.GandanetError(f"{name}: expected a GPU tensor (there is no CPU path)")
-    dt = _filter_dtype(x, name)
-    if x.dim() != 3 or x.numel() == 0:
-        raise L.GandanetError(f"{name}: expected a dense non-empty (T, H, W) cube, got {tuple(x.shape)}")
-    return dt
-
-
 def _nbr_thresholds(thr, T: int, name: str):
     """the (T, K) fp64 HOST table of ``thr``: (K,) entries hold at every step"""
-    import numpy as np
     a = np.asarray(thr.detach().cpu() if isinstance(thr, Tensor) else thr, dtype=np.float64)
     if a.ndim == 0:
         a = a.reshape(1)
@@ -2877,7 +2637,6 @@ def _nbr_thresholds(thr, T: int, name: str):
 
 def _nbr_step_thresholds(thr, T: int, name: str):
     """the (T,) fp64 HOST vector of one threshold, or of one per step"""
-    import numpy as np
     a = np.asarray(thr.detach().cpu() if isinstance(thr, Tensor) else thr, dtype=np.float64).reshape(-1)
     if a.size not in (1, T):
         raise L.GandanetError(f"{name}: one threshold, or one per step ({T}), got {a.size}")
@@ -2885,7 +2644,6 @@ def _nbr_step_thresholds(thr, T: int, name: str):
 
 
 def _nbr_scales(scales):
-    import numpy as np
     seq = [scales] if isinstance(scales, (int, np.integer)) else list(scales)
     if any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 1 << 31 for n in seq):
         raise L.GandanetError(f"scales: expected integer window widths, got {scales!r}")
@@ -2902,107 +2660,75 @@ def nbr_ws_bytes(H: int, W: int, K: int, planes: int = 1) -> int:
     return int(lib().gd_nbr_ws_bytes(int(H), int(W), int(K), int(planes)))
 
 
-def _nbr_ws(ws: Optional[Tensor], like: Tensor, T: int, H: int, W: int, K: int, planes: Optional[int], name: str):
+def _nbr_ws(be, ws, like, T: int, H: int, W: int, K: int, planes: Optional[int], name: str):
+    """the workspace arguments for ``planes`` steps in flight (default: NBR_WS_BUDGET bytes of them)"""
     one = nbr_ws_bytes(H, W, K, 1)
     if planes is None:
         planes = max(1, min(T, NBR_WS_BUDGET // max(one, 1)))
-    ws = _ws(ws, one * max(1, min(int(planes), T)), like, name)
-    return ws, ws.numel()
+    return be.ws(ws, one * max(1, min(int(planes), T)), like, name)
 
 
-def nbr_fss(f: Tensor, o: Tensor, thr_f, thr_o, scales, below: bool = True, normalize: str = "window", maps: bool = False,
-            mask: Optional[Tensor] = None, ws: Optional[Tensor] = None, planes: Optional[int] = None):
+def _nbr_fss(be, f, o, thr_f, thr_o, scales, below: bool = True, normalize: str = "window", maps: bool = False, mask=None, ws=None,
+             planes: Optional[int] = None):
     """(sums (T, K, S, 3), base (T, K, 3), maps (K, S, H, W, 3) or None) of two dense fp32 / fp64 cubes (T, H, W) of one
-    dtype, all on the device: int64 tensors holding the unsigned 64-bit records (every value is below 2^61), or fp64
-    ``sums`` and ``maps`` with ``normalize="valid"``.  ``thr_f``, ``thr_o``: (K,) or (T, K) thresholds on the HOST; ``scales``:
+    dtype: the unsigned 64-bit records (every value is below 2^61; int64 tensors on the device, uint64 arrays on the host), or
+    fp64 ``sums`` and ``maps`` with ``normalize="valid"``.  ``thr_f``, ``thr_o``: (K,) or (T, K) thresholds on the HOST; ``scales``:
     odd widths; ``mask``: H W uint8.  ``planes`` steps in flight (default: NBR_WS_BUDGET bytes of them).  No host sync."""
-    dt = _nbr_cube(f, "nbr_fss forecast")
-    if not isinstance(o, Tensor) or o.dtype != f.dtype or _nbr_cube(o, "nbr_fss observed") != dt or o.shape != f.shape:
-        raise L.GandanetError(f"nbr_fss: forecast {tuple(f.shape)} {f.dtype} against observed "
-                              f"{tuple(getattr(o, 'shape', ()))} {getattr(o, 'dtype', type(o))}")
+    f, dt = be.array(f, "nbr_fss forecast", 3)
+    o, dt2 = be.array(o, "nbr_fss observed", 3)
+    if dt2 != dt or o.shape != f.shape:
+        raise L.GandanetError(f"nbr_fss: forecast {tuple(f.shape)} {f.dtype} against observed {tuple(o.shape)} {o.dtype}")
     T, H, W = f.shape
-    tf = _nbr_thresholds(thr_f, T, "nbr_fss thresholds")
-    to = _nbr_thresholds(thr_o, T, "nbr_fss observed thresholds")
+    tf, to = _nbr_thresholds(thr_f, T, "nbr_fss thresholds"), _nbr_thresholds(thr_o, T, "nbr_fss observed thresholds")
     if tf.shape != to.shape:
         raise L.GandanetError(f"nbr_fss: thresholds {tf.shape} against observed thresholds {to.shape}")
     K, sc, mode = tf.shape[1], _nbr_scales(scales), _nbr_normalize(normalize)
-    S = sc.size
-    kind = torch.float64 if mode else torch.int64
-    rec = torch.empty(T * K * (S + 1) * 3, device=f.device, dtype=torch.int64)
-    n_s = T * K * S * 3
-    out = torch.empty((K, S, H, W, 3), device=f.device, dtype=kind) if maps else None
-    ws, nbytes = _nbr_ws(ws, f, T, H, W, K, planes, "nbr_fss")
-    L.check(lib().gd_nbr_fss(_ptr(f), _ptr(o), dt, T, H, W, _ptr(_eval_mask(mask, H * W)), tf.ctypes.data, to.ctypes.data, K, int(bool(below)),
-                             sc.ctypes.data, S, mode, rec.data_ptr(), rec.data_ptr() + 8 * n_s, _ptr(out), _ptr(ws), nbytes, _stream()),
-            "gd_nbr_fss")
-    return rec[:n_s].view(kind).view(T, K, S, 3), rec[n_s:].view(T, K, 3), out
-
-
-def nbr_fraction(x: Tensor, thr, scale: int, below: bool = True, normalize: str = "window", mask: Optional[Tensor] = None,
-                 out: Optional[Tensor] = None, ws: Optional[Tensor] = None, planes: Optional[int] = None) -> Tensor:
-    """the (T, H, W) fp64 neighbourhood fraction of a dense fp32 / fp64 cube at the odd width ``scale``; ``thr``: one
-    threshold or one per step, on the HOST"""
-    dt = _nbr_cube(x, "nbr_fraction input")
-    T, H, W = x.shape
-    th = _nbr_step_thresholds(thr, T, "nbr_fraction threshold")
-    sc = _nbr_scales(scale)
-    if sc.size != 1:
-        raise L.GandanetError(f"nbr_fraction: one scale, got {scale!r}")
-    out = _out(out, (T, H, W), x, torch.float64, "neighbourhood fraction")
-    ws, nbytes = _nbr_ws(ws, x, T, H, W, 1, planes, "nbr_fraction")
-    L.check(lib().gd_nbr_fraction(_ptr(x), dt, T, H, W, _ptr(_eval_mask(mask, H * W)), th.ctypes.data, int(bool(below)), int(sc[0]),
-                                  _nbr_normalize(normalize), _ptr(out), _ptr(ws), nbytes, _stream()), "gd_nbr_fraction")
-    return out
-
-
-def _nbr_host_cube(x, fn: str):
-    x, dt = _host_f(x, fn)
-    if x.ndim != 3:
-        raise L.GandanetError(f"{fn}: expected a (T, H, W) array, got {x.shape}")
-    return x, dt
-
-
-def nbr_fss_host(f, o, thr_f, thr_o, scales, below: bool = True, normalize: str = "window", maps: bool = False, mask=None):
-    """``nbr_fss`` on HOST arrays (plain C++ over the same per-pixel code, in the device's order of sums, no GPU): (sums
-    (T, K, S, 3) uint64 or fp64, base (T, K, 3) uint64, maps (K, S, H, W, 3) or None)"""
-    import numpy as np
-    f, dt = _nbr_host_cube(f, "nbr_fss_host")
-    o, dt2 = _nbr_host_cube(o, "nbr_fss_host")
-    if dt != dt2 or f.shape != o.shape:
-        raise L.GandanetError(f"nbr_fss_host: forecast {f.shape} {f.dtype} against observed {o.shape} {o.dtype}")
-    T, H, W = f.shape
-    tf, to = _nbr_thresholds(thr_f, T, "nbr_fss_host thresholds"), _nbr_thresholds(thr_o, T, "nbr_fss_host observed thresholds")
-    if tf.shape != to.shape:
-        raise L.GandanetError(f"nbr_fss_host: thresholds {tf.shape} against observed thresholds {to.shape}")
-    K, sc, mode = tf.shape[1], _nbr_scales(scales), _nbr_normalize(normalize)
-    kind = np.float64 if mode else np.uint64
-    mask = _host_vec(mask, H * W, "nbr_fss_host mask", "uint8")
-    sums, base = np.empty((T, K, sc.size, 3), dtype=kind), np.empty((T, K, 3), dtype=np.uint64)
-    out = np.empty((K, sc.size, H, W, 3), dtype=kind) if maps else None
-    L.check(lib().gd_nbr_fss_host(f.ctypes.data, o.ctypes.data, dt, T, H, W, _np_ptr(mask), tf.ctypes.data, to.ctypes.data, K, int(bool(below)),
-                                  sc.ctypes.data, sc.size, mode, sums.ctypes.data, base.ctypes.data, _np_ptr(out)), "gd_nbr_fss_host")
+    S, n_s = sc.size, T * K * sc.size * 3
+    mask = be.vec(mask, H * W, "nbr_fss mask", be.u8)
+    if be.host:
+        kind = np.float64 if mode else np.uint64
+        sums, base = np.empty((T, K, S, 3), dtype=kind), np.empty((T, K, 3), dtype=np.uint64)
+        p_sums, p_base = sums.ctypes.data, base.ctypes.data
+    else:                                                                        # one int64 buffer behind both records
+        kind = torch.float64 if mode else torch.int64
+        rec = torch.empty(n_s + T * K * 3, device=f.device, dtype=torch.int64)
+        sums, base = rec[:n_s].view(kind).view(T, K, S, 3), rec[n_s:].view(T, K, 3)
+        p_sums, p_base = rec.data_ptr(), rec.data_ptr() + 8 * n_s
+    out = be.empty((K, S, H, W, 3), kind, f) if maps else None
+    be.call("gd_nbr_fss", be.ptr(f), be.ptr(o), dt, T, H, W, be.ptr(mask), tf.ctypes.data, to.ctypes.data, K, int(bool(below)),
+            sc.ctypes.data, S, mode, p_sums, p_base, be.ptr(out), *_nbr_ws(be, ws, f, T, H, W, K, planes, "nbr_fss"))
     return sums, base, out
 
 
-def nbr_fraction_host(x, thr, scale: int, below: bool = True, normalize: str = "window", mask=None):
-    """``nbr_fraction`` on a HOST array"""
-    import numpy as np
-    x, dt = _nbr_host_cube(x, "nbr_fraction_host")
+nbr_fss = functools.partial(_nbr_fss, _DEV)
+nbr_fss_host = functools.partial(_nbr_fss, _HOST)   # plain C++ over the same per-pixel code, in the device's order of sums
+
+
+def _nbr_fraction(be, x, thr, scale: int, below: bool = True, normalize: str = "window", mask=None, out=None, ws=None,
+                  planes: Optional[int] = None):
+    """the (T, H, W) fp64 neighbourhood fraction of a dense fp32 / fp64 cube at the odd width ``scale``; ``thr``: one
+    threshold or one per step, on the HOST"""
+    x, dt = be.array(x, "nbr_fraction input", 3)
     T, H, W = x.shape
-    th = _nbr_step_thresholds(thr, T, "nbr_fraction_host threshold")
+    th = _nbr_step_thresholds(thr, T, "nbr_fraction threshold")
     sc = _nbr_scales(scale)
-    mask = _host_vec(mask, H * W, "nbr_fraction_host mask", "uint8")
-    out = np.empty((T, H, W))
-    L.check(lib().gd_nbr_fraction_host(x.ctypes.data, dt, T, H, W, _np_ptr(mask), th.ctypes.data, int(bool(below)), int(sc[0]),
-                                       _nbr_normalize(normalize), out.ctypes.data), "gd_nbr_fraction_host")
+    if not be.host and sc.size != 1:                                             # the host twin reads the first of several
+        raise L.GandanetError(f"nbr_fraction: one scale, got {scale!r}")
+    mask = be.vec(mask, H * W, "nbr_fraction mask", be.u8)
+    out = be.out(out, (T, H, W), be.f64, x, "neighbourhood fraction")
+    be.call("gd_nbr_fraction", be.ptr(x), dt, T, H, W, be.ptr(mask), th.ctypes.data, int(bool(below)), int(sc[0]), _nbr_normalize(normalize),
+            be.ptr(out), *_nbr_ws(be, ws, x, T, H, W, 1, planes, "nbr_fraction"))
     return out
+
+
+nbr_fraction = functools.partial(_nbr_fraction, _DEV)
+nbr_fraction_host = functools.partial(_nbr_fraction, _HOST)
 
 
 # ---- bias correction (include/gandanet.h, "Bias correction"; quantmap.hip) -----------------------------------------------------
 def qm_probs(q, fn: str, qmin: int = 1):
     """the probabilities ``q`` (a number or a sequence, on the host) as a float64 numpy vector of ``qmin`` .. QM_MAX_Q entries
     in [0, 1]"""
-    import numpy as np
     try:
         qa = np.atleast_1d(np.asarray(q, dtype=np.float64))
     except (TypeError, ValueError):
@@ -3016,7 +2742,6 @@ def qm_probs(q, fn: str, qmin: int = 1):
 
 def qm_nodes(n_quantiles: int):
     """the node probabilities j / (Q - 1) of a quantile map of Q = ``n_quantiles`` nodes, a float64 numpy vector"""
-    import numpy as np
     if isinstance(n_quantiles, bool) or not isinstance(n_quantiles, (int, np.integer)) or not 2 <= n_quantiles <= L.QM_MAX_Q:
         raise L.GandanetError(f"quantile map: 2 <= n_quantiles <= {L.QM_MAX_Q}, got {n_quantiles!r}")
     return np.arange(int(n_quantiles), dtype=np.float64) / float(int(n_quantiles) - 1)
@@ -3044,38 +2769,47 @@ def _qm_route(route) -> int:
     return L.QM_ROUTES[route]
 
 
-def qm_quantiles(x: Tensor, q, period: int = 1, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask: Optional[Tensor] = None,
-                 x2: Optional[Tensor] = None, min_samples: int = 1, layout: int = L.QM_LAYOUT_QSM, _route: str = "auto"):
+def _qm_quantiles(be, x, q, period: int = 1, phase: int = 0, b0: int = 0, b1: Optional[int] = None, mask=None, x2=None,
+                  min_samples: int = 1, layout: int = L.QM_LAYOUT_QSM, _route: str = "auto"):
     """(nodes, n) of the M series of a dense fp32 / fp64 ``x`` (T, M): the quantiles at the probabilities ``q`` (a host
-    sequence, checked here, or an fp64 device vector the caller vouches for) of every calendar slot's baseline sample, fp64,
-    (Q, period, M) (QM_LAYOUT_QSM) or (period, Q, M) (QM_LAYOUT_SQM), and the sample sizes (period, M) int32.  ``x2``: a second
-    cube of the shape and dtype of ``x`` whose NaNs leave a step out as well.  ``_route`` ("auto", "small", "long") forces
-    one of the two sort kernels (for the tests: both give the same bits).  New tensors.  No host sync beyond the upload of
-    a host ``q``."""
-    dt = _series_2d(x, "qm_quantiles input")
+    sequence, checked here on the device side and by the C entry on the host side, or an fp64 device vector the caller vouches
+    for) of every calendar slot's baseline sample, fp64, (Q, period, M) (QM_LAYOUT_QSM) or (period, Q, M) (QM_LAYOUT_SQM), and
+    the sample sizes (period, M) int32.  ``x2``: a second cube of the shape and dtype of ``x`` whose NaNs leave a step out as
+    well.  ``_route`` ("auto", "small", "long") forces one of the two sort kernels (for the tests: both give the same bits).
+    New tensors.  No host sync beyond the upload of a host ``q``."""
+    x, dt = be.array(x, "qm_quantiles input", 2)
     T, M = x.shape
-    b1 = T if b1 is None else b1
-    period, phase, b0, b1, min_samples = int(period), int(phase), int(b0), int(b1), int(min_samples)
-    _qm_calendar("qm_quantiles", T, period, phase, b0, b1, min_samples)
-    if x2 is not None and (_series_2d(x2, "qm_quantiles second cube") != dt or x2.shape != x.shape):
-        raise L.GandanetError(f"qm_quantiles: the second cube is {tuple(x.shape)} {x.dtype} like the first, got {tuple(x2.shape)} {x2.dtype}")
-    if isinstance(q, Tensor):
-        qd = _dense(q, "qm_quantiles q", torch.float64).reshape(-1)
-        if not 1 <= qd.numel() <= L.QM_MAX_Q:
-            raise L.GandanetError(f"qm_quantiles: q holds 1 .. {L.QM_MAX_Q} probabilities, got {qd.numel()}")
-    else:
-        qd = torch.from_numpy(qm_probs(q, "qm_quantiles")).to(x.device)
-    Q = qd.numel()
-    if layout not in (L.QM_LAYOUT_QSM, L.QM_LAYOUT_SQM):
-        raise L.GandanetError(f"qm_quantiles: unknown layout {layout!r}")
+    period, phase, b0, b1, min_samples = int(period), int(phase), int(b0), int(T if b1 is None else b1), int(min_samples)
+    if x2 is not None:
+        x2, dt2 = be.array(x2, "qm_quantiles second cube", 2)
+        if dt2 != dt or x2.shape != x.shape:
+            raise L.GandanetError(f"qm_quantiles: the second cube is {tuple(x.shape)} {x.dtype} like the first, got {tuple(x2.shape)} {x2.dtype}")
     route = _qm_route(_route)
-    if route == L.QM_ROUTES["small"] and -(-(b1 - b0) // period) > L.QM_SMALL_N:
-        raise L.GandanetError(f"qm_quantiles: the register route takes at most {L.QM_SMALL_N} baseline steps per slot")
-    quant = torch.empty((Q, period, M) if layout == L.QM_LAYOUT_QSM else (period, Q, M), device=x.device, dtype=torch.float64)
-    n = torch.empty((period, M), device=x.device, dtype=torch.int32)
-    L.check(lib().gd_qm_quantiles(_ptr(x), _ptr(x2), dt, T, M, _ptr(qd), Q, period, phase, b0, b1, _ptr(_eval_mask(mask, M)), min_samples,
-                                  layout, route, _ptr(quant), _ptr(n), _stream()), "gd_qm_quantiles")
+    if be.host:                                 # the host twin leaves q, the calendar, the layout and the route's limit to the C entry
+        qd = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+    else:
+        _qm_calendar("qm_quantiles", T, period, phase, b0, b1, min_samples)
+        if isinstance(q, Tensor):
+            qd = _dense(q, "qm_quantiles q", torch.float64).reshape(-1)
+            if not 1 <= qd.numel() <= L.QM_MAX_Q:
+                raise L.GandanetError(f"qm_quantiles: q holds 1 .. {L.QM_MAX_Q} probabilities, got {qd.numel()}")
+        else:
+            qd = torch.from_numpy(qm_probs(q, "qm_quantiles")).to(x.device)
+        if layout not in (L.QM_LAYOUT_QSM, L.QM_LAYOUT_SQM):
+            raise L.GandanetError(f"qm_quantiles: unknown layout {layout!r}")
+        if route == L.QM_ROUTES["small"] and -(-(b1 - b0) // period) > L.QM_SMALL_N:
+            raise L.GandanetError(f"qm_quantiles: the register route takes at most {L.QM_SMALL_N} baseline steps per slot")
+    Q, slots = math.prod(qd.shape), max(period, 0)
+    mask = be.vec(mask, M, "qm_quantiles mask", be.u8)
+    quant = be.empty((Q, slots, M) if layout == L.QM_LAYOUT_QSM else (slots, Q, M), be.f64, x)
+    n = be.empty((slots, M), be.i32, x)
+    be.call("gd_qm_quantiles", be.ptr(x), be.ptr(x2), dt, T, M, be.ptr(qd), Q, period, phase, b0, b1, be.ptr(mask), min_samples, int(layout),
+            route, be.ptr(quant), be.ptr(n))
     return quant, n
+
+
+qm_quantiles = functools.partial(_qm_quantiles, _DEV)
+qm_quantiles_host = functools.partial(_qm_quantiles, _HOST)
 
 
 def _qm_tables(model_q, obs_q, fn: str, dev: bool):
@@ -3116,72 +2850,29 @@ def _qm_codes(kind, extrapolate, phase, period, fn: str):
     return L.QM_KINDS[kind], L.QM_EXTRAPOLATE[extrapolate]
 
 
-def qm_apply(x: Tensor, model_q: Tensor, obs_q: Tensor, kind: str = "eqm", extrapolate: str = "constant", phase: int = 0,
-             own_q: Optional[Tensor] = None, p: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+def _qm_apply(be, x, model_q, obs_q, kind: str = "eqm", extrapolate: str = "constant", phase: int = 0, own_q=None, p=None, out=None):
     """the dense fp32 / fp64 cube ``x`` (T, f H, f W) mapped through the (period, Q, H, W) fp64 tables, in the dtype of ``x``;
     step t uses slot (t + ``phase``) mod period.  ``"qdm"`` takes ``own_q`` (period, Q, f H, f W), the node table of ``x``
-    itself, and ``p``, the Q node probabilities on the device."""
-    dt = _filter_dtype(x, "qm_apply input")
-    period, Q, H, W = _qm_tables(model_q, obs_q, "qm_apply", True)
+    itself, and ``p``, the Q node probabilities."""
+    x, dt = be.array(x, "qm_apply input")
+    model_q, obs_q = (be.dense(t, f"qm_apply {nm}", be.f64) for t, nm in ((model_q, "model_q"), (obs_q, "obs_q")))
+    period, Q, H, W = _qm_tables(model_q, obs_q, "qm_apply", False)
     f = _qm_factor(x.shape, H, W, "qm_apply")
     k, e = _qm_codes(kind, extrapolate, int(phase), period, "qm_apply")
     if k == L.QM_KINDS["qdm"]:
         if own_q is None or p is None:
             raise L.GandanetError("qm_apply: 'qdm' needs own_q, the node table of x itself, and p, the node probabilities")
-        _dense(own_q, "qm_apply own_q", torch.float64)
+        own_q = be.dense(own_q, "qm_apply own_q", be.f64)
         if tuple(own_q.shape) != (period, Q) + tuple(x.shape[1:]):
             raise L.GandanetError(f"qm_apply: own_q is {(period, Q) + tuple(x.shape[1:])}, got {tuple(own_q.shape)}")
-        _vec(p, Q, "qm_apply p")
+        p = be.vec(p, Q, "qm_apply p")
     else:
         own_q = p = None
-    out = _out(out, x.shape, x, x.dtype, "qm_apply output")
-    L.check(lib().gd_qm_apply(_ptr(x), dt, x.shape[0], H, W, f, _ptr(model_q), _ptr(obs_q), _ptr(own_q), _ptr(p), Q, period, int(phase), k, e,
-                              _ptr(out), _stream()), "gd_qm_apply")
+    out = be.out(out, x.shape, x.dtype, x, "qm_apply output")
+    be.call("gd_qm_apply", be.ptr(x), dt, x.shape[0], H, W, f, be.ptr(model_q), be.ptr(obs_q), be.ptr(own_q), be.ptr(p), Q, period,
+            int(phase), k, e, be.ptr(out))
     return out
 
 
-def qm_quantiles_host(x, q, period: int = 1, phase: int = 0, b0: int = 0, b1=None, mask=None, x2=None, min_samples: int = 1,
-                      layout: int = L.QM_LAYOUT_QSM, _route: str = "auto"):
-    """``qm_quantiles`` on HOST arrays (plain C++ loops over the same per-sample code, no GPU): (nodes, n)"""
-    import numpy as np
-    x, dt = _host_f(x, "qm_quantiles_host")
-    if x.ndim != 2:
-        raise L.GandanetError(f"qm_quantiles_host: expected a (T, M) array, got {x.shape}")
-    T, M = x.shape
-    b1 = T if b1 is None else b1
-    if x2 is not None:
-        x2, dt2 = _host_f(x2, "qm_quantiles_host second cube")
-        if dt2 != dt or x2.shape != x.shape:
-            raise L.GandanetError(f"qm_quantiles_host: the second cube is {x.shape} {x.dtype} like the first, got {x2.shape} {x2.dtype}")
-    qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
-    Q, period = int(qa.size), int(period)
-    mask = _host_vec(mask, M, "qm_quantiles_host mask", "uint8")
-    quant = np.empty((Q, max(period, 0), M) if layout == L.QM_LAYOUT_QSM else (max(period, 0), Q, M))
-    n = np.empty((max(period, 0), M), dtype=np.int32)
-    L.check(lib().gd_qm_quantiles_host(x.ctypes.data, _np_ptr(x2), dt, T, M, qa.ctypes.data, Q, period, int(phase), int(b0), int(b1),
-                                       _np_ptr(mask), int(min_samples), int(layout), _qm_route(_route), quant.ctypes.data, n.ctypes.data),
-            "gd_qm_quantiles_host")
-    return quant, n
-
-
-def qm_apply_host(x, model_q, obs_q, kind: str = "eqm", extrapolate: str = "constant", phase: int = 0, own_q=None, p=None):
-    """``qm_apply`` on HOST arrays"""
-    import numpy as np
-    x, dt = _host_f(x, "qm_apply_host")
-    model_q, obs_q = (np.ascontiguousarray(t, dtype=np.float64) for t in (model_q, obs_q))
-    period, Q, H, W = _qm_tables(model_q, obs_q, "qm_apply_host", False)
-    f = _qm_factor(x.shape, H, W, "qm_apply_host")
-    k, e = _qm_codes(kind, extrapolate, int(phase), period, "qm_apply_host")
-    if k == L.QM_KINDS["qdm"]:
-        if own_q is None or p is None:
-            raise L.GandanetError("qm_apply_host: 'qdm' needs own_q and p")
-        own_q = np.ascontiguousarray(own_q, dtype=np.float64)
-        if own_q.shape != (period, Q) + x.shape[1:]:
-            raise L.GandanetError(f"qm_apply_host: own_q is {(period, Q) + x.shape[1:]}, got {own_q.shape}")
-        p = _host_vec(p, Q, "qm_apply_host p")
-    else:
-        own_q = p = None
-    out = np.empty_like(x)
-    L.check(lib().gd_qm_apply_host(x.ctypes.data, dt, x.shape[0], H, W, f, model_q.ctypes.data, obs_q.ctypes.data, _np_ptr(own_q), _np_ptr(p),
-                                   Q, period, int(phase), k, e, out.ctypes.data), "gd_qm_apply_host")
-    return out
+qm_apply = functools.partial(_qm_apply, _DEV)
+qm_apply_host = functools.partial(_qm_apply, _HOST)

@@ -279,3 +279,47 @@ def test_launcher_edges(M):
                 "gd_block_mean")
         hm, hc = K.block_mean_host(x, 2, 2)
         assert np.array_equal(_middle(buf, M), hm.reshape(-1), equal_nan=True) and np.array_equal(_middle(cbuf, M), hc.reshape(-1)), M
+
+
+def _arg_cases(K):
+    """one device wrapper per analysis family that has a host twin: name -> (call(x), the shape of its main array); the other
+    arguments are good ones on the device, so only the main array can be at fault"""
+    f64 = dict(device="cuda", dtype=torch.float64)
+    stl = dict(period=2, seasonal=3, trend=3, low_pass=3, seasonal_deg=1, trend_deg=1, low_pass_deg=1, inner_iter=2, outer_iter=1)
+    mean, valid = torch.zeros(7, **f64), torch.ones(7, device="cuda", dtype=torch.uint8)
+    clim = torch.ones(3, 2, 7, **f64)
+    table = torch.linspace(-2.0, 2.0, 60, **f64).reshape(1, 3, 4, 5)
+    return {
+        "stl_decompose": (lambda x: K.stl_decompose(x, stl), (5, 7)),
+        "series_stats": (lambda x: K.series_stats(x, x, torch.zeros(8, 7, **f64)), (5, 7)),
+        "trend_test": (lambda x: K.trend_test(x, torch.arange(5, **f64)), (5, 7)),
+        "ens_verify": (lambda x: K.ens_verify(x, torch.zeros(7, device="cuda", dtype=x.dtype), torch.zeros(K.L.ENSV_REC, **f64)), (5, 7)),
+        "eof_gram": (lambda x: K.eof_gram(x, mean, valid), (5, 7)),
+        "spec_prepare": (lambda x: K.spec_prepare(x), (3, 4, 5)),
+        "drought_index": (lambda x: K.drought_index(x, clim), (5, 7)),
+        "ccl_label": (lambda x: K.ccl_label(x, 0.0, 0x1FFF), (3, 4, 5)),
+        "nbr_fraction": (lambda x: K.nbr_fraction(x, 0.0, 3), (3, 4, 5)),
+        "qm_quantiles": (lambda x: K.qm_quantiles(x, [0.25, 0.5]), (5, 7)),
+        "qm_apply": (lambda x: K.qm_apply(x, table, table), (3, 4, 5)),
+    }
+
+
+@pytest.mark.parametrize("name", ["stl_decompose", "series_stats", "trend_test", "ens_verify", "eof_gram", "spec_prepare", "drought_index",
+                                  "ccl_label", "nbr_fraction", "qm_quantiles", "qm_apply"])
+def test_device_wrappers_refuse_a_bad_main_array_before_any_launch(name):
+    """a CPU tensor, a non-contiguous view, a wrong dtype and a wrong ndim each raise GandanetError in the wrapper, which
+    returns before it reaches the C entry; the good array goes through"""
+    from gan_danet_amd import kern as K
+    call, shape = _arg_cases(K)[name]
+    x = torch.linspace(-1.0, 1.0, int(np.prod(shape)), device="cuda", dtype=torch.float64).reshape(shape)
+    call(x)
+    torch.cuda.synchronize()
+    view = x.transpose(0, 1).contiguous().transpose(0, 1)
+    assert view.shape == x.shape and not view.is_contiguous() and not view[0].is_contiguous()
+    bad = {"CPU tensor": x.cpu(), "non-contiguous view": view, "wrong dtype": x.to(torch.int32), "one dimension too few": x[0]}
+    if name != "ens_verify":                                                      # (M, ...) members: any ndim from 2 on
+        bad["one dimension too many"] = x[None]
+    for what, arr in bad.items():
+        with pytest.raises(K.L.GandanetError):
+            call(arr)
+            pytest.fail(f"{name} took a {what}")
