@@ -40,6 +40,9 @@ from . import neighborhood
 from .neighborhood import FSSResult, drought_fss, fractions_skill_score, fss_cross_grid, neighborhood_fraction
 from . import biascorrect
 from .biascorrect import QuantileMap, series_quantiles
+from . import lagcorr
+from .lagcorr import (LagCorrelation, autocorrelation, correlation_significance, driver_lags, fdr_threshold,
+                      lag_correlation)
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

@@ -29,6 +29,10 @@ LSTSQ_MAX_P = 8                  # GD_LSTSQ_MAX_P
 TREND_MAX_T = 2048               # GD_TREND_MAX_T
 TREND_MAPS = ("n", "s", "var_s", "z", "p", "tau", "slope", "intercept", "slope_lo", "slope_hi")   # GD_TREND_*: plane k of `out`
 TREND_SEN, TREND_CI, TREND_CONTINUITY = 1, 2, 4   # GD_TREND_SEN, GD_TREND_CI, GD_TREND_CONTINUITY
+LAG_MAX, LAG_MAX_T, LAG_CHUNK = 64, 2048, 32   # GD_LAG_MAX, GD_LAG_MAX_T, GD_LAG_CHUNK
+LAG_PLANES = ("best_lag", "best_r", "best_n", "r0")   # GD_LAG_*: plane k of `best`
+LAG_SELECT = {"abs": 0, "max": 1, "min": 2}           # GD_LAG_SELECT_*
+ACF_KINDS = {"pearson": 0, "standard": 1}             # GD_ACF_*
 ENSV_MAX_M, ENSV_F64, ENSV_FAIR = 32, 1, 2   # GD_ENSV_MAX_M, GD_ENSV_F64, GD_ENSV_FAIR
 ENSV_FIELDS = ("n", "tied", "crps", "crps_gauss", "abs_e", "e2", "s2")   # GD_ENSV_*: record slot k; then cover, hist
 ENSV_COVER, ENSV_HIST, ENSV_BINS, ENSV_REC = 7, 11, 33, 44   # GD_ENSV_COVER, GD_ENSV_HIST, GD_ENSV_BINS, GD_ENSV_REC
@@ -245,6 +249,11 @@ SIGNATURES = {
     "gd_block_mean_host": (_i, [_p, _i, _l, _l, _l, _i, _i, _p, _i, _p, _p]),
     "gd_trend_test": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p, _p]),
     "gd_trend_test_host": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p]),
+    "gd_lag_corr": (_i, [_p, _p, _i, _l, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "gd_lag_corr_host": (_i, [_p, _p, _i, _l, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "gd_series_acf": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p, _p]),
+    "gd_series_acf_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p]),
+    "gd_corr_signif": (_i, [_p, _p, _p, _l, _p, _l, _p, _p, _p, _p]),
     "gd_ens_verify_ws_bytes": (_sz, [_l]),
     "gd_ens_verify": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gd_ens_verify_host": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p]),

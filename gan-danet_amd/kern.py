@@ -2876,3 +2876,77 @@ def _qm_apply(be, x, model_q, obs_q, kind: str = "eqm", extrapolate: str = "cons
 
 qm_apply = functools.partial(_qm_apply, _DEV)
 qm_apply_host = functools.partial(_qm_apply, _HOST)
+
+
+# ---- lagged correlation (include/gandanet.h, "Lagged correlation"; lagcorr.hip) -------------------------------------------------
+def _lag_range(lag_lo, lag_hi, fn: str):
+    ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (lag_lo, lag_hi))
+    if not ok or not -L.LAG_MAX <= lag_lo <= lag_hi <= L.LAG_MAX:
+        raise L.GandanetError(f"{fn}: the lags are integers with -{L.LAG_MAX} <= lo <= hi <= {L.LAG_MAX}, got ({lag_lo!r}, {lag_hi!r})")
+    return int(lag_lo), int(lag_hi)
+
+
+def _lag_corr(be, a, b, lag_lo: int, lag_hi: int, min_pairs: int = 3, select: str = "abs", mask=None, curve: bool = True, best: bool = True):
+    """r of ``a[t]`` against ``b[t + l]`` for l = ``lag_lo`` .. ``lag_hi`` (l > 0: b follows a) and every series of the dense
+    fp32 / fp64 ``b`` (T, M); ``a`` is (T, M), or one series (T,) / (T, 1) shared by all M, of the dtype of ``b``.  ``mask``: M
+    uint8, 0 = leave the series out.  New arrays (r (NL, M) fp64, n (NL, M) int32, best (4, M) fp64 in the order of
+    L.LAG_PLANES); r and n are None without ``curve``, best is None without ``best``.  No host sync."""
+    b, dt = be.array(b, "lag_corr b", 2)
+    a, dta = be.array(a, "lag_corr a")
+    T, M = b.shape
+    if dta != dt or a.shape[0] != T or tuple(a.shape[1:]) not in ((), (1,), (M,)):
+        raise L.GandanetError(f"lag_corr: a is ({T},), ({T}, 1) or ({T}, {M}) of the dtype of b, got {tuple(a.shape)} {a.dtype} against "
+                              f"{tuple(b.shape)} {b.dtype}")
+    a_M = M if a.ndim == 2 and a.shape[1] == M else 1
+    lo, hi = _lag_range(lag_lo, lag_hi, "lag_corr")
+    if select not in L.LAG_SELECT:
+        raise L.GandanetError(f"lag_corr: select is one of {tuple(L.LAG_SELECT)}, got {select!r}")
+    if not (curve or best):
+        raise L.GandanetError("lag_corr: neither the curve nor the best lag is asked for")
+    mask = be.vec(mask, M, "lag_corr mask", be.u8)
+    nl = hi - lo + 1
+    r = be.empty((nl, M), be.f64, b) if curve else None
+    n = be.empty((nl, M), be.i32, b) if curve else None
+    planes = be.empty((len(L.LAG_PLANES), M), be.f64, b) if best else None
+    be.call("gd_lag_corr", be.ptr(a), be.ptr(b), dt, T, M, a_M, lo, hi, int(min_pairs), L.LAG_SELECT[select], be.ptr(mask), be.ptr(r),
+            be.ptr(n), be.ptr(planes))
+    return r, n, planes
+
+
+lag_corr = functools.partial(_lag_corr, _DEV)
+lag_corr_host = functools.partial(_lag_corr, _HOST)   # plain C++ over the same per-pair arithmetic, one series and lag at a time
+
+
+def _series_acf(be, x, K: int, kind: str = "standard", mask=None, min_pairs: int = 3):
+    """the autocorrelation at the lags 0 .. ``K`` of every series of the dense fp32 / fp64 ``x`` (T, M): new arrays (acf
+    (K + 1, M) fp64, n (K + 1, M) int32, the valid pairs of each lag); ``kind`` "standard" (Box-Jenkins, c_k / c_0) or
+    "pearson" (r of the overlapping parts)"""
+    x, dt = be.array(x, "series_acf input", 2)
+    T, M = x.shape
+    _, K = _lag_range(0, K, "series_acf")
+    if kind not in L.ACF_KINDS:
+        raise L.GandanetError(f"series_acf: kind is one of {tuple(L.ACF_KINDS)}, got {kind!r}")
+    mask = be.vec(mask, M, "series_acf mask", be.u8)
+    acf, n = be.empty((K + 1, M), be.f64, x), be.empty((K + 1, M), be.i32, x)
+    be.call("gd_series_acf", be.ptr(x), dt, T, M, K, L.ACF_KINDS[kind], int(min_pairs), be.ptr(mask), be.ptr(acf), be.ptr(n))
+    return acf, n
+
+
+series_acf = functools.partial(_series_acf, _DEV)
+series_acf_host = functools.partial(_series_acf, _HOST)
+
+
+def corr_signif(r: Tensor, n: Tensor, r1a: Tensor, r1b: Tensor):
+    """(n_eff, z, p) of the correlations ``r`` of ``n`` pairs between series whose lag-1 autocorrelations are ``r1a`` (one value,
+    or one per entry) and ``r1b``: dense fp64 GPU tensors of one size, new tensors of the shape of ``r``.  Device only."""
+    _dense(r, "corr_signif r", torch.float64)
+    M = r.numel()
+    if M == 0:
+        raise L.GandanetError("corr_signif: empty map")
+    n, r1b = _Dev.vec(n, M, "corr_signif n"), _Dev.vec(r1b, M, "corr_signif r1b")
+    _dense(r1a, "corr_signif r1a", torch.float64)
+    if r1a.numel() not in (1, M):
+        raise L.GandanetError(f"corr_signif: r1a holds 1 or {M} values, got {tuple(r1a.shape)}")
+    n_eff, z, p = (torch.empty_like(r) for _ in range(3))
+    _Dev.call("gd_corr_signif", _ptr(r), _ptr(n), _ptr(r1a), r1a.numel(), _ptr(r1b), M, _ptr(n_eff), _ptr(z), _ptr(p))
+    return n_eff, z, p

@@ -1010,6 +1010,63 @@ int gd_trend_test_host(const void* x, int dtype, long T, long M, const double* t
                        int flags, double zq, double* out);
 
 /* ------------------------------------------------------------------------------------------
+ * Lagged correlation (lagcorr.hip, csrc/lagcorr_core.h): how many months does storage run behind precipitation, an index or
+ * any other driver, pixel by pixel, and how strong is the link at that lag; the autocorrelation of every series; and what a
+ * correlation of two autocorrelated series is worth (effective sample size, Fisher z, p).
+ * The layout is that of "Per-pixel time series": series m of a dense (T, M) array at x[t * M + m], storage fp32 (dtype 0) or
+ * fp64 (dtype 1), all arithmetic fp64 with every operation rounded on its own.  1 <= T <= GD_LAG_MAX_T.
+ *   Lag sign   r(l) correlates a[t] with b[t + l]: l > 0 means b follows a.  The lags are the closed range lag_lo .. lag_hi,
+ *              -GD_LAG_MAX <= lag_lo <= lag_hi <= GD_LAG_MAX; lag lag_lo + k is row k of the curve.
+ *   Pairs      only pairs with both members not NaN count (pairwise deletion, per lag).
+ *   Centring   ma, mb: the mean of each series over its own samples that are not NaN, by the recurrence of gd_series_stats
+ *              (m += (x - m) * (1 / n'), in time order).  With u = a - ma, v = b - mb the six sums n, Su, Sv, Suu, Svv, Suv
+ *              run over the valid pairs of a (series, lag) in ascending t.
+ *   r          va = Suu - Su Su / n, vb = Svv - Sv Sv / n, c = Suv - Su Sv / n, r = c / sqrt(va vb) clipped to [-1, 1];
+ *              NaN when n < min_pairs (min_pairs >= 2), va <= 0 or vb <= 0.
+ *   Broadcast  a_M == 1: a is one series of T values shared by all M series of b (an index against every pixel); else a_M == M.
+ *   Best lag   over the lags whose r is not NaN: the largest |r| (GD_LAG_SELECT_ABS), the largest r (_MAX) or the smallest
+ *              (_MIN); a tie goes to the smaller |l|, then to the positive lag.  best is (GD_LAG_PLANES, M) doubles, planar:
+ *              best_lag (NaN when no lag is valid), best_r, best_n (the pairs at that lag, 0 when none is valid) and r0, the
+ *              r of lag 0 (NaN when 0 is outside the range).  The choice is not corrected for the selection over lags.
+ * r: (NL, M) doubles and n: (NL, M) int32, NL = lag_hi - lag_lo + 1, the curve and its pair counts.  r, n and best may each
+ * be NULL, not all three; a curve that is not asked for is never written.  mask: NULL, or M bytes; a series whose byte is 0
+ * is not read: NaN in r and best, 0 in n and best_n.
+ * A workgroup owns 64 neighbouring series and walks time in chunks of GD_LAG_CHUNK steps whose centred values (with a halo
+ * of the lag range for b, kept as a ring) sit in LDS; a lane holds the six sums of one series at up to 9 lags in registers
+ * from the first sample to the last, the waves of the workgroup cover the lags.  The main loop reads every cube once; the
+ * means come from a first pass over the same 64 columns.  No atomics, no workspace, nothing allocated: a series' result
+ * depends on the series and the parameters alone, not on M, its column, the chunk length or the launch.  The host twins run
+ * the same per-pair code and agree bit for bit on r, n, best and acf.
+ * Errors (-1, gd_last_error): a NULL input, every output NULL, dtype, T, M, a_M not in {1, M}, a bad lag range, min_pairs < 2,
+ * select or kind unknown, a pointer that is not element aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_LAG_MAX 64
+#define GD_LAG_MAX_T 2048
+#define GD_LAG_CHUNK 32 /* time steps per staged chunk (no result depends on it) */
+enum { GD_LAG_BEST_LAG = 0, GD_LAG_BEST_R = 1, GD_LAG_BEST_N = 2, GD_LAG_R0 = 3, GD_LAG_PLANES = 4 };
+enum { GD_LAG_SELECT_ABS = 0, GD_LAG_SELECT_MAX = 1, GD_LAG_SELECT_MIN = 2 };
+enum { GD_ACF_PEARSON = 0, GD_ACF_STANDARD = 1 };
+int gd_lag_corr(const void* a, const void* b, int dtype, long T, long M, long a_M, int lag_lo, int lag_hi, int min_pairs,
+                int select, const unsigned char* mask, double* r, int* n, double* best, void* stream);
+int gd_lag_corr_host(const void* a, const void* b, int dtype, long T, long M, long a_M, int lag_lo, int lag_hi, int min_pairs,
+                     int select, const unsigned char* mask, double* r, int* n, double* best);
+/* The autocorrelation of every series at the lags 0 .. K (0 <= K <= GD_LAG_MAX): acf (K + 1, M) doubles, n (K + 1, M) int32
+ * (the valid pairs of each lag; may be NULL).  kind GD_ACF_PEARSON: r as above with a = b.  GD_ACF_STANDARD (Box-Jenkins):
+ * acf_k = c_k / c_0, c_k = (1 / n0) sum (x_t - m)(x_(t+k) - m) over the valid pairs in ascending t, c_0 = (1 / n0) sum
+ * (x_t - m)^2 over the n0 samples that are not NaN, m their mean; NaN at c_0 <= 0 or fewer than min_pairs pairs; acf_0 = 1. */
+int gd_series_acf(const void* x, int dtype, long T, long M, int K, int kind, int min_pairs, const unsigned char* mask, double* acf,
+                  int* n, void* stream);
+int gd_series_acf_host(const void* x, int dtype, long T, long M, int K, int kind, int min_pairs, const unsigned char* mask,
+                       double* acf, int* n);
+/* What a correlation r of n pairs is worth when the two series have the lag-1 autocorrelations r1a, r1b (Bretherton et al.
+ * 1999; Fisher z), M values each, r1a one value when r1a_len == 1:
+ *   n_eff = n (1 - r1a r1b) / (1 + r1a r1b) clamped to [0, n];  z = atanh(r) sqrt(n_eff - 3);  p = erfc(|z| * 0.7071067811865476).
+ * z and p are NaN when n_eff <= 3 or an input is NaN (an input that is NaN makes n_eff NaN too); |r| = 1 gives p = 0.  n_eff, z, p may each be
+ * NULL, not all three.  Device only: atanh and erfc are the device library's. */
+int gd_corr_signif(const double* r, const double* n, const double* r1a, long r1a_len, const double* r1b, long M, double* n_eff,
+                   double* z, double* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Ensemble verification (ensverify.hip, csrc/ensverify_core.h): is the spread of an ensemble the right size?  The
  * continuous ranked probability score, the rank (Talagrand) histogram, the spread against the error of the ensemble mean
  * and the coverage of the +-k sigma intervals, of the members in the slab of evaluate_ensemble against the truth of the
