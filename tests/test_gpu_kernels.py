@@ -80,7 +80,7 @@ def test_wide_conv3x3_through_the_pixel_major_kernel(gd, shape):
     """wide 3x3 / stride 1 / pad 1 convs in 16-bit mode (ops._wide3x3: DANetAttention's fuse conv, generator.py:108) run on
     a pixel-major bf16 copy of x through the NHWC kernel with an fp32 NCHW result; forward, both gradients and the input
     given as a channel slice of a wider buffer, against ATen on the bf16-rounded operands and against the fp32-NCHW
-    patch kernel (ops.CONV_WIDE_NHWC off), which rounds the same operands"""
+    patch kernel (ops.CONV_WIDE_NHWC off), which rounds the same operands.  Exact (zero-tolerance) counterpart: tests/test_gpu_conv_exact.py."""
     ops, _ = _ops()
     B, Cin, H, W, Cout, bias, relu = shape
     assert ops._wide3x3(torch.empty(B, Cin, H, W), torch.empty(Cout, Cin, 3, 3), 1, 1, ops.ACT_NONE, ops.L.PREC_BF16)
@@ -407,7 +407,7 @@ def test_pack16_tile64_kernel_aligned_shapes(gd, R, Cc, Rp, ldp, ldt, f16):
 def test_conv3x3_patch_kernel_matches_generic_and_oracle(gd, shape):
     """the LDS-patch 3x3 kernel against the generic implicit-GEMM kernel (same bf16 operands -> agreement to
     fp32 accumulation order) and against the oracle; forward with fused BN-affine+ReLU prologue, bias, ReLU,
-    and the data gradient."""
+    and the data gradient.  Exact (zero-tolerance) counterpart: tests/test_gpu_conv_exact.py."""
     ops, K = _ops()
     from gan_danet_amd import _lib as L
     B, Cin, H, W, Cout = shape
@@ -441,7 +441,7 @@ def test_conv3x3_patch_kernel_matches_generic_and_oracle(gd, shape):
 @pytest.mark.parametrize("shape", [(2, 1, 64, 96, 64), (2, 64, 32, 64, 128), (1, 128, 17, 35, 256), (1, 40, 9, 130, 24)])
 def test_conv3x3_stride2_patch_kernel(gd, shape):
     """the discriminator's stride-2 3x3 convs (discriminator.py:11-26): LDS-patch forward and weight gradient
-    against the generic kernels (same bf16 operands) and the oracle; odd sizes exercise the ragged tiles."""
+    against the generic kernels (same bf16 operands) and the oracle; odd sizes exercise the ragged tiles.  Exact (zero-tolerance) counterpart: tests/test_gpu_conv_exact.py."""
     ops, K = _ops()
     from gan_danet_amd import _lib as L
     B, Cin, H, W, Cout = shape
@@ -474,7 +474,7 @@ def test_conv1x1_transpose_read_kernel(gd, shape):
     BN-affine+ReLU prologue, forward / data gradient / weight gradient, against the oracle (bf16 operands).
     (1, 32, 5, 7, 24) (35 pixels) is not 16-byte friendly and must fall back to the generic kernel.  The last shape has
     B H W = 2^18 pixels (2048 pixel tiles), a ragged 128-row M tile (72) and Ck = 40 below one k-tile.  Forward and data
-    gradient also run with split-bf16 operands (GD_PREC_X3), both modes against the fp64 convolution of the same operands."""
+    gradient also run with split-bf16 operands (GD_PREC_X3), both modes against the fp64 convolution of the same operands.  Exact (zero-tolerance) counterpart: tests/test_gpu_conv_exact.py."""
     ops, K = _ops()
     from gan_danet_amd import _lib as L
     B, Cin, H, W, Cout = shape

@@ -842,15 +842,19 @@ def test_pam_fused_ragged_inference_size(gd):
 
 def test_conv3x3_full_size_shift_property(gd):
     """size-independent property at the bench's largest map (1024 x 1024): a 3x3 kernel that is a one-hot tap is a
-    pure shift -- checked exactly (bf16-representable data) on the LDS-patch kernel, borders included."""
+    pure shift -- checked exactly (bf16-representable data) on the LDS-patch kernel, borders included.  The comparison is the
+    exact-arithmetic helper's (conv_exact_util.py; tests/test_gpu_conv_exact.py covers every conv route this way): the fp64
+    convolution, stored as fp32, must come back bit for bit."""
+    import conv_exact_util as U
     from gan_danet_amd import _lib as L
     from gan_danet_amd import kern as K
-    x = bf16_round(seeded((1, 2, 1024, 1024), 84)).to(DEV)
+    xc = bf16_round(seeded((1, 2, 1024, 1024), 84))
+    x = xc.to(DEV)
     w = torch.zeros(2, 2, 3, 3)
     w[0, 1, 0, 2] = 1.0     # out0[y][x] = in1[y-1][x+1]
     w[1, 0, 2, 1] = 1.0     # out1[y][x] = in0[y+1][x]
     y = K.conv2d_fwd(x, w.to(DEV), None, 1, 1, L.PREC_BF16).cpu()
-    xc = x.cpu()
+    U.assert_same(y, U.to_store(U.conv(xc, w, 1, 1), "f32", U.conv(xc.abs(), w.abs(), 1, 1)), "one-hot taps at 1024 x 1024")
     ref0 = torch.zeros(1024, 1024)
     ref0[1:, :-1] = xc[0, 1, :-1, 1:]
     ref1 = torch.zeros(1024, 1024)
