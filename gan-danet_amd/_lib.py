@@ -201,6 +201,7 @@ SIGNATURES = {
     "gd_combine_inputs": (_i, [_p, _i, _i, _i, _f, _p, _i, _i, _i, _f, _p, _i, _i, _i, _p]),
     "gd_hist_match_ws_bytes": (_sz, [_l, _l]),
     "gd_hist_match": (_i, [_p, _p, _i, _l, _l, C.c_double, _p, _p, _sz, _p]),
+    "gd_hist_match_host": (_i, [_p, _p, _i, _l, _l, C.c_double, _p]),
     "gd_eval_stats_ws_bytes": (_sz, [_l]),
     "gd_eval_stats": (_i, [_p, _p, _l, _l, _p, C.c_double, C.c_double, _i, _p, _p, _sz, _p]),
     "gd_masked_plane_mean_ws_bytes": (_sz, [_l, _l]),

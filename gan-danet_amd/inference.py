@@ -54,7 +54,13 @@ def mild_histogram_matching(hr_generated: torch.Tensor, lr_grace_025: torch.Tens
     ``matched`` maps the sample's empirical CDF onto the reference field's (np.unique / np.interp semantics).  The
     notebook calls it with ``weight = 0.0`` (c1:161), where the result IS the source: that case returns the input
     untouched.  Otherwise one launch sequence per sample (``gd_hist_match``: radix sorts + a quantile-interpolation
-    kernel); the result is float64, as the notebook's numpy code returns."""
+    kernel); the result is float64, as the notebook's numpy code returns.  CPU tensors go to the host twin of that kernel
+    and give the same bits.
+
+    A NaN in ``hr_generated`` propagates to its own position only: the result is NaN there, and for the other elements it
+    ranks above every number (all NaNs sort last whatever their sign bit, as numpy sorts them).  Non-finite values in
+    ``lr_grace_025`` are outside the contract: np.interp's own rules for them differ between numpy versions, so they are
+    not tested."""
     if weight == 0.0:
         return hr_generated
     return K.hist_match(hr_generated.contiguous(), lr_grace_025.contiguous(), weight)

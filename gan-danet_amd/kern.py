@@ -421,19 +421,39 @@ def combine_inputs(lr: Tensor, aux: Tensor, s1: float = 0.5, s2: float = 0.25) -
     return out
 
 
-def hist_match(src: Tensor, ref: Tensor, weight: float) -> Tensor:
-    """per-sample mild histogram matching (test.ipynb c1:69-85); src (B, ...), ref (B, ...) fp32 -> fp64 like src"""
-    _dense(src, "histogram source"), _dense(ref, "histogram reference")
-    B = src.shape[0]
-    if ref.shape[0] != B:
+def _hist_match(be, src, ref, weight: float):
+    """one body for the device / host twins of gd_hist_match (``be``: _DEV or _HOST, below)"""
+    if be.host:                                           # _Host.dense converts; the device refuses anything but float32
+        src, ref = np.asarray(src), np.asarray(ref)
+        if src.dtype != np.float32 or ref.dtype != np.float32:
+            raise L.GandanetError(f"hist_match: expected float32 arrays, got {src.dtype} / {ref.dtype}")
+    src, ref = be.dense(src, "histogram source", be.f32), be.dense(ref, "histogram reference", be.f32)
+    if src.ndim < 1 or ref.ndim < 1 or ref.shape[0] != src.shape[0]:
         raise L.GandanetError("hist_match: batch sizes differ")
-    ns, nt = src[0].numel(), ref[0].numel()
-    nbytes = int(lib().gd_hist_match_ws_bytes(ns, nt))
-    ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8)
-    out = torch.empty(src.shape, device=src.device, dtype=torch.float64)
-    L.check(lib().gd_hist_match(_ptr(src), _ptr(ref), B, ns, nt, float(weight), _ptr(out), _ptr(ws), nbytes, _stream()),
-            "gd_hist_match")
+    B = src.shape[0]
+    ns, nt = math.prod(src.shape[1:]), math.prod(ref.shape[1:])
+    out = be.empty(src.shape, be.f64, src)
+    ws = () if be.host else be.ws(None, lib().gd_hist_match_ws_bytes(ns, nt), src, "hist_match")
+    be.call("gd_hist_match", be.ptr(src), be.ptr(ref), B, ns, nt, float(weight), be.ptr(out), *ws)
     return out
+
+
+def hist_match(src: Tensor, ref: Tensor, weight: float) -> Tensor:
+    """per-sample mild histogram matching (test.ipynb c1:69-85); src (B, ...), ref (B, ...) fp32 -> fp64 like src.
+    GPU tensors run gd_hist_match on the current stream; CPU tensors go to its host twin gd_hist_match_host (plain C++ over
+    the same per-element code, csrc/histmatch_core.h), and both give the same bits.
+
+    A NaN in ``src`` propagates to its own position only: it gives NaN there and, sorted last whatever its sign bit (as
+    numpy sorts), ranks above every number for the other elements.  Non-finite values in ``ref`` are outside the contract
+    (np.interp's own rules for them differ between numpy versions) and are not tested."""
+    if isinstance(src, Tensor) and isinstance(ref, Tensor) and not src.is_cuda and not ref.is_cuda:
+        return torch.from_numpy(_hist_match(_HOST, src.numpy(), ref.numpy(), weight))
+    return _hist_match(_DEV, src, ref, weight)
+
+
+def hist_match_host(src, ref, weight: float):
+    """``hist_match`` on HOST numpy float32 arrays (gd_hist_match_host); a new float64 array shaped like ``src``"""
+    return _hist_match(_HOST, src, ref, weight)
 
 
 def blend_region(gen: Tensor, grace: Tensor, mask: Tensor, region) -> Tensor:

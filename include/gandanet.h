@@ -505,10 +505,15 @@ int gd_round_to_16(const float* x, float* y, long n, float scale, int f16, void*
 /* test.ipynb c1:69-85 mild_histogram_matching, per sample of a batch: out[b] = (1 - weight) * src[b] + weight *
  * interp(cdf_src(src[b]), cdf_ref, sorted unique ref[b]) with numpy's np.unique / np.interp semantics (float64 result, as
  * the notebook produces).  src (B, ns), ref (B, nt) fp32; out (B, ns) fp64; ws: caller-owned scratch of
- * gd_hist_match_ws_bytes(ns, nt) bytes (sort buffers).  One radix sort pair per sample (rocPRIM via hipCUB). */
+ * gd_hist_match_ws_bytes(ns, nt) bytes (sort buffers).  One radix sort pair per sample (rocPRIM via hipCUB).
+ * Keys are ordered with every NaN last, whatever its sign bit, as numpy orders them: a NaN of src gives NaN at its own
+ * position and counts as larger than every number in the ranks of the others.  Non-finite values in ref are outside the
+ * contract.  gd_hist_match_host: the same on host pointers (a stable CPU sort of (key, index) pairs, then the same
+ * per-element function, csrc/histmatch_core.h); device and host results agree bit for bit. */
 size_t gd_hist_match_ws_bytes(long ns, long nt);
 int gd_hist_match(const float* src, const float* ref, int B, long ns, long nt, double weight, double* out, void* ws,
                   size_t ws_bytes, void* stream);
+int gd_hist_match_host(const float* src, const float* ref, int B, long ns, long nt, double weight, double* out);
 /* test.ipynb c1:87-101 smooth_blend: over the region rows [sr, er) x columns [sc, ec) of every (b, c) plane,
  * gen = gen * (1 - mask) + grace * mask, in place; mask (er-sr, ec-sc) fp32 is the feathered window the host builds. */
 int gd_blend_region(float* gen, const float* grace, const float* mask, int BC, int H, int W, int sr, int er, int sc,

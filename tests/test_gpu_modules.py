@@ -1218,16 +1218,7 @@ def test_mild_histogram_matching_vs_numpy_restatement(gd):
     exact, so agreement is to double round-off"""
     import numpy as np
     from gan_danet_amd import inference as INF
-
-    def ref_impl(source, reference, weight):
-        oldshape = source.shape
-        source, reference = source.ravel(), reference.ravel()
-        s_vals, bin_idx, s_counts = np.unique(source, return_inverse=True, return_counts=True)
-        t_vals, t_counts = np.unique(reference, return_counts=True)
-        s_q = np.cumsum(s_counts).astype(np.float64) / np.sum(s_counts)
-        t_q = np.cumsum(t_counts).astype(np.float64) / np.sum(t_counts)
-        matched = np.interp(s_q, t_q, t_vals)[bin_idx].reshape(oldshape)
-        return ((1 - weight) * source + weight * matched.ravel()).reshape(oldshape)
+    from histmatch_util import restatement as ref_impl      # the notebook's numpy code, shared with test_gpu_histmatch.py
 
     rs = np.random.RandomState(3)
     cases = [
