@@ -43,6 +43,9 @@ from .biascorrect import QuantileMap, series_quantiles
 from . import lagcorr
 from .lagcorr import (LagCorrelation, autocorrelation, correlation_significance, driver_lags, fdr_threshold,
                       lag_correlation)
+from . import collocation
+from .collocation import (TripleCollocation, TripleCollocationBootstrap, bootstrap_indices, triple_collocation,
+                          triple_collocation_bootstrap)
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

@@ -33,6 +33,10 @@ LAG_MAX, LAG_MAX_T, LAG_CHUNK = 64, 2048, 32   # GD_LAG_MAX, GD_LAG_MAX_T, GD_LA
 LAG_PLANES = ("best_lag", "best_r", "best_n", "r0")   # GD_LAG_*: plane k of `best`
 LAG_SELECT = {"abs": 0, "max": 1, "min": 2}           # GD_LAG_SELECT_*
 ACF_KINDS = {"pearson": 0, "standard": 1}             # GD_ACF_*
+TC_MAX_T, TC_MAX_B, TC_MAX_Q = 2048, 2048, 8   # GD_TC_MAX_T, GD_TC_MAX_B, GD_TC_MAX_Q
+TC_STATS = ("err_var_x", "err_var_y", "err_var_z", "rho2_x", "rho2_y", "rho2_z", "beta_y", "beta_z")   # GD_TC_*: plane k of `stats`
+TC_COVS = ("xx", "yy", "zz", "xy", "xz", "yz")   # row k of `cov`
+TC_FLAGS = {"masked": 1, "few": 2, "nonpos": 4, "neg_x": 8, "neg_y": 16, "neg_z": 32, "rho2": 64}   # GD_TC_FLAG_*
 ENSV_MAX_M, ENSV_F64, ENSV_FAIR = 32, 1, 2   # GD_ENSV_MAX_M, GD_ENSV_F64, GD_ENSV_FAIR
 ENSV_FIELDS = ("n", "tied", "crps", "crps_gauss", "abs_e", "e2", "s2")   # GD_ENSV_*: record slot k; then cover, hist
 ENSV_COVER, ENSV_HIST, ENSV_BINS, ENSV_REC = 7, 11, 33, 44   # GD_ENSV_COVER, GD_ENSV_HIST, GD_ENSV_BINS, GD_ENSV_REC
@@ -255,6 +259,12 @@ SIGNATURES = {
     "gd_series_acf": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p, _p]),
     "gd_series_acf_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p]),
     "gd_corr_signif": (_i, [_p, _p, _p, _l, _p, _l, _p, _p, _p, _p]),
+    "gd_tc_estimate": (_i, [_p, _p, _p, _i, _l, _l, _i, _p, _p, _p, _p, _p, _p]),
+    "gd_tc_estimate_host": (_i, [_p, _p, _p, _i, _l, _l, _i, _p, _p, _p, _p, _p]),
+    "gd_tc_group": (_i, [_l]),
+    "gd_tc_bootstrap_workspace": (_sz, [_l, _l, _l]),
+    "gd_tc_bootstrap": (_i, [_p, _p, _p, _i, _l, _l, _p, _l, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "gd_tc_bootstrap_host": (_i, [_p, _p, _p, _i, _l, _l, _p, _l, _i, _p, _i, _p, _p, _p, _p]),
     "gd_ens_verify_ws_bytes": (_sz, [_l]),
     "gd_ens_verify": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gd_ens_verify_host": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p]),

@@ -1,9 +1,9 @@
 // Shared host and device plumbing of the analysis kernels (evalstats, gradguard, filters, spline, prepare, basins, stl,
-// series, trend, ensverify, eof, spectra, drought, ccl, neighborhood, quantmap, lagcorr): the fp32 / fp64 dtype tag, its alignment
+// series, trend, ensverify, eof, spectra, drought, ccl, neighborhood, quantmap, lagcorr, tcol): the fp32 / fp64 dtype tag, its alignment
 // checks and its dispatch (gd_with_dtype: stl, series, trend, ensverify, eof, spectra, drought, ccl, neighborhood, quantmap,
-// lagcorr),
+// lagcorr, tcol),
 // 16-byte vector access with a scalar head and tail, launch-grid sizing, the one-thread-per-item launcher with its host twin
-// (gd_for_items: series, eof, drought, ccl, quantmap, lagcorr), and the fixed-order fp64 reductions.  The training-path kernels do
+// (gd_for_items: series, eof, drought, ccl, quantmap, lagcorr, tcol), and the fixed-order fp64 reductions.  The training-path kernels do
 // not include this file.
 #pragma once
 #include "common.h"

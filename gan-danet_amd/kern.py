@@ -2970,3 +2970,93 @@ def corr_signif(r: Tensor, n: Tensor, r1a: Tensor, r1b: Tensor):
     n_eff, z, p = (torch.empty_like(r) for _ in range(3))
     _Dev.call("gd_corr_signif", _ptr(r), _ptr(n), _ptr(r1a), r1a.numel(), _ptr(r1b), M, _ptr(n_eff), _ptr(z), _ptr(p))
     return n_eff, z, p
+
+
+# ---- triple collocation (include/gandanet.h, "Triple collocation"; tcol.hip) ---------------------------------------------------
+def _tc_cubes(be, x, y, z, fn: str):
+    x, dt = be.array(x, f"{fn} x", 2)
+    cubes = [x]
+    for c, nm in ((y, "y"), (z, "z")):
+        c, dtc = be.array(c, f"{fn} {nm}", 2)
+        if dtc != dt or tuple(c.shape) != tuple(x.shape):
+            raise L.GandanetError(f"{fn}: {nm} is {tuple(x.shape)} {x.dtype} like x, got {tuple(c.shape)} {c.dtype}")
+        cubes.append(c)
+    T, M = x.shape
+    if not be.host and not 1 <= T <= L.TC_MAX_T:
+        raise L.GandanetError(f"{fn}: 1 <= T <= {L.TC_MAX_T}, got T = {T}")
+    return cubes, dt, int(T), int(M)
+
+
+def _tc_min_samples(min_samples, fn: str, host: bool) -> int:
+    if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or (not host and min_samples < 3):
+        raise L.GandanetError(f"{fn}: min_samples is an integer >= 3, got {min_samples!r}")
+    return int(min_samples)
+
+
+def _tc_estimate(be, x, y, z, min_samples: int = 10, mask=None, cov: bool = True):
+    """the triple collocation of three dense fp32 / fp64 cubes (T, M) of one dtype: new arrays (stats (8, M) fp64 in the order of
+    L.TC_STATS, cov (6, M) fp64 in the order of L.TC_COVS or None, n (M,) int32, flags (M,) int32, the bits of L.TC_FLAGS).
+    ``mask``: M uint8, 0 = leave the series out.  No host sync."""
+    (x, y, z), dt, T, M = _tc_cubes(be, x, y, z, "tc_estimate")
+    min_samples = _tc_min_samples(min_samples, "tc_estimate", be.host)
+    mask = be.vec(mask, M, "tc_estimate mask", be.u8)
+    stats = be.empty((len(L.TC_STATS), M), be.f64, x)
+    cv = be.empty((len(L.TC_COVS), M), be.f64, x) if cov else None
+    n, flags = be.empty((M,), be.i32, x), be.empty((M,), be.i32, x)
+    be.call("gd_tc_estimate", be.ptr(x), be.ptr(y), be.ptr(z), dt, T, M, min_samples, be.ptr(mask), be.ptr(stats), be.ptr(cv), be.ptr(n),
+            be.ptr(flags))
+    return stats, cv, n, flags
+
+
+tc_estimate = functools.partial(_tc_estimate, _DEV)
+tc_estimate_host = functools.partial(_tc_estimate, _HOST)   # plain C++ over the same per-series body
+
+
+def tc_bootstrap_workspace(T: int, M: int, B: int) -> int:
+    """the bytes that hold the replicates of all M pixels at once (gd_tc_bootstrap_workspace)"""
+    return int(lib().gd_tc_bootstrap_workspace(int(T), int(M), int(B)))
+
+
+def tc_bootstrap_min_workspace(T: int, B: int) -> int:
+    """the smallest legal workspace: the index-check word and one group of pixels"""
+    return 8 + int(lib().gd_tc_group(int(T))) * len(L.TC_STATS) * int(B) * 8
+
+
+def _tc_bootstrap(be, x, y, z, idx, q=(0.025, 0.5, 0.975), min_samples: int = 10, mask=None, replicates: bool = False, ws=None):
+    """the bootstrap of ``tc_estimate`` over the (T, B) uint16 table ``idx`` of step numbers (``collocation.bootstrap_indices``;
+    a device tensor on the device side): new arrays (summary (8, 2 + Q, M) fp64: mean, std (ddof 1) and the quantiles at the
+    probabilities ``q`` (a host sequence of 1 .. L.TC_MAX_Q numbers in [0, 1]) of the replicates that are not NaN, n_ok (8, M)
+    int32: their number, replicates (B, 8, M) fp64 or None).  ``ws``: a uint8 device workspace of at least
+    tc_bootstrap_min_workspace(T, B) bytes (default: min(tc_bootstrap_workspace(T, M, B), 256 MiB, not below the minimum)); no
+    result depends on its size.  The device side waits once for the stream (the check of the index table)."""
+    (x, y, z), dt, T, M = _tc_cubes(be, x, y, z, "tc_bootstrap")
+    min_samples = _tc_min_samples(min_samples, "tc_bootstrap", be.host)
+    if be.host:
+        idx = np.ascontiguousarray(idx)
+        qd = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if idx.dtype != np.uint16:
+            raise L.GandanetError(f"tc_bootstrap: idx is a uint16 array, got {idx.dtype}")
+    else:
+        _dense(idx, "tc_bootstrap idx", torch.uint16)
+        try:
+            qa = np.atleast_1d(np.asarray(q, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise L.GandanetError(f"tc_bootstrap: q is a sequence of numbers held on the host, got {type(q).__name__}") from None
+        if qa.ndim != 1 or not 1 <= qa.size <= L.TC_MAX_Q or not bool(np.all((qa >= 0.0) & (qa <= 1.0))):
+            raise L.GandanetError(f"tc_bootstrap: q holds 1 .. {L.TC_MAX_Q} probabilities in [0, 1], got {qa.tolist()}")
+        qd = torch.from_numpy(np.ascontiguousarray(qa)).to(x.device)
+    if idx.ndim != 2 or idx.shape[0] != T or not (be.host or 1 <= idx.shape[1] <= L.TC_MAX_B):
+        raise L.GandanetError(f"tc_bootstrap: idx is ({T}, B) with 1 <= B <= {L.TC_MAX_B}, got {tuple(idx.shape)}")
+    B, Q = int(idx.shape[1]), math.prod(qd.shape)
+    mask = be.vec(mask, M, "tc_bootstrap mask", be.u8)
+    summary = be.empty((len(L.TC_STATS), 2 + Q, M), be.f64, x)
+    n_ok = be.empty((len(L.TC_STATS), M), be.i32, x)
+    rep = be.empty((B, len(L.TC_STATS), M), be.f64, x) if replicates else None
+    nbytes = 0 if be.host else max(min(tc_bootstrap_workspace(T, M, B), 1 << 28), tc_bootstrap_min_workspace(T, B))
+    be.call("gd_tc_bootstrap", be.ptr(x), be.ptr(y), be.ptr(z), dt, T, M, be.ptr(idx), B, min_samples, be.ptr(qd), Q, be.ptr(mask),
+            be.ptr(summary), be.ptr(n_ok), be.ptr(rep), *be.ws(ws, nbytes, x, "tc_bootstrap"))
+    return summary, n_ok, rep
+
+
+tc_bootstrap = functools.partial(_tc_bootstrap, _DEV)
+tc_bootstrap_host = functools.partial(_tc_bootstrap, _HOST)   # plain C++ over the same per-step code, one pixel at a time

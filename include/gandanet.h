@@ -1520,6 +1520,79 @@ int gd_qm_apply(const void* x, int dtype, long T, long H, long W, int f, const d
 int gd_qm_apply_host(const void* x, int dtype, long T, long H, long W, int f, const double* model_q, const double* obs_q,
                      const double* own_q, const double* p, int Q, int period, int phase, int kind, int extrapolate, void* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Triple collocation (tcol.hip, csrc/tcol_core.h): how large is the random error of each of three collocated products when
+ * none of them is the truth (Stoffelen 1998; covariance form and the squared correlation with the unknown truth of McColl
+ * et al. 2014), per pixel, and a moving-block bootstrap over time that puts an interval on every statistic.
+ * The layout is that of "Per-pixel time series": x, y, z are dense (T, M) arrays, series m at x[t * M + m], storage fp32
+ * (dtype 0) or fp64 (dtype 1), one dtype for all three; all arithmetic fp64 with every operation rounded on its own (nothing
+ * is contracted into an FMA).  1 <= T <= GD_TC_MAX_T.  The method assumes mutually independent errors; a seasonal cycle
+ * shared by the three products must be removed by the caller.
+ *   Deletion     a step counts for a pixel only if x, y and z are all not NaN there (listwise); n is their number.
+ *   Centring     mx, my, mz: the means over the counted steps by the recurrence m += (v - m) * (1 / k) in time order (k the
+ *                number of counted steps so far, this one included); u = x - mx, v = y - my, w = z - mz.
+ *   Sums         Su, Sv, Sw, Suu, Svv, Sww, Suv, Suw, Svw over the counted steps in ascending order, each from +0.0.
+ *   Covariances  Qab = (Sab - Sa * Sb / n) / (n - 1), evaluated as written, left to right.
+ *   Statistics   GD_TC_STATS = 8 planes, in this order:
+ *                  err_var_x = Qxx - Qxy * Qxz / Qyz   err_var_y = Qyy - Qxy * Qyz / Qxz   err_var_z = Qzz - Qxz * Qyz / Qxy
+ *                  rho2_x = Qxy * Qxz / (Qxx * Qyz)    rho2_y = Qxy * Qyz / (Qyy * Qxz)    rho2_z = Qxz * Qyz / (Qzz * Qxy)
+ *                  beta_y = Qyz / Qxz                  beta_z = Qyz / Qxy      (the scale of y and z against x; beta_x = 1)
+ *   Validity     all eight are NaN when the pixel is masked out (mask[m] == 0; mask NULL or M bytes; such a pixel is not
+ *                read and has n = 0), when n < min_samples (min_samples >= 3), or when any of Qxy, Qxz, Qyz is not > 0 (the
+ *                products do not agree in sign: collocation is undefined).  A negative error variance or a rho2 > 1 is a
+ *                legitimate sampling outcome: it is returned as it is and only flagged.
+ *   flags        (M,) int32, one bit per GD_TC_FLAG_*: MASKED, FEW (n < min_samples), NONPOS (a cross-covariance not > 0),
+ *                NEG_X, NEG_Y, NEG_Z (that error variance < 0), RHO2 (any rho2 > 1).
+ * gd_tc_estimate: stats (GD_TC_STATS, M) doubles, planar; cov (6, M) doubles Qxx Qyy Qzz Qxy Qxz Qyz, or NULL: NaN where the
+ * pixel is masked or n < min_samples, else the covariances (also where the statistics are undefined); n and flags (M,)
+ * int32.  One thread per series, lanes along the pixels, two passes over the cubes (means, then sums).
+ *
+ * gd_tc_bootstrap: idx is a (T, B) table of uint16 step numbers, idx[t * B + b] in 0 .. T - 1, in DEVICE memory, shared by all
+ * pixels (every pixel is resampled at the same times); 1 <= B <= GD_TC_MAX_B.  Replicate b of a pixel takes the steps
+ * idx[0, b], idx[1, b], .., idx[T - 1, b] in that order through the same deletion, the same nine sums and the same eight
+ * formulas; u, v, w are centred with the means of the ORIGINAL series (the covariance form is shift invariant, the centring
+ * only conditions the sums).  Per pixel and statistic, over the replicates whose value is not NaN, in ascending b:
+ *   n_ok (GD_TC_STATS, M) int32: their number; with k = 1, 2, .. counting them,
+ *   d = v - m;  m = m + d * (1 / k);  m2 = m2 + d * (v - m)  (m, m2 from +0.0);  mean = m,  std = sqrt(m2 / (n_ok - 1)),
+ *   quantile j = numpy.nanquantile(values, q[j]) with method "linear", through the keys, sort and node rules of "Bias
+ *   correction".  summary is (GD_TC_STATS, 2 + Q, M) doubles: mean, std, then the Q quantiles, 1 <= Q <= GD_TC_MAX_Q; all NaN
+ *   where n_ok < 2.  q: Q doubles in [0, 1] in DEVICE memory (HOST for the twin).  replicates: NULL, or (B, GD_TC_STATS, M)
+ *   doubles that receive every replicate value.
+ * workspace: gd_tc_bootstrap_workspace(T, M, B) bytes hold all pixels at once; with fewer the pixels are walked in chunks
+ * (whole groups of gd_tc_group(T) pixels), down to 8 + gd_tc_group(T) * GD_TC_STATS * B * 8 bytes; less is an error that names
+ * the bytes needed.  The first 8 bytes receive the verdict of the index check; the call copies them back and waits for the
+ * stream before the first replicate kernel (the only synchronisation), so an index >= T is an error and reads nothing.
+ * A workgroup owns gd_tc_group(T) neighbouring series (8 up to T = 340, then 4, 2, 1: the three centred series of every pixel
+ * of the group are staged in at most 64 KB of LDS, NaN marking a deleted step), a thread runs whole replicates with the
+ * nine sums in registers, the lanes of a wave are neighbouring replicates of one pixel; the replicate values go to the
+ * workspace as (GD_TC_STATS, pixels of the chunk, B); one wave per (pixel, statistic) sorts them in LDS for the quantiles and
+ * one thread per (pixel, statistic) runs the mean / std recurrence.  No atomics, nothing allocated; no result depends on
+ * the workspace size, on M, on a pixel's column or on the launch.  The *_host twins take every pointer in HOST memory (no
+ * stream, no workspace) and run the same per-step code: all outputs agree bit for bit.
+ * Errors (-1, gd_last_error): a NULL input or output, dtype, T, M, B, Q out of range, min_samples < 3, an index >= T, a
+ * pointer that is not element aligned, a workspace smaller than one group.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_TC_MAX_T 2048
+#define GD_TC_MAX_B 2048
+#define GD_TC_MAX_Q 8
+#define GD_TC_COVS 6
+enum { GD_TC_ERR_VAR_X = 0, GD_TC_ERR_VAR_Y = 1, GD_TC_ERR_VAR_Z = 2, GD_TC_RHO2_X = 3, GD_TC_RHO2_Y = 4, GD_TC_RHO2_Z = 5,
+       GD_TC_BETA_Y = 6, GD_TC_BETA_Z = 7, GD_TC_STATS = 8 };
+enum { GD_TC_FLAG_MASKED = 1, GD_TC_FLAG_FEW = 2, GD_TC_FLAG_NONPOS = 4, GD_TC_FLAG_NEG_X = 8, GD_TC_FLAG_NEG_Y = 16,
+       GD_TC_FLAG_NEG_Z = 32, GD_TC_FLAG_RHO2 = 64 };
+int gd_tc_estimate(const void* x, const void* y, const void* z, int dtype, long T, long M, int min_samples, const unsigned char* mask,
+                   double* stats, double* cov, int* n, int* flags, void* stream);
+int gd_tc_estimate_host(const void* x, const void* y, const void* z, int dtype, long T, long M, int min_samples,
+                        const unsigned char* mask, double* stats, double* cov, int* n, int* flags);
+int gd_tc_group(long T);   /* pixels per workgroup of gd_tc_bootstrap at this T (0 for a T out of range) */
+size_t gd_tc_bootstrap_workspace(long T, long M, long B);
+int gd_tc_bootstrap(const void* x, const void* y, const void* z, int dtype, long T, long M, const uint16_t* idx, long B,
+                    int min_samples, const double* q, int Q, const unsigned char* mask, double* summary, int* n_ok, double* replicates,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int gd_tc_bootstrap_host(const void* x, const void* y, const void* z, int dtype, long T, long M, const uint16_t* idx, long B,
+                         int min_samples, const double* q, int Q, const unsigned char* mask, double* summary, int* n_ok,
+                         double* replicates);
+
 #ifdef __cplusplus
 }
 #endif
