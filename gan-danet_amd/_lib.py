@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libgandanet_hip.so")
 
 PREC_FP32, PREC_BF16, PREC_X3 = 0, 1, 2   # GD_PREC_*: exact f32 MFMA / bf16 operands / split-bf16 (hi + lo, three MFMAs per product)
-PAM_BWD_K64_ATOMIC, PAM_BWD_K64_PARTS, PAM_BWD_K32_PARTS, PAM_BWD_TWO_KERNEL = 0, 1, 2, 3
+PAM_BWD_K64_ATOMIC, PAM_BWD_K64_PARTS, PAM_BWD_TWO_KERNEL = 0, 1, 3   # GD_PAM_BWD_* (2 is retired)
 ACT_NONE, ACT_RELU, ACT_LEAKY02, ACT_SIGMOID = 0, 1, 2, 3
 EVAL_F64, EVAL_SKIP_NAN = 1, 2   # GD_EVAL_*
 GUARD_SQNORM, GUARD_NORM, GUARD_COEF, GUARD_OK, GUARD_APPLIED, GUARD_SKIPPED, GUARD_RECORD = range(7)   # GD_GUARD_*

@@ -15,14 +15,14 @@
 //   * the probability tile is already the B operand of O^T = V P^T  (accumulator-as-operand, no LDS trip),
 //   * O^T comes out with the query on the lane: the online rescale is lane-local and the store to the NCHW
 //     output is coalesced along pixels.
-// Backward: one workgroup = 8 (or 4) waves = 256 (128) keys, 32 per wave, holding dV^T and dK^T in accumulators while
-//   it sweeps the queries in 32-row tiles; S and dP are computed with the key on the lane, so P and dS are directly
-//   the B operands of dV^T += dO^T P and dK^T += Q^T dS.  For dQ the dS tile is turned around through wave-private
-//   LDS (transpose read), multiplied by the wave's K rows and the workgroup's sum is stored as a bf16 part per key
-//   block; pam_dq_reduce_kernel adds the key blocks.  No atomics in this file's kernels.  (pam_bwd_dq_kernel: the
-//   scratch-free alternative, a query-parallel kernel that recomputes S and dP.)  The DEFAULT backward is the K64 kernel
-//   of pam_bwd64.hip (64 keys per wave, one wave per SIMD, fp32 atomics or deterministic parts for dQ); the kernels
-//   here are its reproducible / scratch-free fallbacks (gd_pam_flash_bwd forms 2 and 3).
+// Backward: the product's backward is the K64 kernel of pam_bwd64.hip (64 keys per wave, one wave per SIMD, fp32
+//   atomics or deterministic parts for dQ; gd_pam_flash_bwd forms 0 and 1).  This file holds the scratch-free
+//   two-kernel form (form 3), the independent reference the K64 forms are tested against:
+//   * pam_bwd_dkv3_kernel, key-parallel: one workgroup = 4 waves = 128 keys, 32 per wave, holding dV^T and dK^T in
+//     accumulators while it sweeps the queries in 32-row tiles; S and dP are computed with the key on the lane, so P
+//     and dS are directly the B operands of dV^T += dO^T P and dK^T += Q^T dS.
+//   * pam_bwd_dq_kernel, query-parallel like the forward: recomputes S and dP and accumulates dQ^T in registers.
+//   Neither uses atomics or scratch: form 3 is bitwise reproducible.
 #include <stdlib.h>
 #include <type_traits>
 
@@ -359,26 +359,22 @@ __global__ __launch_bounds__(256) void pam_row_shift_kernel(const unsigned short
 }
 
 // =====================================================================================================
-// backward, part 1c: dK^T / dV^T, transpose-read variant.  Only Q [i][d] and dO [i][c] are staged per query
-// tile; the "transposed" A operands of dV^T += dO^T P and dK^T += Q^T dS are taken from the SAME images with
-// ds_read_b64_tr_b16 (4 query rows x 16 channel columns per 16-lane group), so the q^T / dO^T copies, half of
-// the staging traffic and half of the tile LDS disappear.  V rows of the workgroup's keys live in LDS.
-// NW = 4 (without dQ): 4 waves per workgroup and two independent workgroups per CU: their phases drift apart, so one's MFMA
+// backward, two-kernel form, part 1: dK^T / dV^T (dQ is pam_bwd_dq_kernel's).  Only Q [i][d] and dO [i][c] are
+// staged per query tile; the "transposed" A operands of dV^T += dO^T P and dK^T += Q^T dS are taken from the SAME
+// images with ds_read_b64_tr_b16 (4 query rows x 16 channel columns per 16-lane group), so no q^T / dO^T copies are
+// staged.  V rows of the workgroup's keys live in LDS.
+// 4 waves = 128 keys per workgroup and two independent workgroups per CU: their phases drift apart, so one's MFMA
 // segments overlap the other's softmax / staging segments instead of all eight waves meeting at one barrier.
+// kn is not read (dQ's kernel reads it): the two kernels take the same operand list, and without it the compiler
+// numbers the tile loop's registers differently at CT = 2, 3, 5, 6, so the argument stays.
 // =====================================================================================================
-// DQ: also emit this key block's contribution to dQ.  dS is already in registers here; recomputing S and dP in a
-// second query-parallel kernel (pam_bwd_dq_kernel) costs 14 MFMAs per 32x32 tile, turning the tile around through
-// 2.5 KB of wave-private LDS and 2 more MFMAs does not: each wave transposes its dS tile (LDS transpose read),
-// multiplies by its K rows, the NW waves' partial dQ^T tiles are summed after the barrier and stored as bf16
-// [key block][query][32 d]; pam_dq_reduce_kernel sums the key blocks.  No atomics: deterministic.
-template <int CT, bool DQ, int NW = 4>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void pam_bwd_dkv3_kernel(
+template <int CT>
+__global__ __launch_bounds__(256, 2) void pam_bwd_dkv3_kernel(
     const unsigned short* __restrict__ qt, const unsigned short* __restrict__ kt, const unsigned short* __restrict__ kn,
     const unsigned short* __restrict__ vt, const unsigned short* __restrict__ dot_, const float* __restrict__ lse,
-    const float* __restrict__ delta, int N, int Npad, float* __restrict__ dkn, float* __restrict__ dv,
-    unsigned short* __restrict__ dq_part) {
+    const float* __restrict__ delta, int N, int Npad, float* __restrict__ dkn, float* __restrict__ dv) {
     constexpr int CP = CT * 32;
-    constexpr int NT = NW * 64, KEYS = NW * 32;    // NW = 4: 128 keys, two workgroups per CU; NW = 8: 256 keys, one
+    constexpr int NT = 256, KEYS = 128;
     constexpr int DLD = CP + 8;
     constexpr int NCHUNK = 128 + 128 * CT;
     constexpr int NPRE = (NCHUNK + NT - 1) / NT;
@@ -388,8 +384,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void pam_bwd_dkv3_kernel(
     constexpr int DOLD = CP + 32;                                // dO rows, chunk-swizzled (do_off)
     __shared__ __attribute__((aligned(16))) unsigned short dOs[32 * DOLD];
     __shared__ float Ls[32], Ds[32];
-    constexpr int XLD = 36;                                      // 72-byte rows: 32 lanes x 8 bytes hit 32 distinct bank pairs (80-byte rows: 2-way, PMC)
-    __shared__ __attribute__((aligned(16))) unsigned short Xs[DQ ? NW * 32 * XLD : 8];   // per wave: dS^T, then its dQ^T part
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -400,16 +394,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void pam_bwd_dkv3_kernel(
     bf16x8_t kfB[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) kfB[s] = *reinterpret_cast<const bf16x8_t*>(kt + (nb + j0 + r) * 32 + s * 16 + 8 * h);
-    // K^T rows of this wave's keys as the A operand of dQ^T[d][i] += K^T[d][j] dS^T[j][i]: lane = d, 8 keys per k-step
-    // (kn is stored perm16: one 16-byte read is an accumulator-row-ordered k-step)
-    bf16x8_t knA[2];
-    if (DQ) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-            knA[s] = *reinterpret_cast<const bf16x8_t*>(kn + ((long)b * 32 + r) * Npad + j0 + s * 16 + 8 * h);
-    }
-    unsigned short* Xw = Xs + (DQ ? wave * 32 * XLD : 0);
-    unsigned short* part = DQ ? dq_part + ((long)b * (Npad / KEYS) + blockIdx.x) * Npad * 32 : nullptr;
     {
         const unsigned short* vsrc = vt + (nb + (long)blockIdx.x * KEYS) * CP;
         for (int c = tid; c < KEYS * (CP / 8); c += NT) {
@@ -518,59 +502,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void pam_bwd_dkv3_kernel(
             pf[s] = pack_frag(sacc, s);
             dsf[s] = pack_frag(dpacc, s);
         }
-        // the dS tile takes a round trip through wave-private LDS (transpose) for dQ; it is written before the dV^T
-        // MFMAs and read back after them, so the trip is covered by matrix work
-        if (DQ) {
-            // dS tile [query rows][key lanes] -> X[key][query] (this lane's 16 queries are 4 runs of 4)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const u32x4_t w = __builtin_bit_cast(u32x4_t, dsf[s]);
-                const u32x2_t lo = {w.x, w.y}, hi = {w.z, w.w};
-                *reinterpret_cast<u32x2_t*>(Xw + r * XLD + 16 * s + 4 * h) = lo;
-                *reinterpret_cast<u32x2_t*>(Xw + r * XLD + 16 * s + 8 + 4 * h) = hi;
-            }
-        }
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int s = 0; s < 2; ++s) dvacc[ct] = mfma_bf16(read_tr_frag_sw(dOs, DOLD, s, ct, lane), pf[s], dvacc[ct]);
-        f32x16_t dqp;
-        if (DQ) {
-            // transpose read = the B operand (lane = query, k = key) of dQ^T[d][i] += K^T[d][j] dS^T[j][i]
-#pragma unroll
-            for (int e = 0; e < 16; ++e) dqp[e] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) dqp = mfma_bf16(knA[s], read_tr_frag(Xw, XLD, s, 0, lane), dqp);
-        }
 #pragma unroll
         for (int s = 0; s < 2; ++s) dkacc = mfma_bf16(read_tr_frag(Qs, B_QLD, s, 0, lane), dsf[s], dkacc);
-        if (DQ) {
-            // dQ^T part [d rows][query lanes] -> P[query][d] over the same wave-private region
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const u32x4_t w = __builtin_bit_cast(u32x4_t, pack_frag(dqp, s));
-                const u32x2_t lo = {w.x, w.y}, hi = {w.z, w.w};
-                *reinterpret_cast<u32x2_t*>(Xw + r * XLD + 16 * s + 4 * h) = lo;
-                *reinterpret_cast<u32x2_t*>(Xw + r * XLD + 16 * s + 8 + 4 * h) = hi;
-            }
-        }
         __syncthreads();
-        if (DQ) {   // sum the NW waves' parts: thread = (query, 4 d) ; 2 KiB contiguous per key block and query tile
-            const int q = (tid & 255) >> 3, dg = (tid & 7) * 4;
-            float acc4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int w4 = 0; w4 < NW; ++w4) {
-                const u32x2_t v2 = *reinterpret_cast<const u32x2_t*>(Xs + w4 * 32 * XLD + q * XLD + dg);
-                acc4[0] += gd_bf2f((unsigned short)(v2.x & 0xFFFFu));
-                acc4[1] += gd_bf2f((unsigned short)(v2.x >> 16));
-                acc4[2] += gd_bf2f((unsigned short)(v2.y & 0xFFFFu));
-                acc4[3] += gd_bf2f((unsigned short)(v2.y >> 16));
-            }
-            const u32x2_t o = {gd_pack_bf2(acc4[0], acc4[1]), gd_pack_bf2(acc4[2], acc4[3])};
-            if (tid < 256) *reinterpret_cast<u32x2_t*>(part + ((long)i0 + q) * 32 + dg) = o;
+        if (qtile + 1 < nqt) {
+            store_tile();
+            __syncthreads();
         }
-        if (qtile + 1 < nqt) store_tile();
-        if (DQ || qtile + 1 < nqt) __syncthreads();
     }
 
     const int j = j0 + r;
@@ -580,36 +522,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void pam_bwd_dkv3_kernel(
         for (int e = 0; e < 16; ++e) dv[((long)b * CP + ct * 32 + acc_row(e, h)) * Npad + j] = dvacc[ct][e];
 #pragma unroll
     for (int e = 0; e < 16; ++e) dkn[((long)b * 32 + acc_row(e, h)) * Npad + j] = dkacc[e] * LN2;   // Q^T was q * log2 e
-}
-
-// dQ^T[b][d][i] = sum over key blocks of the bf16 parts written by pam_bwd_dkv3_kernel<CT, true>
-//   part : (B, KB, Npad, 32) bf16 ; dqn : (B, 32, Npad) fp32.  One workgroup = 64 queries of one image; a key block's
-//   slab for them is 4 KiB contiguous (thread = query x 8 d, 16-byte loads).
-__global__ __launch_bounds__(256) void pam_dq_reduce_kernel(const unsigned short* __restrict__ part, int KB, int Npad,
-                                                           float* __restrict__ dqn) {
-    __shared__ float tile[32][65];
-    const int b = blockIdx.y, i0 = blockIdx.x * 64;
-    const int q = threadIdx.x >> 2, d8 = (threadIdx.x & 3) * 8;
-    const unsigned short* p = part + ((long)b * KB * Npad + i0 + q) * 32 + d8;
-    float acc[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-#pragma unroll 4
-    for (int kb = 0; kb < KB; ++kb) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(p + (long)kb * Npad * 32);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            acc[2 * k] += gd_bf2f((unsigned short)(v[k] & 0xFFFFu));
-            acc[2 * k + 1] += gd_bf2f((unsigned short)(v[k] >> 16));
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tile[d8 + k][q] = acc[k];
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < 32 * 64; idx += 256) {
-        const int d = idx >> 6, qq = idx & 63;
-        dqn[((long)b * 32 + d) * Npad + i0 + qq] = tile[d][qq];
-    }
 }
 
 // =====================================================================================================
@@ -857,19 +769,12 @@ extern "C" int gd_pam_key_sqnorm_max(const void* kt, int B, int N, int Npad, int
     return 0;
 }
 
-extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int nb, float* dqn, void* stream) {
-    hipLaunchKernelGGL(pam_dq_reduce_kernel, dim3(Npad / 64, nb), dim3(256), 0, (hipStream_t)stream,
-                       (const unsigned short*)part, KB, Npad, dqn);
-}
-
-// Backward forms (gandanet.h GD_PAM_BWD_*):
+// Backward forms (gandanet.h GD_PAM_BWD_*; 2 was the retired K32 parts form and is rejected):
 //   0 K64_ATOMIC : 4 waves x 64 keys, one wave per SIMD, fp32 atomics for dQ            (default, fastest)
 //   1 K64_PARTS  : the same kernel, dQ as bf16 parts per 256-key block + streaming sum   (bitwise reproducible)
-//   2 K32_PARTS  : round-1 kernel, 8 waves x 32 keys, bf16 parts                         (bitwise reproducible)
 //   3 TWO_KERNEL : dK/dV kernel + query-parallel dQ kernel recomputing S and dP          (no scratch)
 extern "C" size_t gd_pam_bwd_scratch_bytes(int Npad, int form) {
     if (form == 0 || form == 1) return gd_pam_bwd64_scratch_bytes(Npad, form == 1);
-    if (form == 2) return (size_t)(Npad / 256) * (size_t)Npad * 32 * sizeof(unsigned short);
     return 0;
 }
 
@@ -881,39 +786,32 @@ extern "C" int gd_pam_flash_bwd(const void* qt, const void* kt, const void* kn, 
     GD_CHECK_ARG(out_bs == 0 || (form == 0 && out_bs >= (long)Cp * Npad), "gd_pam_flash_bwd: a shared output batch stride needs form 0");
     GD_CHECK_ARG(B > 0 && B <= 65535 && N > 0 && Npad >= N && Npad % 256 == 0, "gd_pam_flash_bwd: Npad must be a multiple of 256 >= N");
     GD_CHECK_ARG(Cp > 0 && Cp % 32 == 0 && Cp <= 192, "gd_pam_flash_bwd: Cp must be a multiple of 32 <= 192");
-    GD_CHECK_ARG(form >= 0 && form <= 3, "gd_pam_flash_bwd: form must be 0..3");
+    GD_CHECK_ARG(form == 0 || form == 1 || form == 3, "gd_pam_flash_bwd: form must be 0, 1 or 3");
     GD_CHECK_ARG(!f16 || form <= 1, "gd_pam_flash_bwd: fp16 operands need form 0 or 1");
     hipStream_t s = (hipStream_t)stream;
     const unsigned short *q = (const unsigned short*)qt, *k = (const unsigned short*)kt, *kT = (const unsigned short*)kn;
     const unsigned short *v = (const unsigned short*)vt, *dO = (const unsigned short*)dot_;
-    const size_t per_image = gd_pam_bwd_scratch_bytes(Npad, form);
-    if (form <= 2) {
+    if (form <= 1) {
+        const size_t per_image = gd_pam_bwd_scratch_bytes(Npad, form);
         GD_CHECK_ARG(scratch && scratch_bytes >= per_image, "gd_pam_flash_bwd: scratch smaller than gd_pam_bwd_scratch_bytes (one image)");
         // the batch is walked in slices that fit the caller's scratch buffer
         const int slice = (int)(scratch_bytes / per_image < (size_t)B ? scratch_bytes / per_image : (size_t)B);
         for (int b0 = 0; b0 < B; b0 += slice) {
             const int nb = B - b0 < slice ? B - b0 : slice;
             const long o32 = (long)b0 * Npad * 32, oc = (long)b0 * Npad * Cp, on = (long)b0 * N;
-            if (form <= 1) {
-                const long oq = out_bs ? (long)b0 * out_bs : o32, ov = out_bs ? (long)b0 * out_bs : oc;
-                const int rcode = gd_pam_bwd64_slice(q + o32, k + o32, kT + o32, v + oc, dO + oc, lse + on, delta + on, nb, N,
-                                                     Npad, Cp, f16, form == 1, dqn + oq, dkn + oq, dv + ov, out_bs,
-                                                     scratch, stream);
-                if (rcode) return rcode;
-            } else {
-                PAM_DISPATCH_CT(Cp / 32, hipLaunchKernelGGL((pam_bwd_dkv3_kernel<CT, true, 8>), dim3(Npad / 256, nb), dim3(512), 0, s,
-                                                             q + o32, k + o32, kT + o32, v + oc, dO + oc, lse + on, delta + on,
-                                                             N, Npad, dkn + o32, dv + oc, (unsigned short*)scratch));
-                gd_pam_dq_reduce_launch(scratch, Npad / 256, Npad, nb, dqn + o32, stream);
-            }
+            const long oq = out_bs ? (long)b0 * out_bs : o32, ov = out_bs ? (long)b0 * out_bs : oc;
+            const int rcode = gd_pam_bwd64_slice(q + o32, k + o32, kT + o32, v + oc, dO + oc, lse + on, delta + on, nb, N,
+                                                 Npad, Cp, f16, form == 1, dqn + oq, dkn + oq, dv + ov, out_bs,
+                                                 scratch, stream);
+            if (rcode) return rcode;
         }
         GD_LAUNCH_CHECK();
         return 0;
     }
     // two-kernel form: dK / dV (transpose-read kernel, 4 waves = 128 keys, two workgroups per CU), then dQ with a
     // query-parallel kernel that recomputes S and dP (8 waves, 128-key LDS-DMA tiles; kn perm16 along the keys)
-    PAM_DISPATCH_CT(Cp / 32, hipLaunchKernelGGL((pam_bwd_dkv3_kernel<CT, false>), dim3(Npad / 128, B), dim3(256), 0, s, q, k,
-                                                 kT, v, dO, lse, delta, N, Npad, dkn, dv, (unsigned short*)nullptr));
+    PAM_DISPATCH_CT(Cp / 32, hipLaunchKernelGGL((pam_bwd_dkv3_kernel<CT>), dim3(Npad / 128, B), dim3(256), 0, s, q, k,
+                                                 kT, v, dO, lse, delta, N, Npad, dkn, dv));
     PAM_DISPATCH_CT(Cp / 32, hipLaunchKernelGGL((pam_bwd_dq_kernel<CT, 8, 128>), dim3(Npad / 256, B), dim3(512), 0, s, q, k,
                                                  kT, v, dO, lse, delta, N, Npad, dqn));
     GD_LAUNCH_CHECK();

@@ -67,6 +67,38 @@ __global__ __launch_bounds__(256) void pam_dq_transpose_kernel(const float* __re
     }
 }
 
+// dQ^T[b][d][i] = sum over key blocks of the bf16 parts [key block][query][32 d] written by the deterministic
+// backwards: pam_bwd_k64_kernel<.., ATOMIC = false> below (KB = Npad/256) and pam_wide_bwd_dkq_kernel of pam_wide.hip
+// (KB = Npad/128, every 32-wide slice of d counted as an image).
+//   part : (B, KB, Npad, 32) bf16 ; dqn : (B, 32, Npad) fp32.  One workgroup = 64 queries of one image; a key block's
+//   slab for them is 4 KiB contiguous (thread = query x 8 d, 16-byte loads).
+__global__ __launch_bounds__(256) void pam_dq_reduce_kernel(const unsigned short* __restrict__ part, int KB, int Npad,
+                                                           float* __restrict__ dqn) {
+    __shared__ float tile[32][65];
+    const int b = blockIdx.y, i0 = blockIdx.x * 64;
+    const int q = threadIdx.x >> 2, d8 = (threadIdx.x & 3) * 8;
+    const unsigned short* p = part + ((long)b * KB * Npad + i0 + q) * 32 + d8;
+    float acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+#pragma unroll 4
+    for (int kb = 0; kb < KB; ++kb) {
+        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(p + (long)kb * Npad * 32);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            acc[2 * k] += gd_bf2f((unsigned short)(v[k] & 0xFFFFu));
+            acc[2 * k + 1] += gd_bf2f((unsigned short)(v[k] >> 16));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) tile[d8 + k][q] = acc[k];
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 32 * 64; idx += 256) {
+        const int d = idx >> 6, qq = idx & 63;
+        dqn[((long)b * 32 + d) * Npad + i0 + qq] = tile[d][qq];
+    }
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -641,6 +673,11 @@ extern "C" size_t gd_pam_bwd64_scratch_bytes(int Npad, int deterministic) {
     const size_t dq = deterministic ? (size_t)(Npad / 256) * (size_t)Npad * 32 * sizeof(unsigned short)
                                     : (size_t)Npad * 32 * sizeof(float);
     return rcb + dq;
+}
+
+extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int nb, float* dqn, void* stream) {
+    hipLaunchKernelGGL(pam_dq_reduce_kernel, dim3(Npad / 64, nb), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned short*)part, KB, Npad, dqn);
 }
 
 namespace {

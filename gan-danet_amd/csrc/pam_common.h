@@ -184,7 +184,7 @@ struct Chunks {
     }
 
 // entry points that one PAM translation unit calls in another
-extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int nb, float* dqn, void* stream);   // pam.hip
+extern "C" void gd_pam_dq_reduce_launch(const void* part, int KB, int Npad, int nb, float* dqn, void* stream);   // pam_bwd64.hip
 extern "C" size_t gd_pam_bwd64_scratch_bytes(int Npad, int deterministic);                                       // pam_bwd64.hip
 extern "C" int gd_pam_bwd64_slice(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,
                                   const float* lse, const float* delta, int nb, int N, int Npad, int Cp, int f16,

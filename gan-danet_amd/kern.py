@@ -941,8 +941,8 @@ def gemm_nt_plan(*, B: int, M: int, N: int, kseg: int, klen: int, splits: int = 
 
 def pam_bwd_form() -> int:
     """the backward form (gandanet.h GD_PAM_BWD_*) that pam_flash_bwd takes without an explicit ``form``: K64 with fp32
-    atomics for dQ, or under set_deterministic(True) K64 with bf16 parts (bitwise reproducible).  Forms 2 (the round-1 K32
-    kernel with bf16 parts) and 3 (two kernels without scratch) are reached through ``form`` only."""
+    atomics for dQ, or under set_deterministic(True) K64 with bf16 parts (bitwise reproducible).  Form 3 (two kernels without scratch, the
+    reference the K64 forms are tested against) is reached through ``form`` only."""
     return L.PAM_BWD_K64_PARTS if DETERMINISTIC else L.PAM_BWD_K64_ATOMIC
 
 

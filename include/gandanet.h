@@ -417,15 +417,16 @@ int gd_pam_key_sqnorm_max(const void* kt, int B, int N, int Npad, int f16, float
  *                 accumulation registers), dQ summed across key blocks with fp32 atomics (fastest; not bitwise
  *                 reproducible in dQ)
  *   1 K64_PARTS   the same kernel storing dQ as one bf16 part per 256-key block + a streaming sum (reproducible)
- *   2 K32_PARTS   8 waves x 32 keys per workgroup, bf16 dQ parts (the round-1 kernel; reproducible; bf16 only)
- *   3 TWO_KERNEL  dK/dV kernel, then a query-parallel kernel that recomputes S and dP for dQ (no scratch; bf16 only)
+ *   3 TWO_KERNEL  dK/dV kernel, then a query-parallel kernel that recomputes S and dP for dQ (no scratch;
+ *                 reproducible; bf16 only)
+ *   (2 was the K32 parts form, an 8-wave kernel with bf16 dQ parts that form 1 superseded; the number is not reused and is
+ *   rejected like any other unknown form.)
  * out_bs: 0, or (form 0 only) the batch stride in elements shared by dqn, dkn, dv when the caller passes them as row
  *   blocks of ONE (B, rows, Npad) buffer -- the three projection gradients can then run as one GEMM over that buffer.
  * scratch: caller-owned, >= gd_pam_bwd_scratch_bytes(Npad, form) (= one image's worth; more lets more images go per
  * launch); may be NULL for form 3. */
 #define GD_PAM_BWD_K64_ATOMIC 0
 #define GD_PAM_BWD_K64_PARTS 1
-#define GD_PAM_BWD_K32_PARTS 2
 #define GD_PAM_BWD_TWO_KERNEL 3
 size_t gd_pam_bwd_scratch_bytes(int Npad, int form);
 int gd_pam_flash_bwd(const void* qt, const void* kt, const void* kn, const void* vt, const void* dot_,

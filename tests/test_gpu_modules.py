@@ -996,12 +996,11 @@ def test_generator_eval_forward_inference_tiles_vs_oracle(gd, shape):
 
 
 def test_pam_flash_backward_forms_agree_at_bench_and_max_size(gd):
-    """size-independent check where the oracle cannot go: the four backward forms of gd_pam_flash_bwd on the same packed
-    operands -- K64 with fp32 atomics for dQ (default), K64 with bf16 dQ parts, the round-1 K32 kernel with parts, and
-    the two-kernel form that recomputes S / dP for dQ -- at the bench sequence length (N = 256 * 256, C = 184) and at
-    BASELINE config 5's (N = 512 * 512, C = 64).  dK / dV of the two K32-based forms are the same arithmetic
-    (bit-identical); K64 sums the query tiles in a different order (fp32 round-off); dQ through bf16 parts carries their
-    rounding.  The parts forms must be bitwise reproducible."""
+    """size-independent check where the oracle cannot go: the three backward forms of gd_pam_flash_bwd on the same packed
+    operands -- K64 with fp32 atomics for dQ (default), K64 with bf16 dQ parts, and the two-kernel form that recomputes
+    S / dP for dQ (the reference here) -- at the bench sequence length (N = 256 * 256, C = 184) and at BASELINE config
+    5's (N = 512 * 512, C = 64).  K64 sums the query tiles in a different order than the two-kernel form (fp32
+    round-off); dQ through bf16 parts carries their rounding.  The parts form must be bitwise reproducible."""
     from gan_danet_amd import kern as K
     from gan_danet_amd import _lib as L
     for (C, side) in ((184, 256), (64, 512)):
@@ -1032,9 +1031,6 @@ def test_pam_flash_backward_forms_agree_at_bench_and_max_size(gd):
             return dq[:, :r, :N].clone(), dk[:, :r, :N].clone(), dv[:, :C, :N].clone()
 
         ref = run(L.PAM_BWD_TWO_KERNEL)
-        k32 = run(L.PAM_BWD_K32_PARTS)
-        assert torch.equal(k32[1], ref[1]) and torch.equal(k32[2], ref[2])
-        assert_close(k32[0], ref[0].cpu(), 1e-2, f"dQ K32 parts vs recomputed, N={N}", rell2)
         for form, name in ((L.PAM_BWD_K64_ATOMIC, "K64 atomic"), (L.PAM_BWD_K64_PARTS, "K64 parts")):
             got = run(form)
             assert_close(got[1], ref[1].cpu(), 1e-5, f"dK {name}, N={N}", rell2)

@@ -6,6 +6,7 @@ assembly listings made before and after.
     hipcc <build.py FLAGS> --cuda-device-only -S gan-danet_amd/csrc/pam_bwd64.hip -o after.s
     python tools/isa_compare.py k64 before.s after.s
     python tools/isa_compare.py pam_fwd pam_before.s pam_after.s pam_wide_before.s pam_wide_after.s
+    python tools/isa_compare.py dkv3 pam_before.s pam_after.s pam_bwd64_before.s pam_bwd64_after.s
 
 A family (FAMILIES below) names the kernel templates that are one kernel under different names or parameter lists and
 maps each instantiation to its canonical parameters, None for a variant that is not shipped (counted and ignored).
@@ -14,8 +15,9 @@ Normalised before the diff: the mangled kernel symbol, the per-function number i
 .Lfunc_end<n>), comment-only lines.
 Where a pair differs, the line says whether the tile loop (the innermost loop around an s_barrier, where the kernel
 spends its time) is still identical or the same instructions with other register numbers; --diff prints the diff too.
-A kernel passes when its metadata is unchanged, nothing spills (family kernels) and its instructions are identical or differ outside an
-identical / register-renamed tile loop only.  Exit status 0 = every kernel passes."""
+A kernel passes when its metadata is unchanged, nothing spills (family kernels, but for the instantiations a family lists
+as spilling already) and its instructions are identical or differ outside an identical / register-renamed tile loop
+only.  Exit status 0 = every kernel passes."""
 import difflib
 import re
 import sys
@@ -32,9 +34,18 @@ def _k64(a):
     return tuple(a)
 
 
-# family -> (canonical template, parameter names, shipped instantiations, {template name: arguments -> canonical tuple})
+def _dkv3(a):
+    """<CT, DQ, NW> (shipped: DQ = 0, NW = 4; <CT, 1, 8> was the K32 parts form) or <CT>"""
+    if len(a) == 3:
+        return (a[0],) if a[1] == 0 and a[2] == 4 else None
+    return tuple(a)
+
+
+# family -> (canonical template, parameter names, shipped instantiations, {template name: arguments -> canonical tuple}
+#            [, canonical tuples that spill as they stand: their spill count must only stay what it was])
 FAMILIES = {
     "k64": ("pam_bwd_k64_kernel", ("CT", "F16", "ATOMIC"), 24, {"pam_bwd_k64_kernel": _k64}),
+    "dkv3": ("pam_bwd_dkv3_kernel", ("CT",), 6, {"pam_bwd_dkv3_kernel": _dkv3}, {(6,)}),   # CT = 6: 256 VGPRs + 1 spilled
     "pam_fwd": ("pam_fwd_kernel", ("CT", "D", "KT", "ONES", "F16", "MAXFREE", "CHUNKED"), 40, {
         "pam_fwd_kernel": tuple,
         "pam_fwd_dma_kernel": lambda a: (a[0], 32, a[2], a[3], a[4], 1, 0) if a[1] == 8 else None,   # <CT, NW, KT, ONES, F16>
@@ -45,7 +56,8 @@ FAMILIES = {
 
 class Family:
     def __init__(self, name):
-        self.template, self.params, self.shipped, self.maps = FAMILIES[name]
+        self.template, self.params, self.shipped, self.maps = FAMILIES[name][:4]
+        self.spilling = {(self.template, *args) for args in (FAMILIES[name][4] if len(FAMILIES[name]) > 4 else ())}
         self.sym = re.compile(r"_Z\w*?\d+(%s)I((?:L[ib]\d+E)+)E\w*" % "|".join(sorted(self.maps, key=len, reverse=True)))
 
     def canon(self, sym):
@@ -165,7 +177,7 @@ def main():
             continue
         same_isa = b0[k] == b1[k]
         same_meta = all(m0[k][q] == m1[k][q] for q in META_KEYS)
-        clean = isinstance(k, str) or (int(m1[k][".vgpr_spill_count"]) == 0 and int(m1[k][".private_segment_fixed_size"]) == 0)
+        clean = isinstance(k, str) or k in fam.spilling or (int(m1[k][".vgpr_spill_count"]) == 0 and int(m1[k][".private_segment_fixed_size"]) == 0)
         info = "  ".join("%s %s -> %s" % (q[1:].split("_")[0], m0[k][q], m1[k][q]) for q in INFO_KEYS)
         regs = "v%s a%s s%s spill %s scratch %s lds %s" % tuple(m1[k][q] for q in META_KEYS)
         status, same_loop = "identical", True

@@ -1,5 +1,5 @@
 """Interleaved A/B timing of the PAM backward forms (gandanet.h GD_PAM_BWD_*) in ONE process (guide rule 24).
-    python tools/pam_ab.py --forms 0,1,2,3 --rounds 5"""
+    python tools/pam_ab.py --forms 0,1,3 --rounds 5"""
 import argparse
 import os
 import statistics

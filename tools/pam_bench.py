@@ -61,8 +61,8 @@ ksq = K.pam_key_sqnorm_max(kt, N)
 timeit(lambda: K.pam_flash_fwd(qt, kt, vn, B, N, Np, C, Cp, gamma, x, out, o, lse, r_alg=r, v_ones=ones >= 0, k_sqmax=ksq),
        "fwd, max-free", fl)
 d_raw, delta = K.chan_dot(do, o, gamma)
-forms = [int(f) for f in os.environ.get("PAM_BENCH_FORMS", "0,1,2,3").split(",")]
-names = {0: "bwd k64 atomic", 1: "bwd k64 parts", 2: "bwd k32 parts", 3: "bwd 2 kernels"}
+forms = [int(f) for f in os.environ.get("PAM_BENCH_FORMS", "0,1,3").split(",")]
+names = {0: "bwd k64 atomic", 1: "bwd k64 parts", 3: "bwd 2 kernels"}
 ref = None
 for form in forms:
     timeit(lambda: K.pam_flash_bwd(qt, kt, kn, vt, dot_, lse, delta, B, N, Np, Cp, dqn, dkn, dv, r_alg=r, c_alg=C, form=form),
