@@ -23,6 +23,8 @@ from . import timeseries
 from .timeseries import SeriesSkill, coarsen, consistency, harmonic_fit, lstsq_series, skill_maps, taylor_stats
 from . import trend
 from .trend import TrendTest, mann_kendall, normal_quantile, sen_slope, trend_test
+from . import changepoint
+from .changepoint import ChangePoint, ChangePoints, change_point, change_points, cusum, pettitt, segmented_fit
 from .evaluate import RegressionMetrics, evaluate, evaluate_ensemble
 from . import verification
 from .verification import EnsembleVerification, ensemble_scores

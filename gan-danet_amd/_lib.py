@@ -29,6 +29,11 @@ LSTSQ_MAX_P = 8                  # GD_LSTSQ_MAX_P
 TREND_MAX_T = 2048               # GD_TREND_MAX_T
 TREND_MAPS = ("n", "s", "var_s", "z", "p", "tau", "slope", "intercept", "slope_lo", "slope_hi")   # GD_TREND_*: plane k of `out`
 TREND_SEN, TREND_CI, TREND_CONTINUITY = 1, 2, 4   # GD_TREND_SEN, GD_TREND_CI, GD_TREND_CONTINUITY
+CP_MAX_T = 2048                  # GD_CP_MAX_T
+CP_MAPS = ("n", "pt_k", "pt_u", "pt_index", "pt_p", "cs_q", "cs_r", "cs_index", "cs_p", "st_index", "st_mean_before", "st_mean_after",
+           "st_shift", "st_rss0", "st_rss", "st_f", "tr_index", "tr_slope_before", "tr_slope_after", "tr_intercept_before",
+           "tr_intercept_after", "tr_jump", "tr_rss0", "tr_rss", "tr_f")   # GD_CP_*: plane k of `out`
+CP_PETTITT, CP_CUSUM, CP_STEP, CP_TREND = 1, 2, 4, 8   # GD_CP_PETTITT, GD_CP_CUSUM, GD_CP_STEP, GD_CP_TREND
 LAG_MAX, LAG_MAX_T, LAG_CHUNK = 64, 2048, 32   # GD_LAG_MAX, GD_LAG_MAX_T, GD_LAG_CHUNK
 LAG_PLANES = ("best_lag", "best_r", "best_n", "r0")   # GD_LAG_*: plane k of `best`
 LAG_SELECT = {"abs": 0, "max": 1, "min": 2}           # GD_LAG_SELECT_*
@@ -254,6 +259,8 @@ SIGNATURES = {
     "gd_block_mean_host": (_i, [_p, _i, _l, _l, _l, _i, _i, _p, _i, _p, _p]),
     "gd_trend_test": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p, _p]),
     "gd_trend_test_host": (_i, [_p, _i, _l, _l, _p, _i, _p, _i, C.c_double, _p]),
+    "gd_change_point": (_i, [_p, _i, _l, _l, _p, _p, _p, _i, _i, _p, _p]),
+    "gd_change_point_host": (_i, [_p, _i, _l, _l, _p, _p, _p, _i, _i, _p]),
     "gd_lag_corr": (_i, [_p, _p, _i, _l, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "gd_lag_corr_host": (_i, [_p, _p, _i, _l, _l, _l, _i, _i, _i, _i, _p, _p, _p, _p]),
     "gd_series_acf": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p, _p]),

@@ -2112,6 +2112,32 @@ trend_test = functools.partial(_trend_test, _DEV)
 trend_test_host = functools.partial(_trend_test, _HOST)   # plain C++ over the same per-pair arithmetic; sorts the stored slopes
 
 
+# ---- per-pixel change points (include/gandanet.h, "Per-pixel change points"; changepoint.hip) --------------------------------
+def change_point_flags(pettitt: bool, cusum: bool, step: bool, trend: bool) -> int:
+    return (L.CP_PETTITT if pettitt else 0) | (L.CP_CUSUM if cusum else 0) | (L.CP_STEP if step else 0) | (L.CP_TREND if trend else 0)
+
+
+def _change_point(be, x, times, mask=None, window=None, min_seg: int = 5, flags: int = 15, out=None):
+    """Pettitt / CUSUM / two-segment fits of the M series of a dense fp32 / fp64 ``x`` (T, M) at the fp64 ``times`` (T), which
+    the caller of the device entry has checked to be finite and increasing (the host twin looks itself); ``mask``: M uint8;
+    ``window``: (2, M) int32, begin then end of every series.  The planes (L.CP_MAPS) go into ``out`` (25, M) fp64, a new
+    tensor unless one is given; those of families that ``flags`` does not ask for are left as they are.  No host sync."""
+    x, dt = be.array(x, "change_point input", 2)
+    T, M = x.shape
+    times = be.vec(times, T, "change_point times")
+    if not be.host and times.ndim != 1:
+        raise L.GandanetError(f"change_point: {tuple(times.shape)} times for {T} samples")
+    out = be.out(out, (len(L.CP_MAPS), M), be.f64, x, "change_point output")
+    mask = be.vec(mask, None if be.host else M, "change_point mask", be.u8)      # the host twin takes the length on trust
+    window = be.vec(window, 2 * M, "change_point window", be.i32)
+    be.call("gd_change_point", be.ptr(x), dt, T, M, be.ptr(times), be.ptr(mask), be.ptr(window), int(min_seg), int(flags), be.ptr(out))
+    return out
+
+
+change_point = functools.partial(_change_point, _DEV)
+change_point_host = functools.partial(_change_point, _HOST)   # plain C++ over the same per-sample functions, slot by slot
+
+
 # ---- ensemble verification (include/gandanet.h, "Ensemble verification"; ensverify.hip) ------------------------------------
 def ens_verify_flags(f64: bool, fair: bool) -> int:
     return (L.ENSV_F64 if f64 else 0) | (L.ENSV_FAIR if fair else 0)

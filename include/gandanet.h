@@ -1016,6 +1016,63 @@ int gd_trend_test_host(const void* x, int dtype, long T, long M, const double* t
                        int flags, double zq, double* out);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-pixel change points (changepoint.hip, csrc/changepoint_core.h): WHEN did the behaviour of a series change -- the
+ * Pettitt test (Pettitt 1979), the CUSUM statistics of Buishand (1982) and two least-squares two-segment fits (a shift of
+ * the mean; two separate lines) for every series of a (T, M) cube.
+ * The layout is that of "Per-pixel trend tests": series m of a dense (T, M) array at x[t * M + m], storage fp32 (dtype 0) or
+ * fp64 (dtype 1), all arithmetic fp64 with every operation rounded on its own.  2 <= T <= GD_CP_MAX_T.  times: T doubles,
+ * finite and strictly increasing (the device entry does not look: its caller checks; the host twin does).  NaN samples are
+ * dropped from their series; a series that holds an infinity has unspecified outputs.  mask: NULL, or M bytes, 0 = leave
+ * the series out (n = 0).  window: NULL, or 2 M ints, begin[m] followed by end[m]: only the samples begin <= t < end of
+ * series m take part; begin is clamped to 0 .. T and end to begin .. T.  2 <= min_seg <= GD_CP_MAX_T: the smallest number of
+ * valid samples on either side of a candidate break of the two fitted models (above n / 2 there is no candidate).
+ * For one series with the valid samples (t_k, y_k), k = 0 .. n - 1, in time order, i_k their index among the T steps; every
+ * "index" is the i_k of the LAST SAMPLE BEFORE the change, as a double:
+ *   n         the number of valid samples (written whatever the flags).
+ *   GD_CP_PETTITT  V_k = sum over all j of sign(y_k - y_j); U_k = sum over i <= k of V_i, k = 0 .. n - 2 (= sum over i <= k,
+ *             j > k of sign(y_i - y_j)); pt_k = max |U_k|, taken at the smallest such k; pt_u the signed U there (positive:
+ *             the series was higher before the change); pt_index = i_k; pt_p = min(1, 2 exp(-(6 K^2) / (n^3 + n^2))), K =
+ *             pt_k, both integers exact in doubles.  All sums are integers and exact.  n < 2: NaN, index -1.
+ *   GD_CP_CUSUM    ybar = (sum y) / n; S_k = sum over i <= k of (y_i - ybar); ss = sum of (y_i - ybar)^2, each sum sequential in
+ *             time order; sd = sqrt(ss / n); cs_q = (max_k |S_k| / sd) / sqrt(n); cs_r = ((max(0, max S) - min(0, min S)) /
+ *             sd) / sqrt(n); cs_index = i_k at the first maximum of |S_k|; cs_p = 1 where cs_q < 0.3, else
+ *             2 sum over j = 1 .. 20 of (-1)^(j + 1) exp(-2 j^2 q^2), summed in that order and clipped to [0, 1]: the
+ *             Brownian-bridge limit, asymptotic in n.  n < 1 or sd = 0 or NaN: NaN, index -1.
+ *   GD_CP_STEP     candidates are the k with k + 1 >= min_seg and n - k - 1 >= min_seg.  m1, m2 = (sum y) / count of the
+ *             samples i <= k and of the samples i > k, each summed in time order; rss_k = sum over i <= k of (y_i - m1)^2 +
+ *             sum over i > k of (y_i - m2)^2, each sum in time order.  The break is the candidate of the smallest rss_k,
+ *             ties to the smallest k: st_index = i_k, st_mean_before = m1, st_mean_after = m2, st_shift = m2 - m1,
+ *             st_rss0 = ss as above, st_rss = rss_k, st_f = (rss0 - rss) / (rss / (n - 2)) as IEEE division gives it
+ *             (0 / 0 = NaN, x / 0 = inf).  No candidate: every plane NaN, index -1.
+ *   GD_CP_TREND    a segment is fitted in three passes in time order: tbar, ybar = (sum t) / count, (sum y) / count; stt =
+ *             sum of (t - tbar)^2, sty = sum of (t - tbar)(y - ybar), b = sty / stt; rss_seg = sum of ((y - ybar) -
+ *             b (t - tbar))^2; intercept = ybar - b tbar.  rss_k = rss_seg1 + rss_seg2; candidates and selection as for
+ *             STEP.  tr_index = i_k, slopes and intercepts of both lines, tr_jump = line 2 minus line 1 at
+ *             tm = (t_k + t_(k+1)) * 0.5, i.e. (a2 + b2 tm) - (a1 + b1 tm); tr_rss0 = the same three-pass fit over all n
+ *             samples; tr_rss = rss_k; tr_f = ((rss0 - rss) / 2) / (rss / (n - 4)).  No candidate: every plane NaN, index -1.
+ * Neither F statistic is corrected for the selection of the break among the candidates.
+ * out: planar doubles, map k of series m at out[k * M + m], k as below.  flags selects the families; planes of families
+ * that were not asked for are left untouched.
+ * One wave owns a series, its valid (t, y, i) compacted in LDS; lanes own the candidates k in strides of 64 and the loop
+ * over the samples j is uniform across the wave (sample j is an LDS broadcast, added to the "before" or "after"
+ * accumulators by the predicate j <= k); U_k is an integer wave scan of V_k; the arg-max and arg-min are wave reductions
+ * over (value, k) pairs.  No workspace, no global atomics, and a series' result depends on the series and the parameters
+ * alone.  The host twin runs the same per-sample functions of changepoint_core.h in the same order and agrees bit for bit
+ * on every map but pt_p and cs_p (each side's exp).
+ * ---------------------------------------------------------------------------------------- */
+#define GD_CP_MAX_T 2048
+enum { GD_CP_N = 0, GD_CP_PT_K = 1, GD_CP_PT_U = 2, GD_CP_PT_INDEX = 3, GD_CP_PT_P = 4, GD_CP_CS_Q = 5, GD_CP_CS_R = 6,
+       GD_CP_CS_INDEX = 7, GD_CP_CS_P = 8, GD_CP_ST_INDEX = 9, GD_CP_ST_MEAN_BEFORE = 10, GD_CP_ST_MEAN_AFTER = 11,
+       GD_CP_ST_SHIFT = 12, GD_CP_ST_RSS0 = 13, GD_CP_ST_RSS = 14, GD_CP_ST_F = 15, GD_CP_TR_INDEX = 16,
+       GD_CP_TR_SLOPE_BEFORE = 17, GD_CP_TR_SLOPE_AFTER = 18, GD_CP_TR_INTERCEPT_BEFORE = 19, GD_CP_TR_INTERCEPT_AFTER = 20,
+       GD_CP_TR_JUMP = 21, GD_CP_TR_RSS0 = 22, GD_CP_TR_RSS = 23, GD_CP_TR_F = 24, GD_CP_MAPS = 25 };
+enum { GD_CP_PETTITT = 1, GD_CP_CUSUM = 2, GD_CP_STEP = 4, GD_CP_TREND = 8 };
+int gd_change_point(const void* x, int dtype, long T, long M, const double* times, const unsigned char* mask, const int* window,
+                    int min_seg, int flags, double* out, void* stream);
+int gd_change_point_host(const void* x, int dtype, long T, long M, const double* times, const unsigned char* mask,
+                         const int* window, int min_seg, int flags, double* out);
+
+/* ------------------------------------------------------------------------------------------
  * Lagged correlation (lagcorr.hip, csrc/lagcorr_core.h): how many months does storage run behind precipitation, an index or
  * any other driver, pixel by pixel, and how strong is the link at that lag; the autocorrelation of every series; and what a
  * correlation of two autocorrelated series is worth (effective sample size, Fisher z, p).
