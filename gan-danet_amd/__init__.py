@@ -48,6 +48,8 @@ from .lagcorr import (LagCorrelation, autocorrelation, correlation_significance,
 from . import collocation
 from .collocation import (TripleCollocation, TripleCollocationBootstrap, bootstrap_indices, triple_collocation,
                           triple_collocation_bootstrap)
+from . import ssa
+from .ssa import SSAFill, SSAResult, ssa_decompose, ssa_fill
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

@@ -42,6 +42,10 @@ TC_MAX_T, TC_MAX_B, TC_MAX_Q = 2048, 2048, 8   # GD_TC_MAX_T, GD_TC_MAX_B, GD_TC
 TC_STATS = ("err_var_x", "err_var_y", "err_var_z", "rho2_x", "rho2_y", "rho2_z", "beta_y", "beta_z")   # GD_TC_*: plane k of `stats`
 TC_COVS = ("xx", "yy", "zz", "xy", "xz", "yz")   # row k of `cov`
 TC_FLAGS = {"masked": 1, "few": 2, "nonpos": 4, "neg_x": 8, "neg_y": 16, "neg_z": 32, "rho2": 64}   # GD_TC_FLAG_*
+SSA_MAX_M, SSA_MAX_T, SSA_MAX_RANK, SSA_MAX_ITER, SSA_MAX_SWEEPS, SSA_CHUNK = 64, 2048, 16, 200, 30, 8192   # GD_SSA_MAX_*, GD_SSA_CHUNK
+SSA_METHODS = {"bk": 0, "vg": 1}   # GD_SSA_BK, GD_SSA_VG
+SSA_MAPS = ("n", "n_gaps", "mean", "sd", "trace", "sweeps", "iterations", "last_change", "flags")   # GD_SSA_*: plane k of `maps`
+SSA_FLAGS = {"masked": 1, "few": 2, "constant": 4, "nonfinite": 8, "gaps": 16, "sweeps": 32, "iter": 64}   # GD_SSA_FLAG_*
 ENSV_MAX_M, ENSV_F64, ENSV_FAIR = 32, 1, 2   # GD_ENSV_MAX_M, GD_ENSV_F64, GD_ENSV_FAIR
 ENSV_FIELDS = ("n", "tied", "crps", "crps_gauss", "abs_e", "e2", "s2")   # GD_ENSV_*: record slot k; then cover, hist
 ENSV_COVER, ENSV_HIST, ENSV_BINS, ENSV_REC = 7, 11, 33, 44   # GD_ENSV_COVER, GD_ENSV_HIST, GD_ENSV_BINS, GD_ENSV_REC
@@ -272,6 +276,10 @@ SIGNATURES = {
     "gd_tc_bootstrap_workspace": (_sz, [_l, _l, _l]),
     "gd_tc_bootstrap": (_i, [_p, _p, _p, _i, _l, _l, _p, _l, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "gd_tc_bootstrap_host": (_i, [_p, _p, _p, _i, _l, _l, _p, _l, _i, _p, _i, _p, _p, _p, _p]),
+    "gd_ssa_decompose": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "gd_ssa_decompose_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "gd_ssa_fill": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, C.c_double, _i, _i, _p, _p, _p, _p]),
+    "gd_ssa_fill_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, C.c_double, _i, _i, _p, _p, _p]),
     "gd_ens_verify_ws_bytes": (_sz, [_l]),
     "gd_ens_verify": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gd_ens_verify_host": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p]),

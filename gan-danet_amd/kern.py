@@ -3086,3 +3086,50 @@ def _tc_bootstrap(be, x, y, z, idx, q=(0.025, 0.5, 0.975), min_samples: int = 10
 
 tc_bootstrap = functools.partial(_tc_bootstrap, _DEV)
 tc_bootstrap_host = functools.partial(_tc_bootstrap, _HOST)   # plain C++ over the same per-step code, one pixel at a time
+
+
+# ---- singular spectrum analysis (include/gandanet.h, "Singular spectrum analysis"; ssa.hip) ------------------------------------
+def _ssa_args(be, x, window, rank, method, mask, fn: str):
+    x, dt = be.array(x, f"{fn} input", 2)
+    T, P = x.shape
+    for v, nm in ((window, "window"), (rank, "rank")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise L.GandanetError(f"{fn}: {nm} is an integer, got {v!r}")
+    if method not in L.SSA_METHODS:
+        raise L.GandanetError(f"{fn}: method is one of {sorted(L.SSA_METHODS)}, got {method!r}")
+    mask = be.vec(mask, None if be.host else P, f"{fn} mask", be.u8)             # the host twin takes the length on trust
+    return x, dt, int(T), int(P), int(window), int(rank), L.SSA_METHODS[method], mask
+
+
+def _ssa_decompose(be, x, window: int, rank: int, method: str = "bk", mask=None, components: bool = False, vectors: bool = False):
+    """SSA of the P complete series of a dense fp32 / fp64 ``x`` (T, P): new fp64 arrays (eig (rank, P), maps (9, P) in the order
+    of L.SSA_MAPS, rc (rank, T, P) or None), and with ``vectors`` a fourth, the eigenvectors (rank, window, P).  The C entry checks the ranges of T, window and rank.  No host sync."""
+    x, dt, T, P, window, rank, method, mask = _ssa_args(be, x, window, rank, method, mask, "ssa_decompose")
+    eig, maps = be.empty((max(rank, 1), P), be.f64, x), be.empty((len(L.SSA_MAPS), P), be.f64, x)
+    rc = be.empty((max(rank, 1), T, P), be.f64, x) if components else None
+    evec = be.empty((max(rank, 1), max(window, 1), P), be.f64, x) if vectors else None
+    be.call("gd_ssa_decompose", be.ptr(x), dt, T, P, window, rank, method, be.ptr(mask), be.ptr(eig), be.ptr(maps), be.ptr(rc), be.ptr(evec))
+    return (eig, maps, rc, evec) if vectors else (eig, maps, rc)
+
+
+ssa_decompose = functools.partial(_ssa_decompose, _DEV)
+ssa_decompose_host = functools.partial(_ssa_decompose, _HOST)   # the same per-series function with one lane, plain C++
+
+
+def _ssa_fill(be, x, window: int, rank: int, method: str = "bk", mask=None, tol: float = 1e-3, max_iter: int = 20, min_valid=None):
+    """the SSA gap filling of the P series of a dense fp32 / fp64 ``x`` (T, P), NaN = gap: new fp64 arrays (filled (T, P),
+    eig (rank, P), maps (9, P)).  ``min_valid`` defaults to 2 * window.  No host sync."""
+    x, dt, T, P, window, rank, method, mask = _ssa_args(be, x, window, rank, method, mask, "ssa_fill")
+    min_valid = 2 * window if min_valid is None else min_valid
+    for v, nm in ((max_iter, "max_iter"), (min_valid, "min_valid")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise L.GandanetError(f"ssa_fill: {nm} is an integer, got {v!r}")
+    filled = be.empty((T, P), be.f64, x)
+    eig, maps = be.empty((max(rank, 1), P), be.f64, x), be.empty((len(L.SSA_MAPS), P), be.f64, x)
+    be.call("gd_ssa_fill", be.ptr(x), dt, T, P, window, rank, method, be.ptr(mask), float(tol), int(max_iter), int(min_valid), be.ptr(filled),
+            be.ptr(eig), be.ptr(maps))
+    return filled, eig, maps
+
+
+ssa_fill = functools.partial(_ssa_fill, _DEV)
+ssa_fill_host = functools.partial(_ssa_fill, _HOST)

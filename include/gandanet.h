@@ -1651,6 +1651,81 @@ int gd_tc_bootstrap_host(const void* x, const void* y, const void* z, int dtype,
                          int min_samples, const double* q, int Q, const unsigned char* mask, double* summary, int* n_ok,
                          double* replicates);
 
+/* ------------------------------------------------------------------------------------------
+ * Singular spectrum analysis (ssa.hip, csrc/ssa_core.h): the data-adaptive decomposition of every pixel series into a trend
+ * and oscillatory components, and the iterative filling of gaps in time with it (Kondrashov & Ghil 2006; for the gap between
+ * GRACE and GRACE-FO, Yi & Sneeuw 2021).  The layout is that of "Per-pixel time series": x is a dense (T, P) array
+ * (P = M_pixels), series m at x[t * P + m], storage fp32 (dtype 0) or fp64 (dtype 1); NaN marks a gap.  All arithmetic is
+ * fp64 with every operation rounded on its own (nothing is contracted into an FMA); only +, -, *, / and sqrt occur.
+ *   Series       n valid (not NaN) samples, n_gaps = T - n.  mean = (sum of the valid samples in time order) / n;
+ *                sd = sqrt((sum of (v - mean)^2 in time order) / n).  y = x - mean.  The mean is kept FIXED through the
+ *                filling (Kondrashov & Ghil re-estimate it in every iteration; this version does not).
+ *   Limits       window M: 2 <= M <= GD_SSA_MAX_M; K = T - M + 1 >= M, that is 2 M - 1 <= T <= GD_SSA_MAX_T;
+ *                rank r: 1 <= r <= min(M, GD_SSA_MAX_RANK).
+ *   Covariance   of a complete centred series, M x M, every sum in ascending order of its running index from +0.0:
+ *                GD_SSA_BK (Broomhead & King)  C[i][j] = (sum over k = 0 .. K - 1 of y[k + i] * y[k + j]) / K: the trajectory
+ *                  matrix X[k][i] = y[k + i] gives C = X^T X / K, so K times its eigenvalues are the squared singular values of X;
+ *                GD_SSA_VG (Vautard & Ghil)    C[i][j] = c(|i - j|), c(l) = (sum over t = 0 .. T - l - 1 of y[t] * y[t + l]) / (T - l).
+ *                Entries with i <= j are computed, C[j][i] is a copy.
+ *   Eigenpairs   cyclic Jacobi.  The pairs of a sweep come in the 2 ceil(M / 2) - 1 sets of a round robin: with n1 = 2 ceil(M / 2) - 1,
+ *                set s pairs s with n1 and (s + k) mod n1 with (s - k) mod n1, k = 1 .. ceil(M / 2) - 1; a pair is written p < q, and
+ *                the pair that holds the index M of an odd M is a bye.  The rotation of a pair comes from the matrix as the set
+ *                found it: none where |a_pq| <= thr = 2^-52 * (the largest |C[i][i]| of the matrix the solve started from), else
+ *                tau = (a_qq - a_pp) / (2 a_pq), t = sign(tau) / (|tau| + sqrt(tau^2 + 1)) (sign(0) = +1), c = 1 / sqrt(t^2 + 1),
+ *                s = t c.  A set is applied as all column rotations (x_p, x_q) <- (c x_p - s x_q, s x_p + c x_q), then all row
+ *                rotations; an entry depends only on the 2 x 2 block of its row pair and its column pair, so the blocks are
+ *                independent: those with (slot of the row pair) <= (slot of the column pair) are computed, the others are copies
+ *                (the matrix stays exactly symmetric); the block of a pair with itself is a_pp - t a_pq, a_qq + t a_pq and an exact
+ *                0.  The eigenvector matrix takes the column rotations.  Hence a sequential loop and a parallel one give the same
+ *                bits.  Sweeps run until one rotates nothing (that sweep is counted), at most GD_SSA_MAX_SWEEPS (the suite's
+ *                series need at most 14; see tests/ssa_util.py); reaching the cap with a rotating sweep sets
+ *                GD_SSA_FLAG_SWEEPS and the result of the last sweep is used.  Eigenpairs are sorted by descending eigenvalue,
+ *                ties to the lower original index; each eigenvector is signed so that its first entry of largest magnitude is > 0.
+ *                trace = the sum of all M sorted eigenvalues in that order.
+ *   Components   a_k[i] = sum over j = 0 .. M - 1 of y[i + j] * E[j][k], i = 0 .. K - 1; RC_k[t] = (sum over the j of the
+ *                anti-diagonal, max(0, t - K + 1) <= j <= min(M - 1, t), ascending, of a_k[t - j] * E[j][k]) / (their number).  The
+ *                sum of all M components is y.
+ *   Filling      gaps of y start at 0.  For each stage q = 1 .. r, repeat: C of the current y; its eigenpairs; R[t] = RC_0[t] + ..
+ *                + RC_(q-1)[t] (from +0.0, ascending k) at the gap steps; change = max over the gap steps of |R[t] - y[t]| (a NaN
+ *                counts as +inf); y[t] = R[t] at the gap steps only.  A stage ends when change <= tol * sd or after max_iter
+ *                iterations (then GD_SSA_FLAG_ITER is set); stage q + 1 starts from the result of stage q.  filled = x at the valid
+ *                steps (converted to fp64) and mean + y at the gaps.  eig, trace and sweeps are those of the LAST solve (the series
+ *                before its last update).  A series without gaps takes one solve and 0 iterations.
+ *   Degenerate   a series gets NaN in eig, rc, filled and the float planes, and one flag bit for each reason: MASKED (mask[m] == 0;
+ *                mask NULL or P bytes; such a pixel is not read, n = n_gaps = 0), NONFINITE (a sample is +-inf: mean and sd NaN; or the trace of a
+ *                solve is not finite, the squares having overflowed), CONSTANT
+ *                (sd is not > 0), FEW (gd_ssa_fill: n < min_valid, 2 <= min_valid <= GD_SSA_MAX_T), GAPS (gd_ssa_decompose: n < T;
+ *                fill first).  mean and sd are still given where n >= 1 and no sample is infinite.
+ * maps: (GD_SSA_MAPS, P) doubles, planar: n, n_gaps, mean, sd, trace, sweeps (of the last solve), iterations (total over the
+ * stages), last_change, flags (the bits as a number).  eig: (rank, P) doubles.  rc: NULL or (rank, T, P) doubles.  evec
+ * (gd_ssa_decompose): NULL or (rank, M, P) doubles, evec[(k * M + j) * P + m] = E[j][k] of series m.  filled: (T, P)
+ * doubles.  One wave per series, the series, C, E and one principal component in dynamic LDS sized by T and M (above 64 KB the
+ * kernel's dynamic-LDS limit is raised and its return code checked); the pixels are walked GD_SSA_CHUNK series per launch; no
+ * atomics, no workspace; no result depends on P, on a pixel's column or on the chunk.  The *_host twins take every pointer in
+ * HOST memory (no stream) and run the same per-series function with one lane: all outputs agree bit for bit.
+ * Errors (-1, gd_last_error, before any launch): a NULL x, eig, maps or filled; dtype; window, T, rank, method, max_iter,
+ * min_valid out of range; tol not finite or <= 0; M_pixels <= 0 or >= 2^31; a pointer that is not element aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_SSA_MAX_M 64
+#define GD_SSA_MAX_T 2048
+#define GD_SSA_MAX_RANK 16
+#define GD_SSA_MAX_ITER 200
+#define GD_SSA_MAX_SWEEPS 30
+#define GD_SSA_CHUNK 8192
+enum { GD_SSA_BK = 0, GD_SSA_VG = 1 };
+enum { GD_SSA_N = 0, GD_SSA_N_GAPS = 1, GD_SSA_MEAN = 2, GD_SSA_SD = 3, GD_SSA_TRACE = 4, GD_SSA_SWEEPS = 5, GD_SSA_ITERATIONS = 6,
+       GD_SSA_LAST_CHANGE = 7, GD_SSA_FLAGS = 8, GD_SSA_MAPS = 9 };
+enum { GD_SSA_FLAG_MASKED = 1, GD_SSA_FLAG_FEW = 2, GD_SSA_FLAG_CONSTANT = 4, GD_SSA_FLAG_NONFINITE = 8, GD_SSA_FLAG_GAPS = 16,
+       GD_SSA_FLAG_SWEEPS = 32, GD_SSA_FLAG_ITER = 64 };
+int gd_ssa_decompose(const void* x, int dtype, long T, long M_pixels, int window, int rank, int method, const unsigned char* mask,
+                     double* eig, double* maps, double* rc, double* evec, void* stream);
+int gd_ssa_decompose_host(const void* x, int dtype, long T, long M_pixels, int window, int rank, int method, const unsigned char* mask,
+                          double* eig, double* maps, double* rc, double* evec);
+int gd_ssa_fill(const void* x, int dtype, long T, long M_pixels, int window, int rank, int method, const unsigned char* mask, double tol,
+                int max_iter, int min_valid, double* filled, double* eig, double* maps, void* stream);
+int gd_ssa_fill_host(const void* x, int dtype, long T, long M_pixels, int window, int rank, int method, const unsigned char* mask,
+                     double tol, int max_iter, int min_valid, double* filled, double* eig, double* maps);
+
 #ifdef __cplusplus
 }
 #endif
