@@ -50,6 +50,8 @@ from .collocation import (TripleCollocation, TripleCollocationBootstrap, bootstr
                           triple_collocation_bootstrap)
 from . import ssa
 from .ssa import SSAFill, SSAResult, ssa_decompose, ssa_fill
+from . import regions
+from .regions import Regions, kmeans_scan, kmeans_series, region_agreement
 from .generator import (CAMModule, CBAMBlock, DANetAttention, DenseBlock, DenseLayer, FlexibleUpsamplingModule,
                         OriginalRelationshipLearner, PAMModule, SqueezeExcitation, TransitionLayer)
 from .losses import SSIM, BCEWithLogitsLoss, MSELoss, PerceptualLoss, TVLoss

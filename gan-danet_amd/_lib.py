@@ -46,6 +46,7 @@ SSA_MAX_M, SSA_MAX_T, SSA_MAX_RANK, SSA_MAX_ITER, SSA_MAX_SWEEPS, SSA_CHUNK = 64
 SSA_METHODS = {"bk": 0, "vg": 1}   # GD_SSA_BK, GD_SSA_VG
 SSA_MAPS = ("n", "n_gaps", "mean", "sd", "trace", "sweeps", "iterations", "last_change", "flags")   # GD_SSA_*: plane k of `maps`
 SSA_FLAGS = {"masked": 1, "few": 2, "constant": 4, "nonfinite": 8, "gaps": 16, "sweeps": 32, "iter": 64}   # GD_SSA_FLAG_*
+KM_MAX_T, KM_MAX_K, KM_CHUNK, KM_SLAB = 2048, 64, 64, 1024   # GD_KM_MAX_T, GD_KM_MAX_K, GD_KM_CHUNK, GD_KM_SLAB
 ENSV_MAX_M, ENSV_F64, ENSV_FAIR = 32, 1, 2   # GD_ENSV_MAX_M, GD_ENSV_F64, GD_ENSV_FAIR
 ENSV_FIELDS = ("n", "tied", "crps", "crps_gauss", "abs_e", "e2", "s2")   # GD_ENSV_*: record slot k; then cover, hist
 ENSV_COVER, ENSV_HIST, ENSV_BINS, ENSV_REC = 7, 11, 33, 44   # GD_ENSV_COVER, GD_ENSV_HIST, GD_ENSV_BINS, GD_ENSV_REC
@@ -280,6 +281,14 @@ SIGNATURES = {
     "gd_ssa_decompose_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _p, _p, _p, _p]),
     "gd_ssa_fill": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, C.c_double, _i, _i, _p, _p, _p, _p]),
     "gd_ssa_fill_host": (_i, [_p, _i, _l, _l, _i, _i, _i, _p, C.c_double, _i, _i, _p, _p, _p]),
+    "gd_km_assign": (_i, [_p, _i, _l, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gd_km_assign_host": (_i, [_p, _i, _l, _l, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "gd_km_update_ws_bytes": (_sz, [_l, _l, _i]),
+    "gd_km_update_min_ws_bytes": (_sz, [_l, _i]),
+    "gd_km_update": (_i, [_p, _i, _l, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "gd_km_update_host": (_i, [_p, _i, _l, _l, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "gd_km_farthest": (_i, [_p, _l, _p, _i, _p, _p]),
+    "gd_km_farthest_host": (_i, [_p, _l, _p, _i, _p]),
     "gd_ens_verify_ws_bytes": (_sz, [_l]),
     "gd_ens_verify": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gd_ens_verify_host": (_i, [_p, _i, _l, _p, _l, _l, _p, C.c_double, _i, _p, _p, _p, _p, _p]),

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libgandanet_hip.so")
-SOURCES = ["api.hip", "gemm_conv.hip", "conv3x3.hip", "gemm_nt.hip", "norm.hip", "resample.hip", "pointwise.hip", "nhwc.hip", "disc_nhwc.hip", "pam.hip", "pam_bwd64.hip", "pam_wide.hip", "pam_f32.hip", "comm.hip", "histmatch.hip", "det_reduce.hip", "evalstats.hip", "gradguard.hip", "filters.hip", "spline.hip", "prepare.hip", "basins.hip", "stl.hip", "series.hip", "trend.hip", "changepoint.hip", "ensverify.hip", "eof.hip", "spectra.hip", "drought.hip", "ccl.hip", "neighborhood.hip", "quantmap.hip", "lagcorr.hip", "tcol.hip", "ssa.hip", "pam_probe.hip"]
+SOURCES = ["api.hip", "gemm_conv.hip", "conv3x3.hip", "gemm_nt.hip", "norm.hip", "resample.hip", "pointwise.hip", "nhwc.hip", "disc_nhwc.hip", "pam.hip", "pam_bwd64.hip", "pam_wide.hip", "pam_f32.hip", "comm.hip", "histmatch.hip", "det_reduce.hip", "evalstats.hip", "gradguard.hip", "filters.hip", "spline.hip", "prepare.hip", "basins.hip", "stl.hip", "series.hip", "trend.hip", "changepoint.hip", "ensverify.hip", "eof.hip", "spectra.hip", "drought.hip", "ccl.hip", "neighborhood.hip", "quantmap.hip", "lagcorr.hip", "tcol.hip", "ssa.hip", "kmeans.hip", "pam_probe.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

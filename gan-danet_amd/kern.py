@@ -3133,3 +3133,84 @@ def _ssa_fill(be, x, window: int, rank: int, method: str = "bk", mask=None, tol:
 
 ssa_fill = functools.partial(_ssa_fill, _DEV)
 ssa_fill_host = functools.partial(_ssa_fill, _HOST)
+
+
+# ---- regionalisation: k-means on pixel series (include/gandanet.h, "Regionalisation"; kmeans.hip) -----------------------------
+def _km_cube(be, x, cent, fn: str):
+    x, dt = be.array(x, f"{fn} x", 2)
+    T, M = x.shape
+    cent = be.dense(cent, f"{fn} cent", be.f64)
+    if cent.ndim != 2 or cent.shape[1] != T or not 1 <= cent.shape[0] <= L.KM_MAX_K or not 1 <= T <= L.KM_MAX_T:
+        raise L.GandanetError(f"{fn}: cent is (K, {T}) fp64 with 1 <= K <= {L.KM_MAX_K} and T <= {L.KM_MAX_T}, got {tuple(cent.shape)}")
+    return x, dt, int(T), int(M), cent, int(cent.shape[0])
+
+
+def _km_assign(be, x, cent, shift=None, scale=None, mask=None, second: bool = False):
+    """the nearest of the K centroids ``cent`` (K, T) fp64 for the M series of a dense fp32 / fp64 ``x`` (T, M): new arrays
+    (label (M,) int32, dist (M,) fp64, label2, dist2: the second nearest with ``second``, else None).  ``shift`` / ``scale``: M
+    fp64 each, the sample is (x - shift) * scale; ``mask``: M uint8, 0 = leave the series out.  A masked or non-finite series
+    gets -1 / NaN.  No host sync."""
+    x, dt, T, M, cent, K = _km_cube(be, x, cent, "km_assign")
+    shift, scale = be.vec(shift, M, "km_assign shift", be.f64), be.vec(scale, M, "km_assign scale", be.f64)
+    mask = be.vec(mask, M, "km_assign mask", be.u8)
+    label, dist = be.empty((M,), be.i32, x), be.empty((M,), be.f64, x)
+    label2, dist2 = (be.empty((M,), be.i32, x), be.empty((M,), be.f64, x)) if second else (None, None)
+    be.call("gd_km_assign", be.ptr(x), dt, T, M, be.ptr(cent), K, be.ptr(shift), be.ptr(scale), be.ptr(mask), be.ptr(label), be.ptr(dist),
+            be.ptr(label2), be.ptr(dist2))
+    return label, dist, label2, dist2
+
+
+km_assign = functools.partial(_km_assign, _DEV)
+km_assign_host = functools.partial(_km_assign, _HOST)   # plain C++ over the same per-element code
+
+
+def km_update_workspace(T: int, M: int, K: int) -> int:
+    """the bytes that hold the totals and every slab of gd_km_update at once (gd_km_update_ws_bytes)"""
+    return int(lib().gd_km_update_ws_bytes(int(T), int(M), int(K)))
+
+
+def km_update_min_workspace(T: int, K: int) -> int:
+    """the smallest legal workspace: the totals and one slab (gd_km_update_min_ws_bytes)"""
+    return int(lib().gd_km_update_min_ws_bytes(int(T), int(K)))
+
+
+def _km_update(be, x, label, dist, cent, w=None, shift=None, scale=None, ws=None):
+    """the centroid update of ``km_assign``'s ``label`` / ``dist``: new arrays (cent (K, T) fp64: the weighted member means, the
+    row of ``cent`` where a cluster has no weight; wsum (K,) fp64; count (K,) int64; within (K,) fp64, the weighted sums of
+    ``dist``).  ``w``: M fp64 pixel weights.  ``ws``: a uint8 device workspace of at least km_update_min_workspace(T, K) bytes
+    (default: min(km_update_workspace(T, M, K), 256 MiB)); no result depends on its size.  No host sync."""
+    x, dt, T, M, cent, K = _km_cube(be, x, cent, "km_update")
+    label, dist = be.vec(label, M, "km_update label", be.i32), be.vec(dist, M, "km_update dist", be.f64)
+    if label is None or dist is None:
+        raise L.GandanetError("km_update: label and dist are the outputs of km_assign")
+    w, shift, scale = (be.vec(v, M, f"km_update {nm}", be.f64) for v, nm in ((w, "w"), (shift, "shift"), (scale, "scale")))
+    out = cent.copy() if be.host else cent.clone()
+    wsum, within = be.empty((K,), be.f64, x), be.empty((K,), be.f64, x)
+    count = be.empty((K,), np.int64 if be.host else torch.int64, x)
+    nbytes = 0 if be.host else max(min(km_update_workspace(T, M, K), 1 << 28), km_update_min_workspace(T, K))
+    be.call("gd_km_update", be.ptr(x), dt, T, M, be.ptr(label), be.ptr(dist), be.ptr(w), be.ptr(shift), be.ptr(scale), K, be.ptr(out),
+            be.ptr(wsum), be.ptr(count), be.ptr(within), *be.ws(ws, nbytes, x, "km_update"))
+    return out, wsum, count, within
+
+
+km_update = functools.partial(_km_update, _DEV)
+km_update_host = functools.partial(_km_update, _HOST)   # plain C++: the same slabs, added in the same order
+
+
+def _km_farthest(be, d, exclude=None):
+    """the index of the largest finite entry of the fp64 map ``d`` that is not in ``exclude`` (up to L.KM_MAX_K int32 indices),
+    the lowest index on a tie, -1 if there is none: a new (1,) int32 array on the side of ``d``.  No host sync."""
+    d = be.vec(d, None, "km_farthest d", be.f64)
+    if d is None or math.prod(d.shape) == 0:
+        raise L.GandanetError("km_farthest: d is a non-empty fp64 map")
+    exclude = be.vec(exclude, None, "km_farthest exclude", be.i32)
+    ne = 0 if exclude is None else math.prod(exclude.shape)
+    if ne > L.KM_MAX_K:
+        raise L.GandanetError(f"km_farthest: at most {L.KM_MAX_K} excluded indices, got {ne}")
+    index = be.empty((1,), be.i32, d)
+    be.call("gd_km_farthest", be.ptr(d), math.prod(d.shape), be.ptr(exclude) if ne else None, ne, be.ptr(index))
+    return index
+
+
+km_farthest = functools.partial(_km_farthest, _DEV)
+km_farthest_host = functools.partial(_km_farthest, _HOST)

@@ -1726,6 +1726,59 @@ int gd_ssa_fill(const void* x, int dtype, long T, long M_pixels, int window, int
 int gd_ssa_fill_host(const void* x, int dtype, long T, long M_pixels, int window, int rank, int method, const unsigned char* mask,
                      double tol, int max_iter, int min_valid, double* filled, double* eig, double* maps);
 
+/* ------------------------------------------------------------------------------------------
+ * Regionalisation (kmeans.hip, csrc/kmeans_core.h): k-means (Lloyd) on the pixel series of a cube, the step between pixel
+ * maps and a table of regions.  The layout is that of "Per-pixel time series": x is a dense (T, M) array, series m at
+ * x[t * M + m], storage fp32 (dtype 0) or fp64 (dtype 1).  1 <= T <= GD_KM_MAX_T, 1 <= K <= GD_KM_MAX_K, 0 < M < 2^31.  All
+ * arithmetic is fp64 with every operation rounded on its own (nothing is contracted into an FMA); no floating-point atomics;
+ * no result depends on the run, on the alignment of x beyond element alignment or on the size of a workspace, and a result
+ * of gd_km_assign for series m depends on that series, its shift / scale and the centroids alone (not on M).
+ *   Sample       v[t] = (x[t * M + m] - shift[m]) * scale[m]; a NULL shift counts as 0.0, a NULL scale as 1.0 (both exact), so
+ *                centred or z-scored clustering needs no second copy of the cube.  shift, scale: NULL or M doubles.
+ *   Distance     d[k] = sum over t = 0 .. T - 1, ascending from +0.0, of (v[t] - cent[k * T + t])^2, each term one subtraction
+ *                and one square: never the |x|^2 - 2 x.c + |c|^2 form, which cancels.  cent: (K, T) doubles, finite.
+ *   gd_km_assign label (M) int32: the k of the smallest d[k], the lower k on a tie; dist (M) doubles: that d.  label2 / dist2
+ *                (each NULL or M entries): the smallest among the other k, the lower k on a tie; -1 / NaN when K = 1.  A series
+ *                with mask[m] == 0 (mask NULL or M bytes; it is not read) or with a v[t] that is NaN or +-inf gets label -1,
+ *                label2 -1 and NaN distances: listwise, as in the EOF analysis; fill gaps first (gd_ssa_fill).
+ *   gd_km_update With a[m] = w[m] (w NULL: 1.0; M doubles, e.g. cos lat) over the members of cluster k (label[m] == k; a label
+ *                outside 0 .. K - 1 belongs to none): wsum[k] = sum a, count[k] = their number (int64), within[k] = sum of
+ *                a * dist[m] (the total over k is the inertia), and cent[k * T + t] = (sum of a * v[t]) / wsum[k].  A cluster
+ *                whose wsum is not > 0 (no member, or zero weights) keeps the centroid it came with: cent is in / out.
+ *                The order of every sum: the pixels are cut into slabs of GD_KM_SLAB neighbouring series; a slab's sum runs
+ *                over its members in ascending m from +0.0; the slab sums are added in ascending slab order onto a total that
+ *                starts at +0.0.  workspace: gd_km_update_ws_bytes(T, M, K) bytes hold the totals and all slabs, (1 +
+ *                ceil(M / GD_KM_SLAB)) * (K * T + 3 * K) doubles; with fewer, down to gd_km_update_min_ws_bytes(T, K) (the totals
+ *                and one slab), the slabs are walked in chunks and the result has the same bits; less is an error.
+ *   gd_km_farthest index[0] = the i of the largest d[i] that is finite, i not in exclude[0 .. n_exclude - 1] (0 <= n_exclude <=
+ *                GD_KM_MAX_K; NULL with 0), the lowest i on a tie; -1 if there is none.  d: M doubles.  It serves the maximin
+ *                initialisation and the re-seating of empty clusters.
+ * gd_km_assign: a workgroup of 256 neighbouring series, one per thread, reads each row segment once (coalesced); the centroids
+ * are staged in LDS GD_KM_CHUNK time steps at a time and read as wave-uniform broadcasts; the K sums live in registers (the
+ * kernel is a template on K rounded up to 8 / 16 / 32 / 64).  The cube is read once whatever K is.
+ * The *_host twins take every pointer in HOST memory (no workspace, no stream) and run the same per-element code in the same
+ * order: all outputs agree bit for bit.
+ * Errors (-1, gd_last_error, before any launch): a NULL x, cent, label, dist (wsum, count, within, d, index); dtype; T, K,
+ * n_exclude out of range; M <= 0 or >= 2^31; a pointer that is not element aligned; a workspace that is NULL or too small.
+ * ---------------------------------------------------------------------------------------- */
+#define GD_KM_MAX_T 2048
+#define GD_KM_MAX_K 64
+#define GD_KM_CHUNK 64
+#define GD_KM_SLAB 1024
+int gd_km_assign(const void* x, int dtype, long T, long M, const double* cent, int K, const double* shift, const double* scale,
+                 const unsigned char* mask, int* label, double* dist, int* label2, double* dist2, void* stream);
+int gd_km_assign_host(const void* x, int dtype, long T, long M, const double* cent, int K, const double* shift, const double* scale,
+                      const unsigned char* mask, int* label, double* dist, int* label2, double* dist2);
+size_t gd_km_update_ws_bytes(long T, long M, int K);
+size_t gd_km_update_min_ws_bytes(long T, int K);
+int gd_km_update(const void* x, int dtype, long T, long M, const int* label, const double* dist, const double* w, const double* shift,
+                 const double* scale, int K, double* cent, double* wsum, long long* count, double* within, void* workspace,
+                 size_t workspace_bytes, void* stream);
+int gd_km_update_host(const void* x, int dtype, long T, long M, const int* label, const double* dist, const double* w,
+                      const double* shift, const double* scale, int K, double* cent, double* wsum, long long* count, double* within);
+int gd_km_farthest(const double* d, long M, const int* exclude, int n_exclude, int* index, void* stream);
+int gd_km_farthest_host(const double* d, long M, const int* exclude, int n_exclude, int* index);
+
 #ifdef __cplusplus
 }
 #endif
